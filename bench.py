@@ -28,11 +28,6 @@ import subprocess
 import sys
 import time
 
-# The engine's streaming pipeline runs the optimiser, the fits and two scan launches on four streams beside the context's own; torch and
-# RCCL create streams too.  With the runtime's default of 4 hardware queues they share queues and serialise one another (measured in the
-# one-rank-per-GPU mode: packed route 5.0 -> 6.1 ms per step at 8 paths); 8 queues keep them apart.  Must be set before HIP initialises.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-
 ROOT = os.path.dirname(os.path.abspath(__file__))
 for _p in (ROOT, os.path.join(ROOT, "pathfinder.jl_amd"), os.path.join(ROOT, "tests")):
     if _p not in sys.path:
@@ -51,6 +46,50 @@ def _blocks(K, G):
     for g in range(G):
         b.append(b[-1] + base + (1 if g < rem else 0))
     return b
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def _dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: write what the timed path's caller received in the last timed step as `out_dir/<name>.npy`, float64 (the
+    integer results are exact in it), so that two builds can be compared output for output.  If the arrays exceed `limit` bytes in all,
+    the largest ones are cut, in turn, to a fixed seeded sample of their last axis (columns of the draws), whose indices are written as
+    `<name>_sample_index.npy`."""
+    out = {k: np.atleast_1d(np.asarray(v, dtype=np.float64)) for k, v in arrays.items() if v is not None}
+    total = sum(a.nbytes for a in out.values())
+    for name in sorted(out, key=lambda k: -out[k].nbytes):
+        if total <= limit:
+            break
+        a = out[name]
+        n = a.shape[-1]
+        keep = int(max(1, (limit - (total - a.nbytes)) // (a.nbytes // n + 8)))
+        sel = np.sort(np.random.default_rng(20260928).choice(n, size=min(keep, n), replace=False))
+        out[name], out[name + "_sample_index"] = a[..., sel], sel.astype(np.float64)
+        total += out[name].nbytes + out[name + "_sample_index"].nbytes - a.nbytes
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
+def _elbo_outputs(elbo, se):
+    """the ELBO table as --dump-outputs writes it.  NaN marks a point without a fit (each path's starting point, a failed fit;
+    include/pfmi.h), not an estimate: the table is written at the points that have one, with their positions in it."""
+    fit = np.flatnonzero(~np.isnan(elbo))
+    return {"elbo": elbo[fit], "elbo_se": se[fit], "elbo_fit_index": fit}
+
+
+def _strip_option(argv, opt):
+    """argv without `opt VALUE` / `opt=VALUE`"""
+    out, skip = [], False
+    for a in argv:
+        if skip:
+            skip = False
+        elif a == opt:
+            skip = True
+        elif not a.startswith(opt + "="):
+            out.append(a)
+    return out
 
 
 def _self_launch(ngpus):
@@ -213,7 +252,8 @@ def main_single_process(args):
             e.elbo_batch_enqueue(N_e, sd)
             e.pool_build_best(N_r)
         res, idx, state["draws"] = comm.psis_resample(ndraws, seed=master)
-        state["best"] = [e.elbo_batch_wait()[2] for e in engs]
+        state["tabs"] = [e.elbo_batch_wait() for e in engs]
+        state["best"] = [t[2] for t in state["tabs"]]
         state.update(pareto_k=res["pareto_shape"], tail=res["tail_length"], idx=idx)
 
     # the end-to-end call as pfmi.multipathfinder(engines=[...]) makes it: ONE host thread schedules G streaming pipelines (optimise + fit +
@@ -263,6 +303,11 @@ def main_single_process(args):
     for e in engs:
         e.sync()
     ms_per_step = (time.perf_counter() - t0) / args.steps * 1e3
+    if args.dump_outputs:
+        tabs = state["tabs"]
+        _dump_outputs(args.dump_outputs, {**_elbo_outputs(np.concatenate([t[0] for t in tabs]), np.concatenate([t[1] for t in tabs])),
+                                          "best_iter": np.concatenate(state["best"]), "pareto_k": state["pareto_k"],
+                                          "tail_length": state["tail"], "resample_indices": state["idx"], "draws": state["draws"]})
     host_line = None
     if not args.host_traces:
         import gc
@@ -354,10 +399,16 @@ def main():
     ap.add_argument("--no-verify-sharding", action="store_true")
     ap.add_argument("--maxiters", type=int, default=1000)
     ap.add_argument("--init-scale", type=float, default=2.0)
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps write what the last timed step returned (ELBO estimates and SE of the points that have a "
+                         "fit, with their positions in the table; best iterations, k-hat, tail length, resample indices, draws) as "
+                         "DIR/<name>.npy, float64, at most 64 MB in all (rank 0)")
     args = ap.parse_args()
 
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.single_process:
         return main_single_process(args)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -461,7 +512,7 @@ def main():
             elbo, se, best = eng.elbo_batch_wait()
             eng.defer(0)
             res, idx, state["draws"] = comm.psis_resample_wait(want_draws=(rank == 0))    # ... and this ONE wait delivers everything
-            state.update(elbo=elbo, best=best, pareto_k=res["pareto_shape"], tail=res["tail_length"], idx=idx)
+            state.update(elbo=elbo, se=se, best=best, pareto_k=res["pareto_shape"], tail=res["tail_length"], idx=idx)
             return
         raise RuntimeError("no communicator")
 
@@ -491,6 +542,10 @@ def main():
         step()
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        _dump_outputs(args.dump_outputs, {**_elbo_outputs(state["elbo"], state["se"]), "best_iter": state["best"],
+                                          "pareto_k": state["pareto_k"], "tail_length": state["tail"], "resample_indices": state["idx"],
+                                          "draws": state["draws"]})
     stages, scan_ms, scan_n = {}, 0.0, 0
     if timed_stages:
         for name in ("history", "fit", "elbo_draws", "elbo_draws_x", "elbo_reduce", "psis", "resample", "comm_handshake_host", "comm_allgather",
@@ -779,7 +834,7 @@ def main():
                               "2 waves per SIMD, no MFMA/VALU co-issue (profiles/r02_coissue_microbench.txt, profiles/r03_*)"}
         traffic, traffic_meta = None, None
         if not args.no_pmc and not args.minimal and G == 1 and not use_dist:
-            pmc, why = _pmc_traffic([a for a in sys.argv[1:] if a not in ("--no-cpu-baseline",)],
+            pmc, why = _pmc_traffic([a for a in _strip_option(sys.argv[1:], "--dump-outputs") if a not in ("--no-cpu-baseline",)],
                                     {"scan": "%pf_elbo_qf_kernel%", "writer": "%pf_elbo_xw_kernel%", "reader": "%pfx_%"})
             if pmc is not None and "scan" in pmc:
                 traffic, traffic_meta = pmc["scan"]["traffic_bytes_per_launch"], pmc["scan"]

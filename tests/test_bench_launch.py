@@ -38,3 +38,33 @@ def test_world_size_must_match_gpus():
     assert r.returncode != 0 and "WORLD_SIZE=1" in r.stderr
     r = _run(["--gpus", "1"], {"PFMI_BENCH_LAUNCH_ONLY": "1", "WORLD_SIZE": "2", "RANK": "0"})
     assert r.returncode != 0 and "--gpus 1" in r.stderr
+
+
+def test_steps_must_be_positive():
+    r = _run(["--steps", "0"], {"PFMI_BENCH_LAUNCH_ONLY": "1"})
+    assert r.returncode != 0 and "--steps must be >= 1" in r.stderr
+
+
+def test_dump_outputs_is_float64_deterministic_and_at_most_64_mb(tmp_path):
+    """--dump-outputs writes every array as float64; over 64 MB the draws are cut to the same seeded sample of their columns every run."""
+    import numpy as np
+    import bench
+    draws = np.arange(3000 * 4000, dtype=np.float64).reshape(3000, 4000)      # 96 MB
+    arrays = {"draws": draws, "elbo": np.array([np.nan, 1.5, -2.0]), "best_iter": np.array([2, 7], dtype=np.int64), "pareto_k": 0.7}
+    for run in ("a", "b"):
+        bench._dump_outputs(str(tmp_path / run), arrays)
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    again = {f[:-4]: np.load(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")}
+    assert sorted(got) == ["best_iter", "draws", "draws_sample_index", "elbo", "pareto_k"] == sorted(again)
+    assert all(a.dtype == np.float64 and np.array_equal(a, again[k], equal_nan=True) for k, a in got.items())
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    sel = got["draws_sample_index"].astype(np.int64)
+    assert len(sel) > 2000 and np.all(np.diff(sel) > 0) and np.array_equal(got["draws"], draws[:, sel])
+    np.testing.assert_array_equal(got["elbo"], arrays["elbo"])
+    assert got["best_iter"].tolist() == [2.0, 7.0] and got["pareto_k"].tolist() == [0.7]
+    tab = bench._elbo_outputs(np.array([np.nan, -3.0, -2.5, np.nan, np.nan, -1.0]), np.array([np.nan, 0.1, 0.2, np.nan, np.nan, 0.3]))
+    assert tab["elbo_fit_index"].tolist() == [1, 2, 5] and tab["elbo"].tolist() == [-3.0, -2.5, -1.0] and tab["elbo_se"].tolist() == [0.1, 0.2, 0.3]
+    small = {"draws": draws[:, :10], "idx": np.arange(10)}
+    bench._dump_outputs(str(tmp_path / "c"), small)
+    assert sorted(os.listdir(tmp_path / "c")) == ["draws.npy", "idx.npy"]
+    np.testing.assert_array_equal(np.load(tmp_path / "c" / "draws.npy"), draws[:, :10])

@@ -180,6 +180,34 @@ def test_bench_force_dist_counts_its_ranks(comm_mode):
     assert line["value"] > 0 and line["roofline"]["frac"] > 0
 
 
+def test_bench_dump_outputs_are_the_results_of_the_last_timed_step(tmp_path):
+    """bench.py --dump-outputs: what the timed path returned in its last step, float64.  The inputs are the same seeded ones in every run and
+    a step recomputes from them, so 1 and 3 timed steps dump the same bits; the JSON line's steps / ms_per_step follow --steps."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    dumps = {}
+    for steps in (1, 3):
+        out = tmp_path / f"steps{steps}"
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1",
+                            "--npaths", "8", "--dim", "100", "--target", "diag", "--ndraws", "300", "--minimal", "--no-cpu-baseline",
+                            "--no-pmc", "--dump-outputs", str(out)], capture_output=True, text=True, env=env, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert line["steps"] == steps and line["ms_per_step"] > 0
+        dumps[steps] = {f[:-4]: np.load(out / f) for f in os.listdir(out)}
+    a, b = dumps[1], dumps[3]
+    assert sorted(a) == ["best_iter", "draws", "elbo", "elbo_fit_index", "elbo_se", "pareto_k", "resample_indices", "tail_length"] == sorted(b)
+    for k in a:
+        assert a[k].dtype == np.float64 and np.all(np.isfinite(a[k])) and np.array_equal(a[k], b[k]), k
+    assert a["draws"].shape == (100, 300)
+    assert len(a["best_iter"]) == 8 and a["resample_indices"].shape == (300,)
+    # the NaN entries of the ELBO table (the 8 starting points, failed fits) are not written: the estimates come with their positions
+    fit = a["elbo_fit_index"]
+    assert len(a["elbo"]) == len(a["elbo_se"]) == len(fit) > 8 and fit[0] >= 1 and np.all(np.diff(fit) > 0)
+
+
 # ---- ADVICE r3 -----------------------------------------------------------------------------------------------------------------
 def test_context_destroyed_before_its_communicator(pfmi_mod):
     """A host with unordered finalisers (Julia's GC at exit) may destroy a pfmi_ctx before the pfmi_comm that borrows it:
