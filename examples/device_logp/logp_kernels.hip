@@ -12,6 +12,8 @@
 //   pfx_gauss_create / pfx_gauss_destroy   parameters -> device-resident handle (the closure's `user`)
 //   pfx_gauss_logp                         the closure (pfmi_logp_dev_fn)
 //   pfx_funnel_logp                        the closure for the funnel (user = NULL)
+//   pfx_gauss_logp_grad / pfx_funnel_logp_grad   value-and-gradient closures of the same targets (pfmi_set_target_gradient): out_dev[n]
+//                                          logp, then out_dev[n + j d + i] = d logp / d x_i at column j -- what the device optimiser calls
 //   pfx_host_gauss_create / _destroy / pfx_host_gauss_logp    the same Gaussian family as a compiled HOST closure (pfmi_logp_fn): what a
 //                                          C / Julia caller's `logp` looks like to the library -- re-entrant, so pfmi_set_callback_threads
 //                                          (the reference's ntasks) may call it from several threads at once
@@ -159,6 +161,86 @@ __global__ __launch_bounds__(PFX_THREADS) void pfx_funnel_kernel(int d, const do
     }
 }
 
+// value and gradient, one workgroup per column (the optimiser hands over K columns per round: latency, not bandwidth, is what counts).
+// grad logp = -(a o e) + Wd G'G Wd'e (pfmi/targets.py: GaussTarget.grad); logp as pfx_gauss_kernel.
+__global__ __launch_bounds__(PFX_THREADS) void pfx_gauss_grad_kernel(Gauss P, const double *__restrict__ X, long long n, double *__restrict__ out) {
+    __shared__ double red[PFX_WAVES][17];
+    __shared__ double hv[16];
+    const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63, d = P.d, r = P.r;
+    for (long long c = blockIdx.x; c < n; c += gridDim.x) {
+        const double *x = X + (size_t)c * d;
+        double v[17];
+#pragma unroll
+        for (int j = 0; j < 17; ++j) v[j] = 0.0;
+        for (int i = tid; i < d; i += PFX_THREADS) {
+            const double e = x[i] - P.mean[i];
+            v[16] = fma(P.a[i] * e, e, v[16]);
+#pragma unroll
+            for (int j = 0; j < 16; ++j) v[j] = fma(P.wd16[(size_t)i * 16 + j], e, v[j]);
+        }
+#pragma unroll
+        for (int j = 0; j < 17; ++j) {
+#pragma unroll
+            for (int o = 32; o >= 1; o >>= 1) v[j] += __shfl_xor(v[j], o, 64);
+        }
+        if (lane == 0) {
+#pragma unroll
+            for (int j = 0; j < 17; ++j) red[wv][j] = v[j];
+        }
+        __syncthreads();
+        if (tid == 0) {
+            double t[16], gt[16], q = 0.0, corr = 0.0;
+            for (int j = 0; j < 16; ++j) { double s = 0.0; for (int w = 0; w < PFX_WAVES; ++w) s += red[w][j]; t[j] = s; }
+            for (int w = 0; w < PFX_WAVES; ++w) q += red[w][16];
+            for (int j = 0; j < r; ++j) {
+                double s = 0.0;
+                for (int l = 0; l <= j; ++l) s = fma(P.g[j * 16 + l], t[l], s);
+                gt[j] = s;
+                corr = fma(s, s, corr);
+            }
+            for (int l = 0; l < 16; ++l) {
+                double s = 0.0;
+                for (int j = l; j < r; ++j) s = fma(P.g[j * 16 + l], gt[j], s);
+                hv[l] = l < r ? s : 0.0;
+            }
+            out[c] = P.offset - 0.5 * (q - corr);
+        }
+        __syncthreads();
+        double *gout = out + n + (size_t)c * d;
+        for (int i = tid; i < d; i += PFX_THREADS) {
+            double gi = -P.a[i] * (x[i] - P.mean[i]);
+            for (int j = 0; j < r; ++j) gi = fma(P.wd16[(size_t)i * 16 + j], hv[j], gi);
+            gout[i] = gi;
+        }
+        __syncthreads();
+    }
+}
+
+// funnel: d logp / d tau = -(2 tau / 9 + (d - 1) - exp(-tau) sum x_i^2) / 2, d logp / d x_i = -exp(-tau) x_i
+__global__ __launch_bounds__(PFX_THREADS) void pfx_funnel_grad_kernel(int d, const double *__restrict__ X, long long n, double *__restrict__ out) {
+    __shared__ double red[PFX_WAVES];
+    const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
+    for (long long c = blockIdx.x; c < n; c += gridDim.x) {
+        const double *x = X + (size_t)c * d;
+        double s = 0.0;
+        for (int i = 1 + tid; i < d; i += PFX_THREADS) s = fma(x[i], x[i], s);
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
+        if (lane == 0) red[wv] = s;
+        __syncthreads();
+        double ss = 0.0;
+        for (int w = 0; w < PFX_WAVES; ++w) ss += red[w];
+        const double tau = x[0], t3 = tau / 3.0, ee = exp(-tau);
+        double *gout = out + n + (size_t)c * d;
+        if (tid == 0) {
+            out[c] = (t3 * t3 + (double)(d - 1) * tau + ss * ee) / -2.0;
+            gout[0] = -(2.0 * tau / 9.0 + (double)(d - 1) - ee * ss) / 2.0;
+        }
+        for (int i = 1 + tid; i < d; i += PFX_THREADS) gout[i] = -ee * x[i];
+        __syncthreads();
+    }
+}
+
 bool ok(hipError_t e, const char *what) {
     if (e == hipSuccess) return true;
     fprintf(stderr, "device_logp: %s failed: %s\n", what, hipGetErrorString(e));
@@ -219,6 +301,21 @@ void pfx_funnel_logp(const double *X_dev, int32_t d, int64_t n, double *out_dev,
     if (n <= 0) return;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(pfx_funnel_kernel, dim3(grid_for((n + PFX_WAVES - 1) / PFX_WAVES)), dim3(PFX_THREADS), 0, s, (int)d, X_dev,
+                       (long long)n, out_dev);
+}
+
+// value-and-gradient closures (pfmi_set_target_gradient): out_dev[0..n) logp, out_dev[n + j d + i] grad
+void pfx_gauss_logp_grad(const double *X_dev, int32_t d, int64_t n, double *out_dev, void *stream, void *user) {
+    const Gauss *P = reinterpret_cast<const Gauss *>(user);
+    if (!P || d != P->d || n <= 0) return;
+    hipLaunchKernelGGL(pfx_gauss_grad_kernel, dim3(grid_for(n)), dim3(PFX_THREADS), 0, reinterpret_cast<hipStream_t>(stream), *P, X_dev,
+                       (long long)n, out_dev);
+}
+
+void pfx_funnel_logp_grad(const double *X_dev, int32_t d, int64_t n, double *out_dev, void *stream, void *user) {
+    (void)user;
+    if (n <= 0) return;
+    hipLaunchKernelGGL(pfx_funnel_grad_kernel, dim3(grid_for(n)), dim3(PFX_THREADS), 0, reinterpret_cast<hipStream_t>(stream), (int)d, X_dev,
                        (long long)n, out_dev);
 }
 

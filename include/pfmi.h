@@ -127,7 +127,8 @@ int32_t pfmi_set_traces(pfmi_ctx *ctx, int32_t K, const int64_t *npoints, int32_
  * traces resident in HBM exactly as pfmi_set_traces would (so pfmi_fit_batch follows without a host round trip).
  * This repo's own driver (two-loop recursion, strong-Wolfe line search, maxiters as src/optimize.jl:40, stop at
  * |grad|_inf <= g_tol); Optim.LBFGS + HagerZhang of the reference is third party: trajectory parity unpinned.
- * npoints[k] = L_k + 1 out.  Callback targets -> PFMI_ERR_UNSUPPORTED (optimise on the host, pfmi_set_traces). */
+ * npoints[k] = L_k + 1 out.  Callback targets -> PFMI_ERR_UNSUPPORTED (optimise on the host, pfmi_set_traces), except a DEVICE_CALLBACK
+ * target with a gradient closure (pfmi_set_target_gradient below). */
 int32_t pfmi_optimize_batch(pfmi_ctx *ctx, int32_t K, const double *x0, int32_t history_length, int32_t maxiters,
                             double g_tol, int64_t *npoints);
 /* The same in two halves, for ONE host thread that drives several contexts (one per GPU, src/multipath.jl:190-208 fans the runs
@@ -136,6 +137,26 @@ int32_t pfmi_optimize_batch(pfmi_ctx *ctx, int32_t K, const double *x0, int32_t 
 int32_t pfmi_optimize_batch_enqueue(pfmi_ctx *ctx, int32_t K, const double *x0, int32_t history_length, int32_t maxiters,
                                     double g_tol);
 int32_t pfmi_optimize_batch_wait(pfmi_ctx *ctx, int64_t *npoints);
+
+/* ---- trajectory generation for a user closure (optional gradient of a DEVICE_CALLBACK target) ------------------------------------------ */
+/* Attaches a value-and-gradient closure to the ctx's current DEVICE_CALLBACK target (any other kind: PFMI_ERR_ARG).  It has the
+ * pfmi_logp_dev_fn signature with a wider output: out_dev[0..n) receives logp of each column and out_dev[n + j * d + i] receives
+ * d logp / d x_i at column j (the d x n layout of X).  It enqueues on the stream it is given -- for the optimiser always the ctx's main
+ * stream -- and returns without synchronising.  pfmi_set_target clears it.  With it, pfmi_optimize_batch / _enqueue / _wait accept the
+ * target (history_length 1..32, d bounded by memory): the K paths run the same L-BFGS as for the built-in targets in ROUNDS -- one
+ * library kernel advances every path by one function evaluation, then the closure is called once on all K trial points (d x K,
+ * column-major, in HBM).  The traces end up resident exactly as for a built-in target.  _enqueue launches the first round only; the
+ * closure is called on the thread that pumps (pfmi_optimize_batch_pump, or _wait, which pumps until done). */
+int32_t pfmi_set_target_gradient(pfmi_ctx *ctx, pfmi_logp_dev_fn logp_grad_fn, void *user);
+/* one non-blocking scheduling pass of a closure optimisation (modelled on pfmi_stream_pump; one host thread may drive several contexts):
+ * keeps at most 4 rounds in flight and reads the rounds' published count of running paths.  *finished = 1 once it has read zero (or the
+ * hard cap of maxiters * 55 + 1 rounds, the line search's evaluation budget, is reached); then call pfmi_optimize_batch_wait. */
+int32_t pfmi_optimize_batch_pump(pfmi_ctx *ctx, int32_t *finished);
+/* gives up an outstanding closure optimisation (e.g. the closure failed on the host): drains this ctx's stream and forgets the call; the
+ * context stays usable.  No-op otherwise.  pfmi_set_target, pfmi_set_traces and pfmi_optimize_batch_enqueue do the same implicitly. */
+int32_t pfmi_optimize_batch_cancel(pfmi_ctx *ctx);
+/* rounds and columns handed to the closure in the last closure optimisation (0, 0 after a built-in one) */
+int32_t pfmi_optimize_stats(pfmi_ctx *ctx, int64_t *rounds, int64_t *closure_columns);
 /* OptimizationTrace of path k (src/optimize.jl:94-100): theta/grad (L_k+1) x d point-major, logp L_k+1; any may be
  * NULL.  logp is only available for traces made by pfmi_optimize_batch. */
 int32_t pfmi_get_trace(pfmi_ctx *ctx, int32_t k, double *theta, double *logp, double *grad);

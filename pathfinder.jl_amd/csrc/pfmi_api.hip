@@ -316,11 +316,21 @@ static void stream_abandon(pfmi_ctx *c) {
     c->stream_pending = false;
 }
 
+// a closure optimisation that was never waited for: its rounds still write the staging trace and the closure's buffers on the ctx stream.
+// Drains THIS ctx's stream (never the device) and forgets the call; `active` is only cleared here, so no failure path can skip the drain.
+static void lbc_abandon(pfmi_ctx *c) {
+    if (!c->lbc.active) return;
+    (void)hipStreamSynchronize(c->stream);
+    c->lbc.active = false;
+    c->opt_pending = false;
+}
+
 int32_t pfmi_destroy(pfmi_ctx *c) {
     if (!c) return PFMI_OK;
     pf_comm_ctx_dying(c);                   // communicators that borrow this context close themselves first (any finaliser order is safe)
     (void)hipSetDevice(c->device);
     stream_abandon(c);
+    lbc_abandon(c);
     (void)hipStreamSynchronize(c->stream);
     DevBuf *bufs[] = {&c->theta, &c->grad, &c->d_off, &c->d_path_of, &c->target.mean, &c->target.a, &c->target.wd,
                       &c->target.g, &c->target.wd16, &c->alpha_all, &c->hist_len, &c->hist_src, &c->hist_acc, &c->n_rej, &c->vh, &c->tmat, &c->vchol,
@@ -329,7 +339,8 @@ int32_t pfmi_destroy(pfmi_ctx *c) {
                       &c->pool_lr, &c->pool_lp, &c->pool_lq, &c->pool_points, &c->pool_seeds, &c->lw, &c->w,
                       &c->psis_out, &c->psis_aux, &c->tailbuf, &c->cdf, &c->idx, &c->gbuf, &c->trace_lp, &c->st_theta, &c->st_grad,
                       &c->st_lp, &c->st_npts, &c->lb_hs, &c->lb_hy, &c->lb_x0, &c->sortk, &c->sorti,
-                      &c->pool_ok, &c->fail_seeds, &c->rs_err, &c->hs_ial, &c->hs_nacc};
+                      &c->pool_ok, &c->fail_seeds, &c->rs_err, &c->hs_ial, &c->hs_nacc,
+                      &c->lc_X, &c->lc_out, &c->lc_x, &c->lc_g, &c->lc_p, &c->lc_gram, &c->lc_st, &c->lc_ctr};
     for (DevBuf *b : bufs) b->release();
     for (int b = 0; b < 2; ++b) {
         c->cb_x[b].release(); c->cb_lp[b].release();
@@ -349,6 +360,7 @@ int32_t pfmi_destroy(pfmi_ctx *c) {
     for (hipEvent_t e : c->sg_cb) if (e) (void)hipEventDestroy(e);
     for (int b = 0; b < PF_DCB_NB; ++b) { c->dcb_x[b].release(); c->dcb_lp[b].release(); }
     if (c->h_prog) (void)hipHostFree(c->h_prog);
+    if (c->lc_status) (void)hipHostFree(c->lc_status);
     if (c->h_list) (void)hipHostFree(c->h_list);
     (void)hipStreamDestroy(c->stream);
     delete c;
@@ -402,8 +414,10 @@ int32_t pfmi_set_target(pfmi_ctx *c, const pfmi_target *t) {
     PF_CTX_MUT(c);
     PF_CHECK(t != nullptr, PFMI_ERR_ARG, "null target");
     PF_CHECK(t->d > 0, PFMI_ERR_ARG, "target dimension must be positive");
+    lbc_abandon(c);
     TargetDev &T = c->target;
     T.kind = t->kind; T.d = t->d; T.r = 0; T.rpad = 0; T.offset = 0.0; T.fn = nullptr; T.dev_fn = nullptr; T.user = nullptr;
+    T.grad_fn = nullptr; T.grad_user = nullptr;
     if (t->kind == PFMI_TARGET_GAUSS) {
         PF_CHECK(t->mean && t->a, PFMI_ERR_ARG, "GAUSS target needs mean and a");
         PF_CHECK(t->r >= 0 && t->r <= 16, PFMI_ERR_UNSUPPORTED, "GAUSS target rank %d > 16 unsupported", t->r);
@@ -450,6 +464,7 @@ int32_t pfmi_set_traces(pfmi_ctx *c, int32_t K, const int64_t *npoints, int32_t 
                         const double *grad) {
     PF_CTX_MUT(c);
     if (c->sr.active) stream_abandon(c);
+    lbc_abandon(c);
     PF_CHECK(K > 0 && d > 0 && npoints && theta && grad, PFMI_ERR_ARG, "set_traces: bad arguments");
     c->off.assign((size_t)K + 1, 0);
     for (int k = 0; k < K; ++k) {
@@ -476,12 +491,16 @@ int32_t pfmi_set_traces(pfmi_ctx *c, int32_t K, const int64_t *npoints, int32_t 
 }
 
 // ---- device trajectory generation ------------------------------------------------------------------------
+static int32_t lbc_enqueue(pfmi_ctx *c, int32_t K, const double *x0, int32_t J, int32_t maxiters, double g_tol);
 int32_t pfmi_optimize_batch_enqueue(pfmi_ctx *c, int32_t K, const double *x0, int32_t J, int32_t maxiters, double g_tol) {
     PF_CTX_MUT(c);
     if (c->sr.active) stream_abandon(c);
+    lbc_abandon(c);
     const TargetDev &T = c->target;
+    if (T.kind == PFMI_TARGET_DEVICE_CALLBACK && T.grad_fn) return lbc_enqueue(c, K, x0, J, maxiters, g_tol);
+    c->lbc.rounds = 0; c->lbc.columns = 0;
     PF_CHECK(T.kind == PFMI_TARGET_GAUSS || T.kind == PFMI_TARGET_FUNNEL, PFMI_ERR_UNSUPPORTED,
-             "optimize_batch: needs a built-in target (optimise callback targets on the host, then pfmi_set_traces)");
+             "optimize_batch: needs a built-in target or a DEVICE_CALLBACK target with a gradient closure (pfmi_set_target_gradient)");
     PF_CHECK(K > 0 && x0 && maxiters >= 0, PFMI_ERR_ARG, "optimize_batch: bad arguments");
     PF_CHECK(J >= 1 && J <= 16, PFMI_ERR_UNSUPPORTED, "optimize_batch: history_length %d outside 1..16", J);
     const int d = T.d;
@@ -504,6 +523,15 @@ int32_t pfmi_optimize_batch_wait(pfmi_ctx *c, int64_t *npoints) {
     PF_CTX_MUT(c);
     PF_CHECK(c->opt_pending, PFMI_ERR_STATE, "optimize_batch_wait: no pfmi_optimize_batch_enqueue outstanding");
     PF_CHECK(npoints != nullptr, PFMI_ERR_ARG, "optimize_batch_wait: null npoints");
+    if (c->lbc.active) {
+        int32_t fin = 0;
+        while (true) {
+            PF_TRY(pfmi_optimize_batch_pump(c, &fin));
+            if (fin) break;
+            for (int i = 0; i < 64; ++i) __builtin_ia32_pause();
+        }
+        c->lbc.active = false;                      // (the downloads below synchronise the stream behind the last round)
+    }
     c->opt_pending = false;
     const int K = c->opt_K, d = c->target.d;
     const size_t cap = (size_t)c->opt_cap;
@@ -542,6 +570,101 @@ int32_t pfmi_optimize_batch(pfmi_ctx *c, int32_t K, const double *x0, int32_t J,
     PF_CHECK(npoints != nullptr, PFMI_ERR_ARG, "optimize_batch: bad arguments");
     PF_TRY(pfmi_optimize_batch_enqueue(c, K, x0, J, maxiters, g_tol));
     return pfmi_optimize_batch_wait(c, npoints);
+}
+
+// ---- closure optimisation (lbfgs_closure_kernel.hip): rounds of one step kernel + one closure call, scheduled by the pumping thread --------
+#define PF_LBC_WINDOW 4                 // rounds in flight at most
+static int32_t lbc_enqueue(pfmi_ctx *c, int32_t K, const double *x0, int32_t J, int32_t maxiters, double g_tol) {
+    const TargetDev &T = c->target;
+    PF_CHECK(K > 0 && x0 && maxiters >= 0, PFMI_ERR_ARG, "optimize_batch: bad arguments");
+    PF_CHECK(J >= 1 && J <= 32, PFMI_ERR_UNSUPPORTED, "optimize_batch: history_length %d outside 1..32 (closure target)", J);
+    const int d = T.d;
+    const size_t cap = (size_t)maxiters + 1;
+    {   // everything the call allocates: staging trace, the closure's input / output, x, g, p, the ring, the Gram data
+        size_t fr = 0, tot = 0;
+        PF_HIP(hipMemGetInfo(&fr, &tot));
+        const double need = 8.0 * K * ((double)cap * (2.0 * d + 1.0) + (6.0 + 2.0 * J) * d + 1.0) + (double)K * pf_lbc_path_state_bytes(J);
+        PF_CHECK(need < 0.8 * (double)fr, PFMI_ERR_UNSUPPORTED, "optimize_batch: %.3g GB needed for K = %d, d = %d, J = %d, maxiters = %d; %.3g GB free",
+                 need / 1e9, K, d, J, maxiters, (double)fr / 1e9);
+    }
+    PF_TRY(c->st_theta.ensure(sizeof(double) * K * cap * d));
+    PF_TRY(c->st_grad.ensure(sizeof(double) * K * cap * d));
+    PF_TRY(c->st_lp.ensure(sizeof(double) * K * cap));
+    PF_TRY(c->st_npts.ensure(sizeof(int32_t) * K));
+    PF_TRY(c->lb_x0.ensure(sizeof(double) * (size_t)K * d));
+    PF_TRY(pf_lbc_alloc(c, K, J, d));
+    PF_TRY(h2d(c, c->lb_x0.p, x0, sizeof(double) * (size_t)K * d));
+    LbcState &O = c->lbc;
+    O.K = K; O.J = J; O.maxiters = maxiters; O.g_tol = g_tol;
+    { const char *rj = pf_debug_get("PFMI_LBFGS_REJECT_EVERY"); O.reject_every = rj ? atoi(rj) : 0; }
+    O.issued = 0; O.seen = 0; O.max_rounds = (int64_t)maxiters * (25 + 30) + 1; O.finished = false;
+    O.rounds = 0; O.columns = 0;
+    __atomic_store_n(c->lc_status, (int64_t)K, __ATOMIC_RELEASE);            // round 0: every path running
+    O.active = true;                                                           // from here on, failure paths drain (lbc_abandon)
+    c->opt_pending = true; c->opt_K = K; c->opt_cap = (int32_t)cap;
+    c->fitted = false; c->elbo_done = false; c->pooled = false; c->have_trace_lp = false; c->P = 0;
+    pf_kernel_begin(c);
+    const int32_t rc = pf_launch_lbc_init(c);
+    pf_kernel_end(c, "optimize");
+    if (rc != PFMI_OK) lbc_abandon(c);
+    return rc;
+}
+
+int32_t pfmi_set_target_gradient(pfmi_ctx *c, pfmi_logp_dev_fn logp_grad_fn, void *user) {
+    PF_CTX(c);
+    PF_CHECK(c->target.kind == PFMI_TARGET_DEVICE_CALLBACK, PFMI_ERR_ARG, "set_target_gradient: the current target is not a DEVICE_CALLBACK target");
+    PF_CHECK(logp_grad_fn != nullptr, PFMI_ERR_ARG, "set_target_gradient: null closure");
+    lbc_abandon(c);
+    c->target.grad_fn = logp_grad_fn; c->target.grad_user = user;
+    return PFMI_OK;
+}
+
+static int32_t lbc_pump_pass(pfmi_ctx *c, int32_t *finished) {
+    LbcState &O = c->lbc;
+    const int64_t w = __atomic_load_n(c->lc_status, __ATOMIC_ACQUIRE);
+    const int64_t round = w >> 32, active = w & 0xffffffffll;
+    if (round > O.seen) O.seen = round;
+    if (round == O.seen && active == 0) O.finished = true;
+    const TargetDev &T = c->target;
+    const int d = T.d;
+    while (!O.finished && O.issued < O.max_rounds && O.issued - O.seen < PF_LBC_WINDOW) {
+        // the closure on all K trial points (written by the previous round), then the step kernel of the next round
+        T.grad_fn(c->lc_X.as<double>(), d, O.K, c->lc_out.as<double>(), (void *)c->stream, T.grad_user);
+        O.columns += O.K;
+        ++O.issued;
+        PF_TRY(pf_launch_lbc_step(c, O.issued));
+        O.rounds = O.issued;
+    }
+    if (!O.finished && O.issued >= O.max_rounds && O.seen >= O.issued) O.finished = true;      // the hard cap: a stuck flag cannot loop forever
+    if (!O.finished) {
+        const hipError_t e = hipStreamQuery(c->stream);
+        PF_CHECK(e == hipSuccess || e == hipErrorNotReady, PFMI_ERR_HIP, "optimize_batch_pump: %s", hipGetErrorString(e));
+    }
+    *finished = O.finished ? 1 : 0;
+    return PFMI_OK;
+}
+
+int32_t pfmi_optimize_batch_pump(pfmi_ctx *c, int32_t *finished) {
+    PF_CHECK(c != nullptr && finished != nullptr, PFMI_ERR_ARG, "optimize_batch_pump: null argument");
+    PF_CHECK(c->lbc.active, PFMI_ERR_STATE, "optimize_batch_pump: no closure optimisation outstanding");
+    PF_HIP(hipSetDevice(c->device));
+    const int32_t rc = lbc_pump_pass(c, finished);
+    if (rc != PFMI_OK) lbc_abandon(c);        // a failed pass ends the call: what is in flight is drained, the context is usable again
+    return rc;
+}
+
+int32_t pfmi_optimize_batch_cancel(pfmi_ctx *c) {
+    PF_CHECK(c != nullptr, PFMI_ERR_ARG, "null pfmi_ctx");
+    PF_HIP(hipSetDevice(c->device));
+    lbc_abandon(c);
+    return PFMI_OK;
+}
+
+int32_t pfmi_optimize_stats(pfmi_ctx *c, int64_t *rounds, int64_t *closure_columns) {
+    PF_CHECK(c != nullptr, PFMI_ERR_ARG, "null pfmi_ctx");
+    if (rounds) *rounds = c->lbc.rounds;
+    if (closure_columns) *closure_columns = c->lbc.columns;
+    return PFMI_OK;
 }
 
 int32_t pfmi_get_trace(pfmi_ctx *c, int32_t k, double *theta, double *logp, double *grad) {

@@ -72,6 +72,18 @@ struct TargetDev {
     pfmi_logp_fn fn = nullptr;
     pfmi_logp_dev_fn dev_fn = nullptr;   // DEVICE_CALLBACK: launches the user's kernel(s) on the ctx stream
     void *user = nullptr;
+    pfmi_logp_dev_fn grad_fn = nullptr;  // DEVICE_CALLBACK: optional value-and-gradient closure (pfmi_set_target_gradient)
+    void *grad_user = nullptr;
+};
+
+// an outstanding closure optimisation (pfmi_optimize_batch_enqueue on a DEVICE_CALLBACK target with a gradient closure)
+struct LbcState {
+    bool active = false;          // rounds may still be in flight on the ctx stream: drain it before the buffers are reused
+    int K = 0, J = 0, maxiters = 0, reject_every = 0;
+    double g_tol = 0.0;
+    int64_t issued = 0, seen = 0, max_rounds = 0;     // step rounds launched / last round whose progress the host has read / hard cap
+    bool finished = false;
+    int64_t rounds = 0, columns = 0;                  // statistics of the last optimisation (pfmi_optimize_stats)
 };
 
 struct pfmi_ctx {
@@ -219,6 +231,9 @@ struct pfmi_ctx {
     double cb_bytes_dev = 0.0;    // DEVICE_CALLBACK: bytes of draws materialised in HBM for the callback
     // enqueue / wait split of the blocking entry points
     bool opt_pending = false;     // pfmi_optimize_batch_enqueue issued, _wait not yet called
+    LbcState lbc;                 // closure optimisation (lbfgs_closure_kernel.hip)
+    DevBuf lc_X, lc_out, lc_x, lc_g, lc_p, lc_gram, lc_st, lc_ctr;
+    int64_t *lc_status = nullptr; // page-locked: round << 32 | active paths, written by the last workgroup of each round
     int32_t opt_K = 0, opt_cap = 0;
     bool elbo_pending = false;    // pfmi_elbo_batch_enqueue issued
     bool pool_from_best = false;  // the pool was filled by pfmi_pool_build_best (pool_ok is valid)
@@ -276,6 +291,10 @@ int32_t pf_launch_logratio(pfmi_ctx *c, int64_t n);
 int32_t pf_launch_scatter_rows(pfmi_ctx *c, int64_t ns, int64_t N, const int32_t *d_points, const double *d_src, double *d_dst);
 int32_t pf_launch_lbfgs(pfmi_ctx *c, int K, int J, int maxiters, double g_tol, const double *d_x0, int pub_mask = -1, int32_t *h_prog = nullptr);
 int32_t pf_launch_trace_pack(pfmi_ctx *c, int64_t cap);
+size_t pf_lbc_path_state_bytes(int J);
+int32_t pf_lbc_alloc(pfmi_ctx *c, int K, int J, int d);
+int32_t pf_launch_lbc_init(pfmi_ctx *c);
+int32_t pf_launch_lbc_step(pfmi_ctx *c, int64_t round);
 int32_t pf_launch_woodbury_prim(pfmi_ctx *c, int mode, int64_t p, int64_t N, const double *d_in, double *d_out);
 int32_t pf_launch_colsumsq(pfmi_ctx *c, int64_t N, const double *d_x, double *d_out);
 int32_t pf_launch_woodbury_diag(pfmi_ctx *c, int64_t p, double *d_out);

@@ -196,8 +196,10 @@ an AMDGPU.jl kernel on `HIPStream(stream)`.  The reference's arbitrary `logp` (s
 """
 struct DeviceClosureTarget <: DeviceTarget
     d::Int; fptr::Ptr{Cvoid}; user::Ptr{Cvoid}
+    grad_fptr::Ptr{Cvoid}      # optional value-and-gradient launcher (pfmi_set_target_gradient): out[n] logp, then out[n + j d + i] grad
 end
-DeviceClosureTarget(d::Integer, fptr::Ptr{Cvoid}) = DeviceClosureTarget(d, fptr, C_NULL)
+DeviceClosureTarget(d::Integer, fptr::Ptr{Cvoid}) = DeviceClosureTarget(d, fptr, C_NULL, C_NULL)
+DeviceClosureTarget(d::Integer, fptr::Ptr{Cvoid}, user::Ptr{Cvoid}) = DeviceClosureTarget(d, fptr, user, C_NULL)
 dimension(t::GaussTarget) = length(t.mean)
 dimension(t::Union{FunnelTarget,DeviceClosureTarget}) = t.d
 function set_target!(eng::Engine, t::GaussTarget)
@@ -217,6 +219,26 @@ end
 function set_target!(eng::Engine, t::DeviceClosureTarget)
     ct = Ref(CTarget(3, t.d, 0, 0, C_NULL, C_NULL, C_NULL, C_NULL, 0.0, C_NULL, t.user, t.fptr))
     check(ccall((:pfmi_set_target, libpfmi), Int32, (Ptr{Cvoid}, Ref{CTarget}), eng.ptr, ct))
+    if t.grad_fptr != C_NULL             # the L-BFGS of this target then runs on the device (rounds of one kernel + one launcher call)
+        check(ccall((:pfmi_set_target_gradient, libpfmi), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), eng.ptr, t.grad_fptr, t.user))
+    end
+    return nothing
+end
+has_device_gradient(t::DeviceTarget) = !(t isa DeviceClosureTarget) || t.grad_fptr != C_NULL
+
+"one non-blocking scheduling pass of a closure optimisation (include/pfmi.h); true once every path has finished"
+function optimize_batch_pump!(eng::Engine)
+    fin = Ref{Int32}(0)
+    check(ccall((:pfmi_optimize_batch_pump, libpfmi), Int32, (Ptr{Cvoid}, Ref{Int32}), eng.ptr, fin))
+    return fin[] != 0
+end
+"gives up an outstanding closure optimisation (drains this engine's stream); no-op otherwise"
+optimize_batch_cancel!(eng::Engine) = check(ccall((:pfmi_optimize_batch_cancel, libpfmi), Int32, (Ptr{Cvoid},), eng.ptr))
+"(rounds, closure columns) of the last closure optimisation"
+function optimize_stats(eng::Engine)
+    r = Ref{Int64}(0); n = Ref{Int64}(0)
+    check(ccall((:pfmi_optimize_stats, libpfmi), Int32, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), eng.ptr, r, n))
+    return (r[], n[])
 end
 "host twin of a built-in target (the optimiser's `logp`, result objects): the same formula in Julia"
 function logdensity(t::GaussTarget, x)
@@ -623,9 +645,10 @@ function multipathfinder(engines::Vector{Engine}, target::DeviceTarget, ndraws::
     if ndraws > ndraws_per_run * nruns
         @warn "More draws requested than total number of draws across replicas. Draws will not be unique."
     end
-    on_device = !(target isa DeviceClosureTarget)
-    on_device || optim_fun !== nothing || throw(ArgumentError("a DeviceClosureTarget needs `optim_fun` (its host twin) for the optimiser"))
-    logp = on_device ? (x -> logdensity(target, x)) : (x -> -optim_fun.f(x, nothing))                     # :159
+    on_device = has_device_gradient(target)               # a DeviceClosureTarget with a gradient launcher optimises on the device too
+    on_device || optim_fun !== nothing || throw(ArgumentError("a DeviceClosureTarget without a gradient launcher needs `optim_fun` (its host twin) for the optimiser"))
+    logp = !(target isa DeviceClosureTarget) ? (x -> logdensity(target, x)) :
+           optim_fun !== nothing ? (x -> -optim_fun.f(x, nothing)) : (x -> throw(ArgumentError("this DeviceClosureTarget has no host `logp` (pass optim_fun)")))   # :159
     foreach(e -> set_target!(e, target), engines)
     run_seeds = rand!(rng, Vector{UInt64}(undef, nruns))                                                    # :162
     rngs = [Random.seed!(copy(rng), s) for s in run_seeds]                                                  # :189-193

@@ -47,6 +47,7 @@ SYMBOLS = [
     "pfmi_host_alloc", "pfmi_host_free", "pfmi_comm_psis_resample_enqueue", "pfmi_comm_psis_resample_wait", "pfmi_defer_downloads",
     "pfmi_stream_enqueue", "pfmi_stream_seeds", "pfmi_stream_pump", "pfmi_stream_wait", "pfmi_stream_cancel",
     "pfmi_fit_batch_ex", "pfmi_set_hinit", "pfmi_set_callback_threads",
+    "pfmi_set_target_gradient", "pfmi_optimize_batch_pump", "pfmi_optimize_batch_cancel", "pfmi_optimize_stats",
 ]
 
 

@@ -394,10 +394,21 @@ class DeviceOptimizationTrace:
     def gradients(self): return self.materialise()._cache[2]
 
 
+def _closure_gradient(target):
+    """a device closure target that carries a value-and-gradient closure (pfmi_set_target_gradient)"""
+    return getattr(target, "kind", 2) == 3 and getattr(target, "has_device_gradient", False)
+
+
 def _use_device_optimizer(target, optimizer, history_length=DEFAULT_HISTORY_LENGTH):
     builtin = getattr(target, "kind", 2) in (0, 1)
+    if _closure_gradient(target) and optimizer in ("auto", "device"):  # rounds of the closure L-BFGS: any d, the fit path's J limit
+        if history_length > 32:
+            if optimizer == "device":
+                raise ValueError("optimizer='device' with a gradient closure needs history_length <= 32")
+            return False
+        return True
     if optimizer == "device" and not builtin:
-        raise ValueError("optimizer='device' needs a built-in target (analytic gradient on the GPU)")
+        raise ValueError("optimizer='device' needs a built-in target (analytic gradient on the GPU) or a device closure with a gradient")
     if optimizer == "auto":                                  # the device L-BFGS keeps a path's vectors in registers (d <= 16 384) and its
         return builtin and getattr(target, "d", 0) <= 16384 and history_length <= 16      # ring in LDS / a scratch of 16 pairs
     return optimizer == "device"
@@ -446,7 +457,8 @@ def _run_paths(engs, target, inits, run_rngs, *, dim, history_length, ndraws_elb
             state[k].update(eng=engs[g], g=g, kl=k - k0)
     pending = list(range(K))
     on_device = _use_device_optimizer(target, optimizer, history_length)
-    stream_ok = on_device and history_length <= 16 and os.environ.get("PFMI_NO_STREAM") != "1"
+    closure_opt = on_device and _closure_gradient(target)
+    stream_ok = on_device and not closure_opt and history_length <= 16 and os.environ.get("PFMI_NO_STREAM") != "1"
     okw = {k: v for k, v in optimizer_kwargs.items() if k in ("maxiters", "g_tol")}
     pooled = None
     while pending:
@@ -521,6 +533,20 @@ def _run_paths(engs, target, inits, run_rngs, *, dim, history_length, ndraws_elb
         elif on_device:     # every path in one launch per engine; finished paths are recomputed identically from their x0
             for eng, (k0, k1) in zip(engs, blocks):
                 eng.optimize_batch_enqueue(np.stack([s["x0"] for s in state[k0:k1]]), history_length, **okw)
+            if closure_opt:
+                # the rounds of every engine are pumped in turn by this thread (each pump calls the closure for the rounds it launches);
+                # a closure that raised cancels every engine's call, and the exception propagates with the engines usable again
+                try:
+                    active = list(engs)
+                    while active:
+                        active = [eng for eng in active if not eng.optimize_batch_pump()]
+                except BaseException:
+                    for e2 in engs:
+                        try:
+                            e2.optimize_batch_cancel()
+                        except Exception:
+                            pass
+                    raise
             # while the optimisations run: the per-fit seeds of every pending run for the LONGEST possible trace, drawn from copies of
             # the runs' rngs (counter-based: the real rng is advanced by L_k once L_k is known, so the stream consumption is the
             # reference's: rand!(rng_k, UInt64[L_k]), src/elbo.jl:2)

@@ -155,6 +155,9 @@ class Engine:
         self.target = target                      # keep parameter arrays / callbacks alive
         desc = target.descriptor()
         check(self.L.pfmi_set_target(self.ctx, C.byref(desc)))
+        gp = target.gradient_pointer() if hasattr(target, "gradient_pointer") else None
+        if gp is not None:                        # value-and-gradient closure: the L-BFGS runs on the device
+            check(self.L.pfmi_set_target_gradient(self.ctx, C.c_void_p(gp[0]), gp[1]))
 
     def set_traces(self, thetas, grads):
         """thetas/grads: lists (one per path) of (L_k+1, d) arrays (point-major)."""
@@ -177,6 +180,10 @@ class Engine:
         assert self.target is not None and d == self.target.d
         npts = np.empty(K, dtype=np.int64)
         self.gen_traces += 1
+        if getattr(self.target, "has_device_gradient", False):
+            # closure target: the rounds call the Python closure from inside the C call; a recorded exception cancels and re-raises
+            self.optimize_batch_enqueue(x0, history_length, maxiters, g_tol)
+            return self.optimize_batch_wait()
         check(self.L.pfmi_optimize_batch(self.ctx, C.c_int32(K), _d(x0), C.c_int32(history_length), C.c_int32(maxiters),
                                          C.c_double(g_tol), npts.ctypes.data_as(_i64p)))
         self.K, self.P, self.d = K, int(npts.sum()), d
@@ -195,8 +202,32 @@ class Engine:
         check(self.L.pfmi_optimize_batch_enqueue(self.ctx, C.c_int32(K), _d(x0), C.c_int32(history_length), C.c_int32(maxiters),
                                                  C.c_double(g_tol)))
 
+    def optimize_batch_pump(self):
+        """one non-blocking scheduling pass of a closure optimisation (calls the gradient closure for the rounds it launches); True once
+        every path has finished.  An exception raised by a Python closure cancels the call and propagates."""
+        fin = C.c_int32()
+        rc = self.L.pfmi_optimize_batch_pump(self.ctx, C.byref(fin))
+        if getattr(self.target, "pending_error", None) is not None:
+            self.optimize_batch_cancel()
+            self._raise_target_error()
+        check(rc)
+        return bool(fin.value)
+
+    def optimize_batch_cancel(self):
+        """give up an outstanding closure optimisation: drains this engine's stream; no-op otherwise"""
+        check(self.L.pfmi_optimize_batch_cancel(self.ctx))
+
+    def optimize_stats(self):
+        """(rounds, closure columns) of the last closure optimisation"""
+        r, n = C.c_int64(), C.c_int64()
+        check(self.L.pfmi_optimize_stats(self.ctx, C.byref(r), C.byref(n)))
+        return r.value, n.value
+
     def optimize_batch_wait(self):
         npts = np.empty(self._opt_K, dtype=np.int64)
+        if getattr(self.target, "has_device_gradient", False):
+            while not self.optimize_batch_pump():
+                pass
         check(self.L.pfmi_optimize_batch_wait(self.ctx, npts.ctypes.data_as(_i64p)))
         self.P = int(npts.sum())
         self.offsets = np.concatenate([[0], np.cumsum(npts)]).astype(np.int64)

@@ -191,15 +191,30 @@ class DeviceCallbackTarget:
     engine's stream.  dev_fn: a C function pointer (int address or ctypes function) with the pfmi_logp_dev_fn signature
     (X_dev, d, n, out_dev, stream, user) -- e.g. from a HIP library, or an AMDGPU.jl launcher on the Julia side; `user` is passed
     through.  `host` (optional): an object with logp / grad / logp_and_grad for the host optimiser and for host-side checks (the
-    reference evaluates the same closure in the optimiser and in the ELBO; a device closure needs its host twin for the former)."""
+    reference evaluates the same closure in the optimiser and in the ELBO; a device closure needs its host twin for the former).
+    `grad_fn` (optional): a value-and-gradient closure with the same signature and pointer conventions (and the same `user`) whose
+    out_dev holds logp [n] followed by the gradients [n][d] (include/pfmi.h: pfmi_set_target_gradient); with it the L-BFGS runs on the
+    device and no host twin is needed."""
     kind = KIND_DEVICE_CALLBACK
 
-    def __init__(self, d, dev_fn, user=None, host=None, keepalive=None):
+    def __init__(self, d, dev_fn, user=None, host=None, keepalive=None, grad_fn=None):
         self.d = d
         self._fn = dev_fn
         self._user = user
         self.host = host
         self._keep = keepalive
+        self._grad_fn = grad_fn
+
+    @property
+    def has_device_gradient(self):
+        return self._grad_fn is not None
+
+    def gradient_pointer(self):
+        """(function address, user) for pfmi_set_target_gradient, or None"""
+        fn = self._grad_fn
+        if fn is None:
+            return None
+        return (fn if isinstance(fn, int) else C.cast(fn, C.c_void_p).value), self._user
 
     def _h(self):
         if self.host is None:
@@ -222,10 +237,16 @@ class DeviceCallbackTarget:
 class TorchDeviceTarget(DeviceCallbackTarget):
     """Device closure written with torch ops: fn(X) -> (n,) tensor for X of shape (n, d) (rows = draws; a zero-copy view of the
     draws in HBM), evaluated on the engine's own stream.  The Python host's answer to the reference's arbitrary `logp` closure
-    (src/elbo.jl:15) without the PCIe round trip of CallbackTarget.  `host`: see DeviceCallbackTarget."""
+    (src/elbo.jl:15) without the PCIe round trip of CallbackTarget.  `host`: see DeviceCallbackTarget.
+    `grad`: None (no gradient: the optimiser needs the host twin), "autograd" (torch.autograd.grad(fn(X).sum(), X): the rows are
+    independent, so this is the per-draw gradient -- the reference's default_ad()), or a callable X -> (logp (n,), grad (n, d)).  With a
+    gradient the L-BFGS runs on the device (pfmi_set_target_gradient).  An exception in either closure is recorded in pending_error and
+    re-raised by the Engine."""
 
-    def __init__(self, d, fn, host=None, device=0):
+    def __init__(self, d, fn, host=None, device=0, grad=None):
         import torch
+        if not (grad is None or grad == "autograd" or callable(grad)):
+            raise ValueError("grad must be None, 'autograd' or a callable X -> (logp, grad)")
 
         class _View:
             def __init__(self, ptr, shape):
@@ -249,7 +270,35 @@ class TorchDeviceTarget(DeviceCallbackTarget):
                     self.pending_error = ex
 
         self._cfn = _lib.LOGP_DEV_FN(_cb)
-        super().__init__(d, self._cfn, None, host)
+
+        def _value_and_grad(X):
+            if grad == "autograd":
+                with torch.enable_grad():
+                    Xg = X.detach().clone().requires_grad_(True)
+                    lp = fn(Xg).to(torch.float64).reshape(-1)
+                    (gr,) = torch.autograd.grad(lp.sum(), Xg)
+                return lp.detach(), gr
+            return grad(X)
+
+        def _gcb(xp, d_, n, outp, stream, _user):
+            try:
+                dev = torch.device("cuda", device)
+                with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=dev)):
+                    out = torch.as_tensor(_View(outp, (n * (d_ + 1),)), device=dev)
+                    try:
+                        X = torch.as_tensor(_View(xp, (n, d_)), device=dev)
+                        lp, gr = _value_and_grad(X)
+                        out[:n].copy_(lp.to(torch.float64).reshape(n))
+                        out[n:].copy_(gr.to(torch.float64).reshape(n * d_))
+                    except BaseException:
+                        out.fill_(float("nan"))
+                        raise
+            except BaseException as ex:  # noqa: BLE001 -- recorded, re-raised by the Engine once the C call has returned
+                if self.pending_error is None:
+                    self.pending_error = ex
+
+        self._gcfn = _lib.LOGP_DEV_FN(_gcb) if grad is not None else None
+        super().__init__(d, self._cfn, None, host, grad_fn=self._gcfn)
 
 
 # ---- the synthetic targets of SURVEY.md 8(d) ------------------------------------------------------------
