@@ -176,8 +176,11 @@ int32_t pfmi_get_trace(pfmi_ctx *ctx, int32_t k, double *theta, double *logp, do
  * The calling thread SCHEDULES the dataflow: the optimiser (one workgroup per path) publishes its progress into page-locked host memory,
  * pfmi_stream_pump / pfmi_stream_wait launch the walk, fits and scan of each segment of trace positions once every path has produced it -- no
  * kernel ever waits for another.  After pfmi_stream_wait: pfmi_pool_build_best / pfmi_comm_psis_resample as usual, pfmi_get_fit_status and
- * pfmi_elbo_batch_wait return the slot arrays.  Built-in targets, history_length <= 16, d <= 16384, room for the fixed-stride layout;
- * PFMI_ERR_UNSUPPORTED otherwise (use the three calls above). */
+ * pfmi_elbo_batch_wait return the slot arrays.
+ * Accepted targets: the built-in ones (d <= 16384), and DEVICE_CALLBACK targets with a gradient closure (pfmi_set_target_gradient; any d the
+ * memory check admits) -- the producer is then the closure optimiser of pfmi_optimize_batch, whose rounds the pump issues.  history_length
+ * <= 16 and room for the fixed-stride layout in both cases; PFMI_ERR_UNSUPPORTED otherwise (device closures without a gradient, host
+ * closures, history_length 17 .. 32: use the three calls above). */
 int32_t pfmi_stream_enqueue(pfmi_ctx *ctx, int32_t K, const double *x0, int32_t history_length, int32_t maxiters, double g_tol,
                             double eps, int64_t N, const uint64_t *seeds);
 /* seeds may be NULL in pfmi_stream_enqueue: the optimiser starts at once and the host draws the streams while it runs; pfmi_stream_seeds
@@ -185,13 +188,20 @@ int32_t pfmi_stream_enqueue(pfmi_ctx *ctx, int32_t K, const double *x0, int32_t 
 int32_t pfmi_stream_seeds(pfmi_ctx *ctx, const uint64_t *seeds);
 /* pfmi_stream_pump: ONE scheduling pass of the calling thread (never blocks): launches the walk, fits and scan of the trace positions every
  * path has produced since the last pass; *finished = 1 once the last segment and the reduction are enqueued.  pfmi_stream_wait pumps until
- * then and returns the points per path -- it does NOT wait for the GPU.  A host that drives several contexts pumps them in turn. */
+ * then and returns the points per path -- it does NOT wait for the GPU.  A host that drives several contexts pumps them in turn.
+ * A closure target's closures are called from INSIDE pfmi_stream_pump / pfmi_stream_wait, on the calling thread: the gradient closure once per
+ * optimiser round, with the pipeline's optimiser stream as its `stream` argument (at most 4 rounds in flight, at most maxiters * 55 + 1
+ * rounds); the value closure once per block of draws of a segment's ELBO scan, with that segment's scan stream -- the context's own stream
+ * or its second scan stream, alternating.  A closure must only enqueue on the stream it is handed.  pfmi_optimize_stats counts the rounds.
+ * A pass that fails ends the call; an error of the optimiser's stream or the watchdog leaves the call to be drained by the next
+ * pfmi_stream_cancel / pfmi_stream_enqueue / pfmi_set_traces / pfmi_optimize_batch_enqueue (this context's streams, never the device). */
 int32_t pfmi_stream_pump(pfmi_ctx *ctx, int32_t *finished);
 int32_t pfmi_stream_wait(pfmi_ctx *ctx, int64_t *npoints);
 /* Give up an outstanding streaming call -- for a host that failed between pfmi_stream_enqueue and pfmi_stream_wait (an exception while it
  * drew the seed streams or pumped another context; the reference's task-based fan-out simply propagates the exception, src/multipath.jl:190-208).
  * Drains what is in flight, forgets the half-made results; the context is usable again.  No call outstanding: no-op.  (pfmi_stream_enqueue,
- * pfmi_set_traces and pfmi_optimize_batch_enqueue do the same implicitly when they find a stale call.) */
+ * pfmi_set_traces and pfmi_optimize_batch_enqueue do the same implicitly when they find a stale call or one an error exit left undrained.)
+ * A host whose closure failed inside pfmi_stream_pump cancels here. */
 int32_t pfmi_stream_cancel(pfmi_ctx *ctx);
 
 /* ---- fit_mvnormals / lbfgs_inverse_hessians / pdfactorize --------------------------------------- */

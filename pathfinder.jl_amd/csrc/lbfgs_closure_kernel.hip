@@ -26,6 +26,12 @@
 // Progress: every path that is still running after a round adds one to a device counter; the last workgroup of the round (a ticket)
 // publishes (round << 32 | active paths) to page-locked host memory and resets the counters.  The host (pfmi_optimize_batch_pump) keeps
 // at most a few rounds in flight and stops once it reads zero.
+//
+// Streaming (pfmi_stream_enqueue): h_prog != null.  A round that records a trace row, or ends the path, publishes the path's point count
+// to h_prog[k] and -- behind the final count -- its done flag to h_prog[K + k], the page-locked words pfmi_stream_pump reads for the
+// built-in optimiser too (same recipe as pf_lbfgs_kernel: every thread fences its row stores at agent scope, a barrier, then thread 0's
+// system-scope release).  The staging trace [K][maxiters + 1][d] is already the fixed-stride layout of the stream: nothing is packed.
+// h_prog == null (the packed route): nothing is published, the bits are today's.
 #include "pfmi_common.h"
 
 #define LC_NT 256                      // threads per path (4 waves)
@@ -58,6 +64,7 @@ struct LcArgs {
     int32_t *npts;                     // [K]
     int32_t *ctr;                      // [2]: paths still active after this round, workgroups finished
     int64_t *h_status;                 // page-locked host word: round << 32 | active
+    int32_t *h_prog;                   // streaming: page-locked [2 K] (counts, then done flags); null: no publication
 };
 
 // Block-wide sums of NV values per thread; every thread returns the same totals.  Ping-pong buffers: a buffer is only rewritten two
@@ -110,6 +117,7 @@ __global__ __launch_bounds__(LC_NT) void pf_lbc_step_kernel(LcArgs A) {
     int flip = 0;
     LcPath S = A.st[k];
     if (S.phase != LC_DONE) {
+        const int n_in = S.n;
         const size_t kd = (size_t)k * d;
         double *X = A.X + kd, *x = A.x + kd, *g = A.g + kd, *p = A.p + kd;
         const double *gout = A.out + K + kd;
@@ -332,8 +340,18 @@ __global__ __launch_bounds__(LC_NT) void pf_lbc_step_kernel(LcArgs A) {
                 S.phase = LC_SEARCH;
             }
         }
+        // streaming: rows 0 .. S.n - 1 reach memory (every thread's stores, agent scope) before thread 0 publishes the count; the flag
+        // goes behind the final count.  (S is the same in every thread: the condition is uniform.)
+        const bool pub = A.h_prog && (S.n != n_in || S.phase == LC_DONE);
+        if (pub) __threadfence();
         __syncthreads();                    // every thread has read S and the LDS state before thread 0 writes
-        if (tid == 0) A.st[k] = S;
+        if (tid == 0) {
+            A.st[k] = S;
+            if (pub) {
+                __hip_atomic_store(A.h_prog + k, S.n, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+                if (S.phase == LC_DONE) __hip_atomic_store(A.h_prog + K + k, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+            }
+        }
     }
     // ---- progress of the round: the last workgroup publishes the number of paths still running
     if (tid == 0) {
@@ -359,7 +377,7 @@ static LcArgs lc_args(pfmi_ctx *c, int64_t round) {
     A.hs = c->lb_hs.as<double>(); A.hy = c->lb_hy.as<double>(); A.gram = c->lc_gram.as<double>();
     A.st = c->lc_st.as<LcPath>();
     A.tr_theta = c->st_theta.as<double>(); A.tr_grad = c->st_grad.as<double>(); A.tr_lp = c->st_lp.as<double>();
-    A.npts = c->st_npts.as<int32_t>(); A.ctr = c->lc_ctr.as<int32_t>(); A.h_status = c->lc_status;
+    A.npts = c->st_npts.as<int32_t>(); A.ctr = c->lc_ctr.as<int32_t>(); A.h_status = c->lc_status; A.h_prog = O.h_prog;
     return A;
 }
 
@@ -381,14 +399,14 @@ int32_t pf_lbc_alloc(pfmi_ctx *c, int K, int J, int d) {
     return PFMI_OK;
 }
 
-int32_t pf_launch_lbc_init(pfmi_ctx *c) {
-    hipLaunchKernelGGL(pf_lbc_init_kernel, dim3(c->lbc.K), dim3(LC_NT), 0, c->stream, lc_args(c, 0));
+int32_t pf_launch_lbc_init(pfmi_ctx *c, hipStream_t s) {
+    hipLaunchKernelGGL(pf_lbc_init_kernel, dim3(c->lbc.K), dim3(LC_NT), 0, s, lc_args(c, 0));
     PF_HIP(hipGetLastError());
     return PFMI_OK;
 }
 
-int32_t pf_launch_lbc_step(pfmi_ctx *c, int64_t round) {
-    hipLaunchKernelGGL(pf_lbc_step_kernel, dim3(c->lbc.K), dim3(LC_NT), 0, c->stream, lc_args(c, round));
+int32_t pf_launch_lbc_step(pfmi_ctx *c, int64_t round, hipStream_t s) {
+    hipLaunchKernelGGL(pf_lbc_step_kernel, dim3(c->lbc.K), dim3(LC_NT), 0, s, lc_args(c, round));
     PF_HIP(hipGetLastError());
     return PFMI_OK;
 }

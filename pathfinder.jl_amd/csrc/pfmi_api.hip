@@ -307,13 +307,15 @@ int32_t pfmi_create(int32_t device, pfmi_ctx **out) {
     return PFMI_OK;
 }
 
-// a streaming call that was never waited for (pfmi_stream_wait): let what is in flight on the side streams finish -- the optimiser still writes the
-// staging trace -- and forget the call.  Called by whatever is about to reuse or free that memory.
+// a streaming call that was never waited for (pfmi_stream_wait), or that an error exit of the pump left in the "needs drain" state: let what
+// is in flight on the side streams finish -- the optimiser still writes the staging trace, a closure's scans their block buffers -- and forget
+// the call.  Called by whatever is about to reuse or free that memory.  Drains THIS ctx's streams, never the device.
 static void stream_abandon(pfmi_ctx *c) {
     for (hipStream_t s : {c->s_opt, c->s_fit, c->s_scan1}) if (s) (void)hipStreamSynchronize(s);
     for (hipStream_t s : c->s_cb) if (s) (void)hipStreamSynchronize(s);
     c->sr.active = false;
     c->stream_pending = false;
+    c->stream_drain = false;
 }
 
 // a closure optimisation that was never waited for: its rounds still write the staging trace and the closure's buffers on the ctx stream.
@@ -415,6 +417,7 @@ int32_t pfmi_set_target(pfmi_ctx *c, const pfmi_target *t) {
     PF_CHECK(t != nullptr, PFMI_ERR_ARG, "null target");
     PF_CHECK(t->d > 0, PFMI_ERR_ARG, "target dimension must be positive");
     lbc_abandon(c);
+    if (c->sr.active && c->sr.closure) stream_abandon(c);   // its pump would call the closures being replaced
     TargetDev &T = c->target;
     T.kind = t->kind; T.d = t->d; T.r = 0; T.rpad = 0; T.offset = 0.0; T.fn = nullptr; T.dev_fn = nullptr; T.user = nullptr;
     T.grad_fn = nullptr; T.grad_user = nullptr;
@@ -463,7 +466,7 @@ int32_t pfmi_set_target(pfmi_ctx *c, const pfmi_target *t) {
 int32_t pfmi_set_traces(pfmi_ctx *c, int32_t K, const int64_t *npoints, int32_t d, const double *theta,
                         const double *grad) {
     PF_CTX_MUT(c);
-    if (c->sr.active) stream_abandon(c);
+    if (c->sr.active || c->stream_drain) stream_abandon(c);
     lbc_abandon(c);
     PF_CHECK(K > 0 && d > 0 && npoints && theta && grad, PFMI_ERR_ARG, "set_traces: bad arguments");
     c->off.assign((size_t)K + 1, 0);
@@ -494,7 +497,7 @@ int32_t pfmi_set_traces(pfmi_ctx *c, int32_t K, const int64_t *npoints, int32_t 
 static int32_t lbc_enqueue(pfmi_ctx *c, int32_t K, const double *x0, int32_t J, int32_t maxiters, double g_tol);
 int32_t pfmi_optimize_batch_enqueue(pfmi_ctx *c, int32_t K, const double *x0, int32_t J, int32_t maxiters, double g_tol) {
     PF_CTX_MUT(c);
-    if (c->sr.active) stream_abandon(c);
+    if (c->sr.active || c->stream_drain) stream_abandon(c);
     lbc_abandon(c);
     const TargetDev &T = c->target;
     if (T.kind == PFMI_TARGET_DEVICE_CALLBACK && T.grad_fn) return lbc_enqueue(c, K, x0, J, maxiters, g_tol);
@@ -574,6 +577,39 @@ int32_t pfmi_optimize_batch(pfmi_ctx *c, int32_t K, const double *x0, int32_t J,
 
 // ---- closure optimisation (lbfgs_closure_kernel.hip): rounds of one step kernel + one closure call, scheduled by the pumping thread --------
 #define PF_LBC_WINDOW 4                 // rounds in flight at most
+// the round bookkeeping of a closure optimisation, packed (prog = null) or streamed (prog = the pipeline's progress words)
+static void lbc_begin(pfmi_ctx *c, int32_t K, int32_t J, int32_t maxiters, double g_tol, int32_t *prog) {
+    LbcState &O = c->lbc;
+    O.K = K; O.J = J; O.maxiters = maxiters; O.g_tol = g_tol;
+    { const char *rj = pf_debug_get("PFMI_LBFGS_REJECT_EVERY"); O.reject_every = rj ? atoi(rj) : 0; }
+    O.issued = 0; O.seen = 0; O.max_rounds = (int64_t)maxiters * (25 + 30) + 1; O.finished = false;
+    O.rounds = 0; O.columns = 0; O.h_prog = prog;
+    __atomic_store_n(c->lc_status, (int64_t)K, __ATOMIC_RELEASE);            // round 0: every path running
+}
+
+// Issues the rounds a closure optimisation may have in flight on stream `s` (the ctx stream: pfmi_optimize_batch_pump; s_opt: the streaming
+// pipeline, pfmi_stream_pump): the gradient closure on all K trial points, with `s` as its stream, then the step kernel of the next round.
+// At most PF_LBC_WINDOW rounds ahead of the last one whose progress word the host has read, never more than the hard cap.  Sets O.finished.
+static int32_t lbc_issue_rounds(pfmi_ctx *c, hipStream_t s) {
+    LbcState &O = c->lbc;
+    const int64_t w = __atomic_load_n(c->lc_status, __ATOMIC_ACQUIRE);
+    const int64_t round = w >> 32, active = w & 0xffffffffll;
+    if (round > O.seen) O.seen = round;
+    if (round == O.seen && active == 0) O.finished = true;
+    const TargetDev &T = c->target;
+    const int d = T.d;
+    while (!O.finished && O.issued < O.max_rounds && O.issued - O.seen < PF_LBC_WINDOW) {
+        // the closure on all K trial points (written by the previous round), then the step kernel of the next round
+        T.grad_fn(c->lc_X.as<double>(), d, O.K, c->lc_out.as<double>(), (void *)s, T.grad_user);
+        O.columns += O.K;
+        ++O.issued;
+        PF_TRY(pf_launch_lbc_step(c, O.issued, s));
+        O.rounds = O.issued;
+    }
+    if (!O.finished && O.issued >= O.max_rounds && O.seen >= O.issued) O.finished = true;      // the hard cap: a stuck flag cannot loop forever
+    return PFMI_OK;
+}
+
 static int32_t lbc_enqueue(pfmi_ctx *c, int32_t K, const double *x0, int32_t J, int32_t maxiters, double g_tol) {
     const TargetDev &T = c->target;
     PF_CHECK(K > 0 && x0 && maxiters >= 0, PFMI_ERR_ARG, "optimize_batch: bad arguments");
@@ -594,17 +630,15 @@ static int32_t lbc_enqueue(pfmi_ctx *c, int32_t K, const double *x0, int32_t J, 
     PF_TRY(c->lb_x0.ensure(sizeof(double) * (size_t)K * d));
     PF_TRY(pf_lbc_alloc(c, K, J, d));
     PF_TRY(h2d(c, c->lb_x0.p, x0, sizeof(double) * (size_t)K * d));
-    LbcState &O = c->lbc;
-    O.K = K; O.J = J; O.maxiters = maxiters; O.g_tol = g_tol;
-    { const char *rj = pf_debug_get("PFMI_LBFGS_REJECT_EVERY"); O.reject_every = rj ? atoi(rj) : 0; }
-    O.issued = 0; O.seen = 0; O.max_rounds = (int64_t)maxiters * (25 + 30) + 1; O.finished = false;
-    O.rounds = 0; O.columns = 0;
-    __atomic_store_n(c->lc_status, (int64_t)K, __ATOMIC_RELEASE);            // round 0: every path running
-    O.active = true;                                                           // from here on, failure paths drain (lbc_abandon)
+    // a streamed closure call may have left rounds behind its last one on s_opt (they find every path done, but still write the progress
+    // word and the closure's buffers): they finish before this call reuses them
+    if (c->s_opt) PF_HIP(hipStreamSynchronize(c->s_opt));
+    lbc_begin(c, K, J, maxiters, g_tol, nullptr);
+    c->lbc.active = true;                                                      // from here on, failure paths drain (lbc_abandon)
     c->opt_pending = true; c->opt_K = K; c->opt_cap = (int32_t)cap;
     c->fitted = false; c->elbo_done = false; c->pooled = false; c->have_trace_lp = false; c->P = 0;
     pf_kernel_begin(c);
-    const int32_t rc = pf_launch_lbc_init(c);
+    const int32_t rc = pf_launch_lbc_init(c, c->stream);
     pf_kernel_end(c, "optimize");
     if (rc != PFMI_OK) lbc_abandon(c);
     return rc;
@@ -615,27 +649,14 @@ int32_t pfmi_set_target_gradient(pfmi_ctx *c, pfmi_logp_dev_fn logp_grad_fn, voi
     PF_CHECK(c->target.kind == PFMI_TARGET_DEVICE_CALLBACK, PFMI_ERR_ARG, "set_target_gradient: the current target is not a DEVICE_CALLBACK target");
     PF_CHECK(logp_grad_fn != nullptr, PFMI_ERR_ARG, "set_target_gradient: null closure");
     lbc_abandon(c);
+    if (c->sr.active && c->sr.closure) stream_abandon(c);
     c->target.grad_fn = logp_grad_fn; c->target.grad_user = user;
     return PFMI_OK;
 }
 
 static int32_t lbc_pump_pass(pfmi_ctx *c, int32_t *finished) {
     LbcState &O = c->lbc;
-    const int64_t w = __atomic_load_n(c->lc_status, __ATOMIC_ACQUIRE);
-    const int64_t round = w >> 32, active = w & 0xffffffffll;
-    if (round > O.seen) O.seen = round;
-    if (round == O.seen && active == 0) O.finished = true;
-    const TargetDev &T = c->target;
-    const int d = T.d;
-    while (!O.finished && O.issued < O.max_rounds && O.issued - O.seen < PF_LBC_WINDOW) {
-        // the closure on all K trial points (written by the previous round), then the step kernel of the next round
-        T.grad_fn(c->lc_X.as<double>(), d, O.K, c->lc_out.as<double>(), (void *)c->stream, T.grad_user);
-        O.columns += O.K;
-        ++O.issued;
-        PF_TRY(pf_launch_lbc_step(c, O.issued));
-        O.rounds = O.issued;
-    }
-    if (!O.finished && O.issued >= O.max_rounds && O.seen >= O.issued) O.finished = true;      // the hard cap: a stuck flag cannot loop forever
+    PF_TRY(lbc_issue_rounds(c, c->stream));
     if (!O.finished) {
         const hipError_t e = hipStreamQuery(c->stream);
         PF_CHECK(e == hipSuccess || e == hipErrorNotReady, PFMI_ERR_HIP, "optimize_batch_pump: %s", hipGetErrorString(e));
@@ -745,32 +766,55 @@ int32_t pfmi_stream_enqueue(pfmi_ctx *c, int32_t K, const double *x0, int32_t J,
     }
     return rc;
 }
+static int64_t devcb_chunk_fits(const pfmi_ctx *c, int64_t per_fit_doubles, int64_t nf, int64_t N);
 static int32_t stream_enqueue_impl(pfmi_ctx *c, int32_t K, const double *x0, int32_t J, int32_t maxiters, double g_tol, double eps, int64_t N,
                                    const uint64_t *seeds) {
     const TargetDev &T = c->target;
-    PF_CHECK(T.kind == PFMI_TARGET_GAUSS || T.kind == PFMI_TARGET_FUNNEL, PFMI_ERR_UNSUPPORTED,
-             "stream_enqueue: needs a built-in target (the optimiser runs on the device)");
+    // the producer: the built-in optimiser (one persistent kernel), or -- a DEVICE_CALLBACK target with a gradient closure -- the rounds of the
+    // closure optimiser, issued by the pump on s_opt; the closure's scans then write the draws and call the value closure segment by segment
+    const bool closure = T.kind == PFMI_TARGET_DEVICE_CALLBACK && T.grad_fn != nullptr;
+    PF_CHECK(T.kind == PFMI_TARGET_GAUSS || T.kind == PFMI_TARGET_FUNNEL || closure, PFMI_ERR_UNSUPPORTED,
+             "stream_enqueue: needs a built-in target or a DEVICE_CALLBACK target with a gradient closure (the optimiser runs on the device)");
     PF_CHECK(K > 0 && x0 && maxiters >= 0 && N >= 1, PFMI_ERR_ARG, "stream_enqueue: bad arguments");
     PF_CHECK(J >= 1 && J <= 16, PFMI_ERR_UNSUPPORTED, "stream_enqueue: history_length %d outside 1..16", J);
-    // a previous streaming call that was never waited for (a host exception between enqueue and wait): drain and forget it, like
-    // pfmi_set_traces / pfmi_optimize_batch_enqueue do -- a persistent context must stay usable
-    if (c->sr.active) stream_abandon(c);
+    // a previous streaming call that was never waited for (a host exception between enqueue and wait) or that an error exit left to be
+    // drained: drain and forget it, like pfmi_set_traces / pfmi_optimize_batch_enqueue do -- a persistent context must stay usable.
+    // A packed closure optimisation still in flight writes the same staging trace: drained too.
+    if (c->sr.active || c->stream_drain) stream_abandon(c);
+    lbc_abandon(c);
     if (c->s_opt) PF_TRY(stream_sync(c));      // the page-locked progress words and work lists are reused: the previous call's copies must have landed
     const int ncu = c->ncu > 0 ? c->ncu : 256;
     const int d = T.d;
-    PF_CHECK(d <= 16384, PFMI_ERR_UNSUPPORTED, "stream_enqueue: the device optimiser takes d <= 16384");
+    // (the built-in optimiser keeps a path's vectors in registers; the closure's round kernel walks memory: any d the memory check admits)
+    PF_CHECK(closure || d <= 16384, PFMI_ERR_UNSUPPORTED, "stream_enqueue: the device optimiser takes d <= 16384");
     const int64_t cap = (int64_t)maxiters + 1, P = (int64_t)K * cap;
     PF_CHECK(P < (1ll << 31), PFMI_ERR_UNSUPPORTED, "stream_enqueue: too many trace slots");
     int kpad = 0;
     for (int o : {4, 8, 12, 16, 20, 32}) if (2 * J <= o) { kpad = o; break; }
+    const int64_t nf = (int64_t)K * (cap - 1);
+    int64_t dcb_chunk = 1;
     {   // the fixed-stride layout sizes every per-point buffer for the LONGEST possible path: refuse what the device cannot hold
         size_t free_b = 0, total_b = 0;
-        const double need = 8.0 * (double)P * ((double)d * (kpad + 5) + 2.0 * (double)N + 4.0 * kpad * kpad);
+        double need = 8.0 * (double)P * ((double)d * (kpad + 5) + 2.0 * (double)N + 4.0 * kpad * kpad);
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
             double have = (double)free_b;
             for (const DevBuf *b : {&c->vh, &c->alpha_all, &c->sqrt_alpha, &c->mu, &c->logp, &c->logq, &c->st_theta, &c->st_grad}) have += (double)b->cap;
+            if (closure) {
+                // the closure optimiser's own footprint (lbc_enqueue's line without the staging trace, counted above) and the scans' two
+                // block buffers of draws + log densities (one per scan stream), sized as pfmi_elbo_batch_enqueue sizes them
+                for (const DevBuf *b : {&c->lc_X, &c->lc_out, &c->lc_x, &c->lc_g, &c->lc_p, &c->lb_hs, &c->lb_hy, &c->dcb_x[0], &c->dcb_x[1],
+                                        &c->dcb_lp[0], &c->dcb_lp[1]}) have += (double)b->cap;
+                need += 8.0 * K * ((6.0 + 2.0 * J) * d + 1.0) + (double)K * pf_lbc_path_state_bytes(J);
+                const int64_t per = (int64_t)d * N;
+                dcb_chunk = devcb_chunk_fits(c, per, nf, N);
+                if (2.0 * sizeof(double) * (double)dcb_chunk * (double)(per + N) > 0.5 * have) dcb_chunk = (dcb_chunk + 1) / 2;
+                if (dcb_chunk < 1) dcb_chunk = 1;
+                need += 2.0 * sizeof(double) * (double)dcb_chunk * (double)(per + N);
+            }
             PF_CHECK(need < 0.8 * have, PFMI_ERR_UNSUPPORTED, "stream_enqueue: the fixed-stride layout needs %.1f GB for %d paths x %lld slots "
                      "(%.1f GB available): use the packed route", need / 1e9, K, (long long)cap, have / 1e9);
+        } else if (closure) {
+            dcb_chunk = devcb_chunk_fits(c, (int64_t)d * N, nf, N);
         }
     }
     // ---- every allocation BEFORE the first launch (a hipFree behind a grown buffer would synchronise the device in mid-flight)
@@ -804,6 +848,13 @@ static int32_t stream_enqueue_impl(pfmi_ctx *c, int32_t K, const double *x0, int
     PF_TRY(c->d_off.ensure(sizeof(int64_t) * (K + 1)));
     PF_TRY(c->d_path_of.ensure(sizeof(int32_t) * Pz));
     for (int q = 0; q < 2; ++q) PF_TRY(qf_share_reserve(c, q, (size_t)ncu * 1700 * sizeof(double) + ((size_t)ncu + 1) * sizeof(unsigned) + (64 << 10)));
+    if (closure) {
+        PF_TRY(pf_lbc_alloc(c, K, J, d));
+        for (int q = 0; q < 2; ++q) {                                   // block buffers of the scans: one per scan stream (ctx stream, s_scan1)
+            PF_TRY(c->dcb_x[q].ensure(sizeof(double) * (size_t)dcb_chunk * dz * (size_t)N));
+            PF_TRY(c->dcb_lp[q].ensure(sizeof(double) * (size_t)dcb_chunk * (size_t)N));
+        }
+    }
     if (!c->s_opt) {
         int lo = 0, hi = 0;
         PF_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));              // (hi is the numerically smaller = more urgent one)
@@ -818,7 +869,6 @@ static int32_t stream_enqueue_impl(pfmi_ctx *c, int32_t K, const double *x0, int
         PF_HIP(hipHostMalloc(reinterpret_cast<void **>(&c->h_prog), sizeof(int32_t) * 2 * (size_t)K, hipHostMallocCoherent | hipHostMallocMapped));
         c->h_prog_cap = 2 * K;
     }
-    const int64_t nf = (int64_t)K * (cap - 1);
     const size_t list_bytes = (size_t)(nf > 0 ? nf : 1) * (sizeof(uint64_t) + sizeof(int32_t));
     if (c->h_list_cap < list_bytes) {
         if (c->h_list) (void)hipHostFree(c->h_list);
@@ -864,7 +914,7 @@ static int32_t stream_enqueue_impl(pfmi_ctx *c, int32_t K, const double *x0, int
         R = pfmi_ctx::StreamRun();
         R.seeds_pt.swap(keep);
     }
-    R.K = K; R.J = J; R.cap = (int)cap; R.N = N; R.eps = eps;
+    R.K = K; R.J = J; R.cap = (int)cap; R.N = N; R.eps = eps; R.closure = closure; R.dcb_chunk = dcb_chunk;
     R.d_lseeds = reinterpret_cast<uint64_t *>(c->seeds.as<char>() + off_ls);
     R.d_list = reinterpret_cast<int32_t *>(c->seeds.as<char>() + off_li);
     // a segment should fill at least half the CUs with one workgroup per fit
@@ -884,10 +934,18 @@ static int32_t stream_enqueue_impl(pfmi_ctx *c, int32_t K, const double *x0, int
     c->stream_pending = true;
     PF_HIP(hipEventRecord(c->sg_start, c->stream));
     for (hipStream_t s : {c->s_opt, c->s_fit, c->s_scan1}) PF_HIP(hipStreamWaitEvent(s, c->sg_start, 0));
+    c->lbc.rounds = 0; c->lbc.columns = 0;
     {   // ---- the producer
         StreamSwap sw(c, c->s_opt);
         pf_kernel_begin(c);
-        PF_TRY(pf_launch_lbfgs(c, K, J, maxiters, g_tol, c->lb_x0.as<double>(), R.pub - 1, c->h_prog));
+        if (closure) {
+            // its init kernel now; the rounds (closure + step kernel, on s_opt) are issued by the pump.  Every round that records a row
+            // publishes the count, so R.pub only sets where the segments may be cut.
+            lbc_begin(c, K, J, maxiters, g_tol, c->h_prog);
+            PF_TRY(pf_launch_lbc_init(c, c->s_opt));
+        } else {
+            PF_TRY(pf_launch_lbfgs(c, K, J, maxiters, g_tol, c->lb_x0.as<double>(), R.pub - 1, c->h_prog));
+        }
         pf_kernel_end(c, "optimize");
         PF_HIP(hipEventRecord(c->sg_opt, c->s_opt));
     }
@@ -900,7 +958,7 @@ static int32_t stream_enqueue_impl(pfmi_ctx *c, int32_t K, const double *x0, int
 // half-made results are forgotten, the context is usable again.  No call outstanding: no-op.
 int32_t pfmi_stream_cancel(pfmi_ctx *c) {
     PF_CTX(c);
-    if (!c->sr.active && !c->stream_pending) return PFMI_OK;
+    if (!c->sr.active && !c->stream_pending && !c->stream_drain) return PFMI_OK;
     stream_abandon(c);
     (void)hipStreamSynchronize(c->stream);
     c->fitted = false; c->elbo_done = false; c->elbo_pending = false; c->pooled = false;
@@ -939,10 +997,14 @@ static int32_t stream_pump_pass(pfmi_ctx *c, int32_t *finished) {
     if (finished) *finished = R.active ? 0 : 1;
     if (!R.active) return PFMI_OK;
     const int K = R.K;
+    // a closure producer: the rounds it may have in flight are issued first (the gradient closure is called here, on s_opt).  Once the
+    // optimisation has finished -- no path running, or the hard cap -- every published count is final.
+    if (R.closure && !c->lbc.finished) PF_TRY(lbc_issue_rounds(c, c->s_opt));
+    const bool opt_over = R.closure && c->lbc.finished;
     bool all_done = true;
     int avail = INT_MAX, lmax = 0;
     for (int k = 0; k < K; ++k) {
-        const int dn = __atomic_load_n(c->h_prog + K + k, __ATOMIC_ACQUIRE);         // flag first: a raised flag means the count is final
+        const int dn = opt_over ? 1 : __atomic_load_n(c->h_prog + K + k, __ATOMIC_ACQUIRE);     // flag first: a raised flag means the count is final
         const int n = __atomic_load_n(c->h_prog + k, __ATOMIC_ACQUIRE);
         c->npts_h[(size_t)k] = dn ? n : -n;                                           // (negative: still running, at least that many points)
         if (!dn) { all_done = false; if (n < avail) avail = n; }
@@ -955,17 +1017,20 @@ static int32_t stream_pump_pass(pfmi_ctx *c, int32_t *finished) {
         // progress alone ends it only after PFMI_STREAM_TIMEOUT_S seconds (default 60: a host that pumps rarely or a GPU shared with another
         // process must not trip it), and never with a device-wide synchronise -- that would block for ever behind a hung kernel and stall
         // every other context of the device.  The context's own side streams are drained by the next entry point that reuses its memory.
+        // An error exit leaves the call in the "needs drain" state (stream_drain): the next entry point that reuses its memory drains the
+        // side streams.
         const hipError_t q = hipStreamQuery(c->s_opt);
         if (q != hipSuccess && q != hipErrorNotReady) {
-            R.active = false; c->stream_pending = false;
+            R.active = false; c->stream_pending = false; c->stream_drain = true;
             PF_CHECK(false, PFMI_ERR_HIP, "stream_pump: the optimiser's stream reports %s", hipGetErrorString(q));
         }
-        if (avail != R.last_min) { R.last_min = avail; R.t_progress = now; }
+        const int64_t rnd = R.closure ? c->lbc.seen : -1;                            // a closure round that has completed is progress too
+        if (avail != R.last_min || rnd != R.last_round) { R.last_min = avail; R.last_round = rnd; R.t_progress = now; }
         else {
             double limit = 60.0;
             if (const char *tl = pf_debug_get("PFMI_STREAM_TIMEOUT_S")) { const double v = atof(tl); if (v > 0) limit = v; }
             if (std::chrono::duration<double>(now - R.t_progress).count() > limit) {
-                R.active = false; c->stream_pending = false;
+                R.active = false; c->stream_pending = false; c->stream_drain = true;
                 PF_CHECK(false, PFMI_ERR_HIP, "stream_pump: the optimiser made no progress for %.0f s (stream state: %s)", limit, hipGetErrorString(q));
             }
         }
@@ -1035,8 +1100,27 @@ static int32_t stream_pump_pass(pfmi_ctx *c, int32_t *finished) {
             PF_HIP(hipMemcpyAsync(R.d_lseeds + R.s0, hs + R.s0, sizeof(uint64_t) * (size_t)ns, hipMemcpyHostToDevice, ss));
             PF_HIP(hipMemcpyAsync(R.d_list + R.s0, hl + R.s0, sizeof(int32_t) * (size_t)ns, hipMemcpyHostToDevice, ss));
             PF_HIP(hipStreamWaitEvent(ss, c->sg_fit, 0));
-            PF_TRY(pf_launch_elbo_draws(c, R.d_list + R.s0, R.d_lseeds + R.s0, ns, 0, R.N, nullptr, 0, nullptr, 0, c->logp.as<double>(),
-                                        c->logq.as<double>(), R.N, true, true));
+            if (R.closure) {
+                // the device-closure scan of pfmi_elbo_batch_enqueue on this segment's work list, in blocks of this stream's buffer: the
+                // draw writer, the user's value closure on the scan stream, the scatter into the point-indexed table (a failed fit's rows
+                // become NaN there).  Same kernels on the same (fit, seed) pairs: the packed route's bits.
+                const int64_t per = (int64_t)c->d * R.N;
+                double *bx = c->dcb_x[qq].as<double>(), *blp = c->dcb_lp[qq].as<double>();
+                for (int64_t b0 = 0; b0 < ns; b0 += R.dcb_chunk) {
+                    const int64_t nb = ns - b0 < R.dcb_chunk ? ns - b0 : R.dcb_chunk;
+                    const int32_t *pl = R.d_list + R.s0 + b0;
+                    PF_TRY(pf_launch_elbo_draws(c, pl, R.d_lseeds + R.s0 + b0, nb, 0, R.N, nullptr, 0, bx, per, c->logp.as<double>(),
+                                                c->logq.as<double>(), R.N, false, true));
+                    pf_kernel_begin(c);
+                    c->target.dev_fn(bx, c->d, nb * R.N, blp, (void *)ss, c->target.user);
+                    pf_kernel_end(c, "device_callback");
+                    PF_HIP(hipGetLastError());
+                    PF_TRY(pf_launch_scatter_rows(c, nb, R.N, pl, blp, c->logp.as<double>()));
+                }
+            } else {
+                PF_TRY(pf_launch_elbo_draws(c, R.d_list + R.s0, R.d_lseeds + R.s0, ns, 0, R.N, nullptr, 0, nullptr, 0, c->logp.as<double>(),
+                                            c->logq.as<double>(), R.N, true, true));
+            }
             PF_HIP(hipEventRecord(c->sg_scan[qq], ss));
             R.scan_used[qq] = true;
             R.scan_ns[qq] = ns;
@@ -1052,6 +1136,10 @@ static int32_t stream_pump_pass(pfmi_ctx *c, int32_t *finished) {
         PF_CHECK(c->npts_h[(size_t)k] >= 1 && c->npts_h[(size_t)k] <= R.cap, PFMI_ERR_NUMERIC, "stream: path %d produced %d points", k, c->npts_h[(size_t)k]);
     }
     PF_HIP(hipEventRecord(c->sg_fit, c->s_fit));
+    if (R.closure) {
+        c->lbc.finished = true;                                     // every path has ended: no further round is issued
+        PF_HIP(hipEventRecord(c->sg_opt, c->s_opt));                // behind the last round issued
+    }
     PF_HIP(hipStreamWaitEvent(c->stream, c->sg_opt, 0));
     PF_HIP(hipStreamWaitEvent(c->stream, c->sg_fit, 0));
     if (R.scan_used[1]) PF_HIP(hipStreamWaitEvent(c->stream, c->sg_scan[1], 0));

@@ -84,6 +84,7 @@ struct LbcState {
     int64_t issued = 0, seen = 0, max_rounds = 0;     // step rounds launched / last round whose progress the host has read / hard cap
     bool finished = false;
     int64_t rounds = 0, columns = 0;                  // statistics of the last optimisation (pfmi_optimize_stats)
+    int32_t *h_prog = nullptr;                        // streaming: the pipeline's progress words (pf_lbc_step_kernel publishes); null: packed
 };
 
 struct pfmi_ctx {
@@ -150,8 +151,13 @@ struct pfmi_ctx {
         std::chrono::steady_clock::time_point t_progress, t_start;
         std::vector<double> trace;            // PFMI_STREAM_TRACE: (t_us, l0, l1, fits, scan stream) per segment
         double host_s = 0.0; int host_n = 0;   // host time of the scheduling passes that LAUNCHED something (not the idle polls), and their number
+        bool closure = false;                 // the producer is the closure optimiser (rounds issued by the pump); the scans call the closure
+        int64_t dcb_chunk = 1;                // closure scans: fits whose draws one block of dcb_x holds
+        int64_t last_round = -1;              // closure: the last optimiser round seen (progress for the watchdog)
     } sr;
     bool stream_pending = false;
+    bool stream_drain = false;                // a streaming call ended by an error exit: its side streams are drained by the next entry point that
+                                              // reuses its memory (pfmi_stream_cancel / _enqueue, pfmi_set_traces, pfmi_optimize_batch_enqueue)
     bool qf_seg_mode = false;                 // scan launches of a segment that is not the last: one workgroup per fit, no tail cut (they overlap)
     // the trace as the kernels see it: the packed buffers, or -- streaming layout -- the optimiser's staging buffers themselves
     double *th() const { return virt ? st_theta.as<double>() : theta.as<double>(); }
@@ -293,8 +299,8 @@ int32_t pf_launch_lbfgs(pfmi_ctx *c, int K, int J, int maxiters, double g_tol, c
 int32_t pf_launch_trace_pack(pfmi_ctx *c, int64_t cap);
 size_t pf_lbc_path_state_bytes(int J);
 int32_t pf_lbc_alloc(pfmi_ctx *c, int K, int J, int d);
-int32_t pf_launch_lbc_init(pfmi_ctx *c);
-int32_t pf_launch_lbc_step(pfmi_ctx *c, int64_t round);
+int32_t pf_launch_lbc_init(pfmi_ctx *c, hipStream_t s);
+int32_t pf_launch_lbc_step(pfmi_ctx *c, int64_t round, hipStream_t s);
 int32_t pf_launch_woodbury_prim(pfmi_ctx *c, int mode, int64_t p, int64_t N, const double *d_in, double *d_out);
 int32_t pf_launch_colsumsq(pfmi_ctx *c, int64_t N, const double *d_x, double *d_out);
 int32_t pf_launch_woodbury_diag(pfmi_ctx *c, int64_t p, double *d_out);

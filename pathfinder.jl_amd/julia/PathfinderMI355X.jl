@@ -830,6 +830,10 @@ end
 # per-point table; `seeds` = the runs' predrawn streams, `maxiters + 1` values per run (`rand!(copy(rng_k), Vector{UInt64}(undef, maxiters + 1))`).
 #   stream_enqueue!(eng, x0; ...)  ->  stream_seeds!(eng, seeds)  ->  npts = stream_wait!(eng, K)  ->  _pool_build_best! / psis_resample ...
 # stream_wait! only schedules (it returns when the last segment is enqueued); several engines: call stream_pump! on each in turn.
+# Targets: GaussTarget, FunnelTarget, and a DeviceClosureTarget with a gradient launcher (history_length <= 16).  Its launchers are called
+# from inside stream_pump! / stream_wait! on the calling task: the gradient launcher once per optimiser round with the pipeline's optimiser
+# stream, the value launcher once per block of a segment's ELBO scan with that segment's scan stream.  An exception in a launcher must not
+# unwind through the C frames: record it, return, and call stream_cancel! before rethrowing.
 function stream_enqueue!(eng::Engine, x0::Matrix{Float64}, ndraws_elbo::Int; history_length::Int=6, maxiters::Int=1000, g_tol::Float64=1e-8,
                          ϵ::Float64=1e-12, seeds::Union{Nothing,Vector{UInt64}}=nothing)
     K = size(x0, 2)

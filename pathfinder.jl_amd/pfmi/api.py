@@ -414,6 +414,15 @@ def _use_device_optimizer(target, optimizer, history_length=DEFAULT_HISTORY_LENG
     return optimizer == "device"
 
 
+def _use_stream(target, on_device, history_length=DEFAULT_HISTORY_LENGTH):
+    """the streaming pipeline (pfmi_stream_enqueue: fits and ELBO scans while the paths are still being optimised) for a run that optimises
+    on the device: built-in targets and device closures with a gradient, history_length <= 16 (the pipeline pads to 32 columns), unless
+    PFMI_NO_STREAM=1.  (A shape the library cannot stream is refused with -4 and takes the packed route.)"""
+    if not on_device or history_length > 16 or os.environ.get("PFMI_NO_STREAM") == "1":
+        return False
+    return getattr(target, "kind", 2) in (0, 1) or _closure_gradient(target)
+
+
 # ---- batched driver shared by pathfinder / multipathfinder ------------------------------------------------
 def _comm_for(engs):
     """the pfmi_comm joining `engs` (cached on the first engine; a single engine forms a world of one without RCCL)"""
@@ -458,7 +467,7 @@ def _run_paths(engs, target, inits, run_rngs, *, dim, history_length, ndraws_elb
     pending = list(range(K))
     on_device = _use_device_optimizer(target, optimizer, history_length)
     closure_opt = on_device and _closure_gradient(target)
-    stream_ok = on_device and not closure_opt and history_length <= 16 and os.environ.get("PFMI_NO_STREAM") != "1"
+    stream_ok = _use_stream(target, on_device, history_length)
     okw = {k: v for k, v in optimizer_kwargs.items() if k in ("maxiters", "g_tol")}
     pooled = None
     while pending:

@@ -262,14 +262,22 @@ class Engine:
         check(self.L.pfmi_stream_seeds(self.ctx, seeds.ctypes.data_as(_u64p)))
 
     def stream_pump(self):
-        """one scheduling pass of the pipeline (never blocks); True once its last segment has been launched"""
+        """one scheduling pass of the pipeline (never blocks); True once its last segment has been launched.  A closure target's closures
+        are called from inside this pass; an exception raised by one cancels the call and propagates."""
         fin = C.c_int32()
-        check(self.L.pfmi_stream_pump(self.ctx, C.byref(fin)))
+        rc = self.L.pfmi_stream_pump(self.ctx, C.byref(fin))
+        if getattr(self.target, "pending_error", None) is not None:
+            self.stream_cancel()
+            self._raise_target_error()
+        check(rc)
         return bool(fin.value)
 
     def stream_wait(self):
         """points per path of the last stream_enqueue (the first wait of that call)"""
         npts = np.empty(self.K, dtype=np.int64)
+        if getattr(self.target, "has_device_gradient", False):
+            while not self.stream_pump():               # (a closure that raises is re-raised here, not inside the C wait)
+                pass
         check(self.L.pfmi_stream_wait(self.ctx, npts.ctypes.data_as(_i64p)))
         self.npoints = npts
         return npts
