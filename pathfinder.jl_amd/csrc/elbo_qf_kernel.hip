@@ -473,7 +473,7 @@ __global__ __launch_bounds__(QF_THREADS) void pf_elbo_qf_kernel(ElboArgs A, int 
                     }
                 } else {
                     // one block of both groups; the body exists twice: interior blocks (no row masking, no head transform) and the
-                    // first / second / last block, selected by ONE wave-uniform branch per block
+                    // first / second / last block (see the block loop below)
                     // KC >= 16 with two groups (round 3): the block is MFMA dominated (2 x 4 x 2 NT quarter-size MFMAs), registers are the
                     // scarce resource -- one set of pending look-ups at a time, and the A tiles of ONE k-step (4 rows) live at a time,
                     // shared by both groups' MFMAs (the r loop is outermost)
@@ -547,8 +547,7 @@ __global__ __launch_bounds__(QF_THREADS) void pf_elbo_qf_kernel(ElboArgs A, int 
                     // counts at the loop head have to cover the unknown entry state and become a full `s_waitcnt lgkmcnt(0)` in EVERY
                     // block (the previous block's table reads drained before the next block's operand reads issue: +0.7 % per scan)
                     __builtin_amdgcn_s_waitcnt(0xC07F);
-                    for (int bl = 0; bl < nb; ++bl) {
-                        const int blk = blk0 + bl;
+                    auto prio_turn = [&](const int blk) {
 #if QF_PRIO_FAIR
                         // the two waves of a SIMD (w and w + 4) take turns at the higher issue priority, QF_PRIO_FAIR blocks at a time (see the
                         // note on wave balance at the launch code)
@@ -556,8 +555,31 @@ __global__ __launch_bounds__(QF_THREADS) void pf_elbo_qf_kernel(ElboArgs A, int 
                             if (((blk / QF_PRIO_FAIR) ^ (wv >> 2) ^ lb) & 1) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0);
                         }
 #endif
-                        if (__builtin_expect((blk == 0) | (blk == nblk - 1) | (KC > 16 && blk == 1), 0)) block_body(bl, std::true_type{});
-                        else block_body(bl, std::false_type{});
+                    };
+                    if constexpr (NG == 2 && KC >= 16) {
+                        // register-lean body: ONE loop, the body selected per block (it has no accumulator copies to lose; peeled like
+                        // below, its three inlined special bodies put 880 B per thread on the stack)
+                        for (int bl = 0; bl < nb; ++bl) {
+                            const int blk = blk0 + bl;
+                            prio_turn(blk);
+                            if (__builtin_expect((blk == 0) | (blk == nblk - 1) | (KC > 16 && blk == 1), 0)) block_body(bl, std::true_type{});
+                            else block_body(bl, std::false_type{});
+                        }
+                    } else {
+                        // The special blocks (the first, the second when KC > 16, the last) are peeled off the interior loop: blocks [0, s_lo)
+                        // and [s_hi, nb) of this chunk run the special body as straight-line code, [s_lo, s_hi) the interior loop, in block
+                        // order.  (Round 6 selected the body per block inside the one loop: the accumulators then merged from two bodies at
+                        // the latch, 20 v_mov_b64 per block at <12, 1, 8, 2>, ~4 % of the block's issue -- tools/qf_issue_count.py,
+                        // profiles/r07_scan_issue.md.  The special blocks as a loop of their own kept both loops' invariants alive across
+                        // both: 56 -> 260 B of scratch.)
+                        constexpr int LEAD = (KC > 16) ? 2 : 1;
+                        const int s_lo = (LEAD - blk0 <= 0) ? 0 : (LEAD - blk0 < nb ? LEAD - blk0 : nb);
+                        const int s_hi = (blk0 + nb == nblk) ? (nb - 1 > s_lo ? nb - 1 : s_lo) : nb;   // [s_hi, nb): at most the last block
+#pragma unroll
+                        for (int bl = 0; bl < LEAD; ++bl)
+                            if (bl < s_lo) { prio_turn(blk0 + bl); block_body(bl, std::true_type{}); }
+                        for (int bl = s_lo; bl < s_hi; ++bl) { prio_turn(blk0 + bl); block_body(bl, std::false_type{}); }
+                        if (s_hi < nb) { prio_turn(blk0 + s_hi); block_body(s_hi, std::true_type{}); }
                     }
                 }
             }
