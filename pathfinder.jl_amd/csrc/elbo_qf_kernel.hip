@@ -7,7 +7,9 @@
 //   sum_i a_i e_i^2 = C0 + sum a s^2 z^2 + 2 sum a c s z  +  tv'M tv - 2 tv'(v + A3),      A3 = Vh'(a s^2 . z)
 //   Wd'e            = t0 + A4 - Nn tv,                                                        A4 = Wd'(s . z)
 // with per-fit constants C0 = sum a c^2, M = Vh' diag(a s^2) Vh, v = Vh'(a c s), t0 = Wd'c, Nn = Wd' diag(s) Vh
-// (computed by the scan itself from "pseudo draws", see the kernel).  One pass over the rows therefore accumulates, per draw, |u|^2, two scalars and the three skinny
+// (computed by the scan itself from "pseudo draws", see the kernel).  The draws fold the linear term into the A3 operand: they
+// accumulate A3' = Vh'(a s^2 z + 2 a c s) = A3 + 2v, whose row operand is the same fma that feeds the scalar sum a s^2 z^2 + 2 a c s z,
+// and the draw's finish uses -2 tv'(A3' - v).  One pass over the rows therefore accumulates, per draw, |u|^2, two scalars and the three skinny
 // contractions w = Vh'z, A3, A4 -- all with the SAME A operand tiles -- and the draw is finished with O(KC^2) flops.
 // (Verified against the direct evaluation in extended precision: same 1e-14 relative error, no cancellation, because
 // every term is a sum of squares or a projection of one.)
@@ -56,7 +58,8 @@
 #ifndef QF_SETPRIO
 #define QF_SETPRIO 0                   // s_setprio level during a group's MFMA burst (0 = off; A/B in profiles/r03_scan_experiments.md)
 #endif
-#define QF_MIN_FRONT 1024             // doubles in front of the inverse-CDF table (>= (32 - 19) * 32 * 2 = 832)
+#define QF_MIN_FRONT 1024             // doubles in front of the inverse-CDF table (>= 2 * PF_ICDF_BFE_FRONT = 704)
+static_assert(QF_MIN_FRONT >= 2 * PF_ICDF_BFE_FRONT, "the look-up's front guard");
 // blocks (of 16 rows) per streamed chunk; KC = 32 halves it: two staging buffers of 16 blocks x 32 columns would not fit 160 KB of LDS
 // (round 3: history_length 11..16 with d > ~1000 used to fail with "LDS too large")
 template <int KC> struct qf_chb { static constexpr int v = (KC > 20) ? 8 : 16; };
@@ -110,6 +113,10 @@ __global__ __launch_bounds__(QF_THREADS) void pf_elbo_qf_kernel(ElboArgs A, int 
 #endif
     constexpr int NT = KC / 4, TR = RPAD / 4, NC = qf_nconst(KC, RPAD);
     constexpr int QF_CHB = qf_chb<KC>::v;
+    // real draws accumulate A3' = A3 + 2v (the linear term folded into the A3 operand, see the top of the file) -- except in the
+    // register-lean body (two groups, KC >= 16): there the fused operand needs both row scalars at once, and the extra LDS waits and
+    // wait states cost more than the saved f64 adds (tools/qf_issue_count.py at <20, 2, 0, 2>)
+    constexpr bool FOLD = !(NG == 2 && KC >= 16);
     constexpr int PRE = (QF_CHB * 16 * KC + QF_THREADS - 1) / QF_THREADS;      // prefetch registers per thread (streaming)
     const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63, q = lane >> 4, c = lane & 15, l3 = lane & 3;
     const int d = A.d, nblk = (d + 15) >> 4;
@@ -151,14 +158,15 @@ __global__ __launch_bounds__(QF_THREADS) void pf_elbo_qf_kernel(ElboArgs A, int 
     // ---- LDS carve-up (offsets in doubles from `lds`; plain offsets keep every access a ds_ instruction)
     const int vh_sz = ch_blocks * 16 * KC, rs_sz = ch_blocks * 48;
     const int buf_stride = (nchunks > 1) ? vh_sz + rs_sz : 0;       // second staging buffer only when streaming
-    // the clamp-free interval look-up may read up to 13 binades x 32 x 16 B = 6.5 KB in FRONT of the table: keep at least that much
-    // staged data before it (only matters for d < 64)
+    // the clamp-free interval look-up (pf_icdf_issue_bfe) may read up to PF_ICDF_BFE_FRONT x 16 B = 5.5 KB in FRONT of the table: keep at
+    // least that much staged data before it (only matters for d < 64); the PF_ICDF_BFE_BEHIND entries behind it are the end of the
+    // allocation (qf_lds_bytes)
     const int stage_sz = (nchunks > 1 ? 2 : 1) * (vh_sz + rs_sz);
     const int fix_off = stage_sz > QF_MIN_FRONT ? stage_sz : QF_MIN_FRONT;
     double *t_s = lds + fix_off;                   // [KC][KC]
     double *cn_s = t_s + KC * KC;                  // [NC]
     double *g_s = cn_s + NC;                       // [RPAD][RPAD]
-    double2 *icdf = reinterpret_cast<double2 *>(g_s + RPAD * RPAD + ((KC * KC + NC + RPAD * RPAD) & 1));   // [2 * 608] inverse-CDF table
+    double2 *icdf = reinterpret_cast<double2 *>(g_s + RPAD * RPAD + ((KC * KC + NC + RPAD * RPAD) & 1));   // [2 * 608] inverse-CDF table + guard
 
     const double *Vh = A.vh + (size_t)p * d * KC, *mu = A.mu + (size_t)p * d, *sqa = A.sqrt_alpha + (size_t)p * d;
     auto stage_direct = [&](int ck, int buf) {
@@ -294,7 +302,7 @@ __global__ __launch_bounds__(QF_THREADS) void pf_elbo_qf_kernel(ElboArgs A, int 
         // shared by the alternating groups -- was built and measured in round 2: 25.3 vs 24.7 ms for two groups, 121 vs 95 ms for
         // one group at d = 10^4; with no MFMA / VALU co-issue on gfx950 there is nothing to hide the look-ups behind.)
         struct Pend { uint32_t x[4]; double dp[4]; double2 c01[4], c23[4]; };
-        const uint32_t icdf_adj = pf_icdf_adj<PF_ICDF_NB_LDS>(icdf);
+        const uint32_t icdf_adj = pf_icdf_adj_bfe<PF_ICDF_NB_LDS>(icdf);
         auto gen_issue = [&](const int g, const int blk, Pend &P) {
 #if QF_ABLATE == 1                     // ablation (timing experiments only): no generator at all
 #pragma unroll
@@ -306,7 +314,7 @@ __global__ __launch_bounds__(QF_THREADS) void pf_elbo_qf_kernel(ElboArgs A, int 
 #else
             pf_philox_normals(n[g], (uint32_t)(blk * 4 + q), 0u, 0u, k0, k1, P.x);
 #pragma unroll
-            for (int r = 0; r < 4; ++r) pf_icdf_issue_adj<PF_ICDF_NB_LDS>(P.x[r], icdf_adj, P.dp[r], P.c01[r], P.c23[r]);
+            for (int r = 0; r < 4; ++r) pf_icdf_issue_bfe<PF_ICDF_NB_LDS>(P.x[r], icdf_adj, P.dp[r], P.c01[r], P.c23[r]);
 #endif
         };
         for (int ck = 0; ck < nchunks; ++ck) {
@@ -352,28 +360,33 @@ __global__ __launch_bounds__(QF_THREADS) void pf_elbo_qf_kernel(ElboArgs A, int 
                             for (int T = 0; T < TR; ++T) o.wd[r][T] = wp[r * 16 + 4 * T];
                     }
                 };
-                // the contractions of one group: w = Vh'z, A3 = Vh'(a s^2 z), A4 = Wd'(s z), and the two scalars
+                // the contractions of one group: w = Vh'z, A3' = Vh'(a s^2 z + 2 a c s) (real draws, FOLD; a pseudo group, with_w = false,
+                // accumulates A3 = Vh'(a s^2 z) so that M and v come out directly, without the cancellation M = A3' - 2v), A4 = Wd'(s z),
+                // and the two scalars
                 auto contract = [&](const int g, const double (&z)[4], const Ops &o, const bool with_w) {
 #if QF_SETPRIO                         // experiment (round 3): raise the wave's priority for its MFMA burst
                     __builtin_amdgcn_s_setprio(QF_SETPRIO);
 #endif
+                    // the B operands of the whole group first: each lands well before the MFMAs that read it (no s_nop in between)
+                    double bp[4], bs[4];
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        const double zr = z[r];
-                        double bp = 0.0;
-                        if (TGT != 0) {
-                            bp = o.rs[r] * zr;
-                            q12[g] = fma(bp + o.rs[4 + r], zr, q12[g]);
-                        }
+                        bp[r] = 0.0; bs[r] = 0.0;
+                        if (TGT != 0) bp[r] = (with_w && FOLD) ? fma(o.rs[r], z[r], o.rs[4 + r]) : o.rs[r] * z[r];
+                        if (TGT == 1 && RPAD > 0) bs[r] = o.rs[8 + r] * z[r];
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        if (TGT != 0) q12[g] = fma((with_w && FOLD) ? bp[r] : bp[r] + o.rs[4 + r], z[r], q12[g]);
 #pragma unroll
                         for (int T = 0; T < NT; ++T) {
-                            if (with_w) accw[g][T] = qf_mfma4(o.av[r][T], zr, accw[g][T]);
-                            if (TGT != 0) acc3[g][T] = qf_mfma4(o.av[r][T], bp, acc3[g][T]);
+                            if (with_w) accw[g][T] = qf_mfma4(o.av[r][T], z[r], accw[g][T]);
+                            if (TGT != 0) acc3[g][T] = qf_mfma4(o.av[r][T], bp[r], acc3[g][T]);
                         }
                         if (TGT == 1 && RPAD > 0) {
-                            const double bs = o.rs[8 + r] * zr;
 #pragma unroll
-                            for (int T = 0; T < TR; ++T) acc4[g][T] = qf_mfma4(o.wd[r][T], bs, acc4[g][T]);
+                            for (int T = 0; T < TR; ++T) acc4[g][T] = qf_mfma4(o.wd[r][T], bs[r], acc4[g][T]);
                         }
                     }
 #if QF_SETPRIO
@@ -732,7 +745,8 @@ __global__ __launch_bounds__(QF_THREADS) void pf_elbo_qf_kernel(ElboArgs A, int 
                 matvec(Mm, KC, KC, std::integral_constant<int, NT>{}, std::integral_constant<int, NT>{}, std::false_type{}, tvd, mt);
                 double qa = 0.0;
 #pragma unroll
-                for (int T = 0; T < NT; ++T) qa = fma(tvd[T], mt[T] - 2.0 * (vv[4 * T + qe] + acc3[g][T]), qa);
+                for (int T = 0; T < NT; ++T)
+                    qa = fma(tvd[T], mt[T] - 2.0 * (FOLD ? acc3[g][T] - vv[4 * T + qe] : vv[4 * T + qe] + acc3[g][T]), qa);   // A3' - v = A3 + v
                 qa = pf_sum_q(qa);
                 const double q1 = cn_s[0] + qs + qa;
                 if (TGT == 1) {
@@ -780,7 +794,7 @@ static size_t qf_lds_bytes(int ch_blocks, int nchunks, int kc, int rpad) {
     const size_t per = (size_t)ch_blocks * 16 * kc + (size_t)ch_blocks * 48;
     size_t stage = per * (nchunks > 1 ? 2 : 1);
     if (stage < QF_MIN_FRONT) stage = QF_MIN_FRONT;
-    return sizeof(double) * (stage + (size_t)kc * kc + qf_nconst(kc, rpad) + (size_t)rpad * rpad + 1 + 4 * PF_ICDF_LDS_ENTRIES);
+    return sizeof(double) * (stage + (size_t)kc * kc + qf_nconst(kc, rpad) + (size_t)rpad * rpad + 1 + 4 * PF_ICDF_LDS_ENTRIES + 2 * PF_ICDF_BFE_BEHIND);
 }
 
 template <int KC, int TGT, int RPAD, int NG>

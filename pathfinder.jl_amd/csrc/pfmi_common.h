@@ -376,7 +376,7 @@ __device__ __forceinline__ void pf_philox_normals(uint32_t c0, uint32_t c1, uint
 // tools/gen_icdf_table.py, which documents the construction): p = (mag + 1/2) 2^-32; exponent / top-5 mantissa bits of v = (double) mag
 // select a table entry, z = +-(c0 + v (c1 + v (c2 + v c3))) -- the cubic of every interval in GLOBAL monomial form in v (the 1/2 folded
 // into the coefficients).  Only exactly rounded IEEE operations (cvt, fma) => bit-identical to the CPU checker (pfo_randn4).
-// 8 VALU instructions + two 16-byte LDS reads per normal in the scan's form (pf_icdf_issue_adj), round 1's Box-Muller: ~27 + Philox.  Words with mag < 2^PF_ICDF_TAILBITS (probability 2^-19) are refined with a second Philox word
+// 7 VALU instructions + two 16-byte LDS reads per normal in the scan's form (pf_icdf_issue_bfe; 8 with the clamp of pf_icdf_issue_adj), round 1's Box-Muller: ~27 + Philox.  Words with mag < 2^PF_ICDF_TAILBITS (probability 2^-19) are refined with a second Philox word
 // (counter word 3 = 1) so that the tails reach |z| = 9.1 with >= 12 bits of resolution.
 static __device__ const double PF_ICDF_TAB_DEV[PF_ICDF_ENTRIES][4] = { PF_ICDF_TABLE_ROWS };
 
@@ -453,6 +453,41 @@ __device__ __forceinline__ void pf_icdf_issue_adj(uint32_t x, uint32_t adj, doub
     idx = max(idx, (unsigned)(PF_ICDF_IDX0 - ((32 << PF_ICDF_B) - 1)));
 #endif
     asm("" : "+v"(idx));                                            // keeps (idx << 4) + adj one v_lshl_add_u32 (else: shift, mask, add)
+    const pf_lds_d2 e = (pf_lds_d2)(uintptr_t)(adj + (idx << 4));
+    const pf_v2d a = e[0], b = e[NENT];
+    c01 = make_double2(a.x, a.y); c23 = make_double2(b.x, b.y);
+}
+// The same look-up without the clamp (the ELBO scan): the interval index is one v_bfe_u32 of hi32(v) -- the 5 mantissa bits and the
+// LOW 5 bits of the exponent -- instead of a shift and a v_max_u32.  The 19 binades of the LDS copy (exponents 1035 .. 1053) do not
+// wrap modulo 32, so their slots are those of pf_icdf_issue_adj; every other word (mag < 2^12, fixed up by the caller) gets an index in
+// [0, 1024) as well, i.e. at most PF_ICDF_BFE_FRONT entries in front of the table and PF_ICDF_BFE_BEHIND entries behind its second
+// coefficient array: the caller reserves both guards inside its LDS allocation.
+#define PF_ICDF_BFE_BITS 10
+template <int NB = PF_ICDF_NB_LDS>
+struct pf_icdf_bfe {
+    static constexpr int NENT = NB << PF_ICDF_B;
+    static constexpr int SLOT0 = PF_ICDF_IDX0 - (NENT - 1);
+    static constexpr int BASE = SLOT0 & ((1 << PF_ICDF_BFE_BITS) - 1);          // bfe index of LDS slot 0
+    static_assert((PF_ICDF_IDX0 >> PF_ICDF_BFE_BITS) == (SLOT0 >> PF_ICDF_BFE_BITS), "the LDS binades wrap in the bfe index");
+    static constexpr int FRONT = BASE;                                           // entries below slot 0 an index can reach
+    static constexpr int BEHIND = (1 << PF_ICDF_BFE_BITS) - BASE - NENT;         // entries past the end of the {c2, c3} array
+};
+#define PF_ICDF_BFE_FRONT (pf_icdf_bfe<>::FRONT)
+#define PF_ICDF_BFE_BEHIND (pf_icdf_bfe<>::BEHIND)
+template <int NB = PF_ICDF_NB_LDS>
+__device__ __forceinline__ uint32_t pf_icdf_adj_bfe(const double2 *lds_tab) {
+    uint32_t off = (uint32_t)__builtin_amdgcn_readfirstlane(
+        (int)((uint32_t)(uintptr_t)(pf_lds_d2)lds_tab - (uint32_t)pf_icdf_bfe<NB>::BASE * 16u));    // wave-uniform, >= 0 by the front guard
+    asm volatile("" : "+s"(off));
+    return off;
+}
+template <int NB = PF_ICDF_NB_LDS>
+__device__ __forceinline__ void pf_icdf_issue_bfe(uint32_t x, uint32_t adj, double &v, double2 &c01, double2 &c23) {
+    constexpr int NENT = NB << PF_ICDF_B;
+    v = (double)(x & 0x7FFFFFFFu);
+    const unsigned hi = (unsigned)__double2hiint(v);
+    unsigned idx = (hi >> (20 - PF_ICDF_B)) & ((1u << PF_ICDF_BFE_BITS) - 1);       // one v_bfe_u32
+    asm("" : "+v"(idx));                                            // keeps (idx << 4) + adj one v_lshl_add_u32
     const pf_lds_d2 e = (pf_lds_d2)(uintptr_t)(adj + (idx << 4));
     const pf_v2d a = e[0], b = e[NENT];
     c01 = make_double2(a.x, a.y); c23 = make_double2(b.x, b.y);
