@@ -106,7 +106,14 @@ int32_t pfmi_debug_set(const char *key, const char *value);
  * "psis", "resample") since pfmi_profile(ctx, mode).  mode 1: the host waits after every stage (each stage starts on an idle
  * GPU: its figure includes the host's launch latency); mode 2: the event pairs stay in the stream and are read by
  * pfmi_kernel_time (which waits for them) -- the pipeline runs as it does unprofiled and a stage's figure is its kernels'
- * time; mode 0: off. */
+ * time; mode 0: off.
+ * Two kinds of name are host-side counters, not stages: they are counted whatever the mode, since the ctx was created, and
+ * report *milliseconds = 0.  "qf_handover_lost": scan pieces that gave up waiting for their fit's constants.
+ * "qf:<KC>,<TGT>,<RPAD>,<NG>:<res|stream>:<cut>": scan calls that took this plan of the single-pass ELBO scan -- column padding
+ * KC (4 .. 32), target kind TGT (0 none, 1 Gaussian, 2 funnel), target rank padding RPAD (0, 8, 16), NG 16-draw groups per
+ * wave (1, 2), factor block resident in LDS or streamed in chunks, and cut "whole" (one workgroup per fit), "split" (few fits,
+ * each cut into pieces), "tail-share" (one launch; the fits of the last partial round of CUs cut into pieces that share the
+ * per-fit constants) or "tail-two" (the same tail as a second launch). */
 int32_t pfmi_timer_start(pfmi_ctx *ctx);
 int32_t pfmi_timer_stop(pfmi_ctx *ctx, double *milliseconds);
 int32_t pfmi_profile(pfmi_ctx *ctx, int32_t enable);

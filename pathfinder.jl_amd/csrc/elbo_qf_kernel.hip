@@ -24,6 +24,7 @@
 //   * per 16-row block a wave issues 4 k-steps x (2 KC/4 + RPAD/4) quarter-size MFMAs (16 cycles each) -- the same
 //     matrix work as the two-pass kernel -- plus the RNG.
 #include <type_traits>
+#include <stdio.h>
 #include <stdlib.h>
 #include "pfmi_common.h"
 #include "elbo_args.h"
@@ -797,6 +798,15 @@ static size_t qf_lds_bytes(int ch_blocks, int nchunks, int kc, int rpad) {
     return sizeof(double) * (stage + (size_t)kc * kc + qf_nconst(kc, rpad) + (size_t)rpad * rpad + 1 + 4 * PF_ICDF_LDS_ENTRIES + 2 * PF_ICDF_BFE_BEHIND);
 }
 
+// the plan of one scan call, counted per ctx for pfmi_kernel_time (include/pfmi.h): instantiation, resident / streamed factor block, and the
+// cut -- whole (a workgroup per fit, or per fit and piece), split (few fits: each cut into pieces), tail-share (the one-launch tail with
+// its publishers and dependents), tail-two (the tail as a second launch)
+static void qf_note_plan(pfmi_ctx *c, int kc, int tgt, int rpad, int ng, bool streamed, const char *cut) {
+    char nm[64];
+    snprintf(nm, sizeof nm, "qf:%d,%d,%d,%d:%s:%s", kc, tgt, rpad, ng, streamed ? "stream" : "res", cut);
+    ++c->qf_plans[nm];
+}
+
 template <int KC, int TGT, int RPAD, int NG>
 static int32_t launch_qf_ng(pfmi_ctx *c, const ElboArgs &a, int64_t nfits) {
     const int nblk = (a.d + 15) / 16;
@@ -867,11 +877,13 @@ static int32_t launch_qf_ng(pfmi_ctx *c, const ElboArgs &a, int64_t nfits) {
             unsigned *cflag = reinterpret_cast<unsigned *>(share.as<char>() + share.cap) - (tail + 1);
             hipLaunchKernelGGL(kern, dim3(1, (unsigned)((nfits - tail) + tail * (1 + ndep))), dim3(QF_THREADS), lds_bytes, c->stream, a, ch_blocks,
                                nchunks, gpw, ngroups, (int)(nfits - tail), (int)tail, ndep, share.as<double>(), cflag, ++epoch);
+            qf_note_plan(c, KC, TGT, RPAD, NG, nchunks > 1, "tail-share");
             return PFMI_OK;
         }
     }
     if (nfits - tail > 0) launch(0, nfits - tail, gpw, gx);
     if (tail > 0) launch(nfits - tail, tail, gpw_t, gx_t);
+    qf_note_plan(c, KC, TGT, RPAD, NG, nchunks > 1, tail > 0 ? "tail-two" : (split > 1 ? "split" : "whole"));
     return PFMI_OK;
 }
 

@@ -405,6 +405,12 @@ int32_t pfmi_kernel_time(pfmi_ctx *c, const char *name, double *ms, int64_t *lau
         if (launches) *launches = c->qf_lost_total;
         return PFMI_OK;
     }
+    if (strncmp(name, "qf:", 3) == 0) {                               // not a stage either: scan launches of one plan (launch_qf_ng), host-side count
+        auto pl = c->qf_plans.find(name);
+        if (ms) *ms = 0.0;
+        if (launches) *launches = (pl == c->qf_plans.end()) ? 0 : pl->second;
+        return PFMI_OK;
+    }
     auto it = c->kstats.find(name);
     if (ms) *ms = (it == c->kstats.end()) ? 0.0 : it->second.ms;
     if (launches) *launches = (it == c->kstats.end()) ? 0 : it->second.launches;

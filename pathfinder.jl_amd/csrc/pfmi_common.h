@@ -203,6 +203,7 @@ struct pfmi_ctx {
     int qf_slot = 0;        // which of the two the next scan launch uses (0 outside the streaming pipeline)
     bool qf_no_share = false; // a hand-over of the shared-constants scan timed out on this ctx: later scans take the two-launch cut (no in-kernel wait)
     int64_t qf_lost_total = 0; // pieces that ever gave up waiting (pfmi_kernel_time("qf_handover_lost") reports it as `launches`)
+    std::map<std::string, int64_t> qf_plans;   // scan launches per plan "qf:<KC>,<TGT>,<RPAD>,<NG>:<res|stream>:<cut>" (launch_qf_ng; pfmi_kernel_time)
 
     // pool / PSIS / resample state
     bool pooled = false;
