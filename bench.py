@@ -12,7 +12,12 @@ resample indices -> gather of the selected columns [-> xGMI all-reduce].
 value = ELBO draws per second of the whole job = (sum over fits of ndraws_elbo) / step time (the step time
 includes fit, PSIS and resampling, i.e. it is also the hot-path part of the multipathfinder wall-clock).
 
-Run:  python bench.py [--gpus N --steps K --warmup W]
+Run:  python bench.py [--gpus N --steps K --warmup W] [--full]
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the result line: the headline, with the per-stage
+hipEvent figures and the roofline arithmetic of the timed steps themselves.  --full adds everything that takes work of its own: the
+end-to-end loops (device L-BFGS, streamed and packed, the public API), the host- and device-closure samples, the rocprofv3 counter
+passes of roofline.traffic, the CPU baselines, the single-thread scheduler figures of --single-process and, at N > 1, the comparison of
+the sharded answer with a single-GPU recomputation; its fields are null in a plain line.
 A step is ENQUEUED as one pipeline (round 3): fit -> scan -> reduce / argmax -> winners picked on the device -> pool -> [all-gather] ->
 PSIS -> index selection -> owner gather [-> all-reduce] with ONE host synchronisation at the end (pfmi_*_enqueue,
 pfmi_pool_build_best, pfmi_comm_psis_resample); the results every step downloads: elbo / se / best_iter, k-hat, indices, draws.
@@ -309,7 +314,7 @@ def main_single_process(args):
                                           "best_iter": np.concatenate(state["best"]), "pareto_k": state["pareto_k"],
                                           "tail_length": state["tail"], "resample_indices": state["idx"], "draws": state["draws"]})
     host_line = None
-    if not args.host_traces:
+    if args.full and not args.host_traces:
         import gc
         try:
             for _ in range(2):
@@ -347,7 +352,7 @@ def main_single_process(args):
             for e in engs:
                 e.stream_cancel()
     verdict, vnote = None, "not requested"
-    if args.verify_sharding or (G > 1 and not args.no_verify_sharding):
+    if args.verify_sharding or (args.full and G > 1 and not args.no_verify_sharding):
         from pfmi.distributed import result_fingerprint, sharded_equals_single
         ref, vnote = _single_gpu_reference(pfmi, tg, x0, run_seeds, J, args.maxiters, N_e, N_r, ndraws, master, engs[0].device)
         verdict, bad = sharded_equals_single(None, result_fingerprint(state["pareto_k"], state["tail"], state["idx"], state["draws"]), ref)
@@ -364,7 +369,7 @@ def main_single_process(args):
                        "ranks_in_collective": info["world"], "rccl_version": info["rccl_version"]},
             "pareto_k": state.get("pareto_k"), "sharded_equals_single": verdict, "sharded_equals_single_note": vnote,
             "single_thread_scheduler": host_line,
-            "rccl_version": info["rccl_version"], "roofline": None, "cpu_baseline": None}
+            "rccl_version": info["rccl_version"], "roofline": None, "cpu_baseline": None, "full": args.full}
     comm.close()
     for e in engs:
         e.close()
@@ -376,6 +381,9 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, also the end-to-end and public-API loops, the closure samples, the rocprofv3 counter passes, "
+                         "the CPU baselines, the single-thread scheduler figures and (N > 1) the sharding self-check")
     ap.add_argument("--npaths", type=int, default=64)
     ap.add_argument("--dim", type=int, default=1000)
     ap.add_argument("--ndraws-elbo", type=int, default=1000)
@@ -391,11 +399,11 @@ def main():
     ap.add_argument("--single-process", action="store_true",
                     help="--gpus N driven by ONE host process (N contexts, pfmi_comm_init_all) instead of one rank per GPU")
     ap.add_argument("--minimal", action="store_true", help="timed steps only (the rocprofv3 counter passes re-run bench.py this way)")
-    ap.add_argument("--with-devcb", action="store_true", help="with --minimal: also one device-closure scan (counter passes)")
+    ap.add_argument("--with-devcb", action="store_true", help="the device-closure sample even without --full (with --minimal: one scan, for the counter passes)")
     ap.add_argument("--no-pmc", action="store_true", help="do not re-run a step under rocprofv3 --pmc for roofline.traffic")
     ap.add_argument("--verify-sharding", action="store_true",
                     help="after the timed steps rank 0 recomputes ALL paths on one GPU and every rank compares k-hat, the indices and a hash "
-                         "of the d x ndraws result with its sharded answer (default when --gpus > 1; this flag forces it at --gpus 1)")
+                         "of the d x ndraws result with its sharded answer (default with --full when --gpus > 1; this flag forces it)")
     ap.add_argument("--no-verify-sharding", action="store_true")
     ap.add_argument("--maxiters", type=int, default=1000)
     ap.add_argument("--init-scale", type=float, default=2.0)
@@ -580,7 +588,7 @@ def main():
             rccl_version = comm.info()["rccl_version"]
         except Exception:
             pass
-    if (args.verify_sharding or (world > 1 and not args.no_verify_sharding)) and not args.minimal and not args.host_traces:
+    if (args.verify_sharding or (args.full and world > 1 and not args.no_verify_sharding)) and not args.minimal and not args.host_traces:
         from pfmi.distributed import result_fingerprint, sharded_equals_single
         mine = result_fingerprint(state["pareto_k"], state["tail"], state["idx"], state["draws"])    # (draws: rank 0 only, the result lives there)
         ref = None
@@ -607,7 +615,7 @@ def main():
     # ---- metric (ii): end-to-end wall-clock incl. trajectory generation (x0 on the host -> resampled draws on the host)
     wall_e2e = wall_e2e_packed = None
     streamed_equal, stream_note = None, None
-    if not args.host_traces and not args.minimal:
+    if args.full and not args.host_traces and not args.minimal:
         barrier()
         t0 = time.perf_counter()
         for _ in range(args.steps):
@@ -650,7 +658,7 @@ def main():
     # ---- the same job through the public host API (pfmi.multipathfinder: x0 sampling, device L-BFGS, fit, ELBO, pool, PSIS,
     #      resample, result objects), single GPU only
     api_wall = None
-    if G == 1 and not use_dist and not args.host_traces and not args.minimal:
+    if args.full and G == 1 and not use_dist and not args.host_traces and not args.minimal:
         ts = []
         for rep in range(7):                                            # 2 untimed calls (first-use allocations), median of 5
             t0 = time.perf_counter()
@@ -665,7 +673,7 @@ def main():
     #      to cross PCIe, so this is a separate, much lower line.  Bounded sample: the first 2 paths of this run, a vectorised
     #      NumPy closure (-|x|^2 / 2); the draws of block i + 1 are generated / downloaded while the host evaluates block i.
     callback_line = None
-    if G == 1 and not use_dist and not args.host_traces and not args.no_cpu_baseline and not args.minimal:
+    if args.full and G == 1 and not use_dist and not args.host_traces and not args.no_cpu_baseline and not args.minimal:
         try:
             import cpu_lapack_baseline as cl
             from helpers import demo_host_target
@@ -716,7 +724,7 @@ def main():
     #      materialised in HBM (8 d bytes written per draw) and read there by the user's kernel (8 d bytes read): the path on which
     #      SURVEY 8(d)'s 16 d bytes per draw PHYSICALLY move, so its HBM fraction is a real utilisation.  Bounded sample: 8 paths.
     devcb_line = None
-    if G == 1 and not use_dist and not args.host_traces and (not args.minimal or args.with_devcb):
+    if G == 1 and not use_dist and not args.host_traces and ((args.full and not args.minimal) or args.with_devcb):
         try:
             Kd = min(8, Kl)
             trs = [eng.get_trace(k, logp=False) for k in range(Kd)]
@@ -833,8 +841,8 @@ def main():
                      "model": f"per wave and 16x32 block: {n_mfma} MFMA4 x 7.44 ns + {n_phx} Philox rounds x 10.5 ns + {n_valu} VALU x 2.0 ns, "
                               "2 waves per SIMD, no MFMA/VALU co-issue (profiles/r02_coissue_microbench.txt, profiles/r03_*)"}
         traffic, traffic_meta = None, None
-        if not args.no_pmc and not args.minimal and G == 1 and not use_dist:
-            pmc, why = _pmc_traffic([a for a in _strip_option(sys.argv[1:], "--dump-outputs") if a not in ("--no-cpu-baseline",)],
+        if args.full and not args.no_pmc and not args.minimal and G == 1 and not use_dist:
+            pmc, why = _pmc_traffic([a for a in _strip_option(sys.argv[1:], "--dump-outputs") if a not in ("--no-cpu-baseline", "--full")],
                                     {"scan": "%pf_elbo_qf_kernel%", "writer": "%pf_elbo_xw_kernel%", "reader": "%pfx_%"})
             if pmc is not None and "scan" in pmc:
                 traffic, traffic_meta = pmc["scan"]["traffic_bytes_per_launch"], pmc["scan"]
@@ -869,7 +877,7 @@ def main():
     # `cores` = the cores this process can really use (affinity mask, capped by a cgroup CPU quota), NOT os.cpu_count(); the scaling of
     # the port from 1 thread to all cores is reported so that a reader can see where it stops.
     cpu = None
-    if rank == 0 and G == 1 and not args.no_cpu_baseline:          # contract: rank 0 at N = 1 only
+    if args.full and rank == 0 and G == 1 and not args.no_cpu_baseline:          # contract: rank 0 at N = 1 only
         try:
             from helpers import oracle_target
             from oracle import pf_oracle as po
@@ -982,6 +990,7 @@ def main():
             "device_callback_target": devcb_line,
             "roofline": roofline,
             "cpu_baseline": cpu,
+            "full": args.full,
         }
         # ---- self-checks of the line are FATAL (a NaN parity figure went out unnoticed): the line is still printed, the
         #      process then exits non-zero

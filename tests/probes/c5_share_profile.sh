@@ -1,5 +1,5 @@
 R=$GRAFT_REPO_ROOT; cd /tmp && export TMPDIR=/tmp
-B="python $R/bench.py --npaths 32 --dim 10000 --target funnel --history 10 --ndraws-elbo 2000 --ndraws 2000 --init-scale 10 --maxiters 1000 --steps 2 --warmup 1 --no-pmc --no-cpu-baseline"
+B="python $R/bench.py --npaths 32 --dim 10000 --target funnel --history 10 --ndraws-elbo 2000 --ndraws 2000 --init-scale 10 --maxiters 1000 --steps 2 --warmup 1 --full --no-pmc --no-cpu-baseline"
 $B > $R/gpurun_out/${TAG:-r05}_c5_share_bench_line.json 2> $R/gpurun_out/${TAG:-r05}_c5.err
 rm -rf $R/gpurun_out/prof_c5
 rocprofv3 --kernel-trace --stats -d $R/gpurun_out/prof_c5 -o s -- $B > $R/gpurun_out/${TAG:-r05}_c5_share_bench_line_under_rocprof.json 2> $R/gpurun_out/${TAG:-r05}_c5_rocprof.err

@@ -2,9 +2,9 @@
 # single-thread scheduler through the RCCL stand-in, the large-d fit kernels side by side with their HBM traffic, writer variants)
 TAG=$1; R=$GRAFT_REPO_ROOT; O=$R/gpurun_out; cd $R
 bash tests/probes/final_round.sh $TAG
-python bench.py --npaths 8 --dim 100 --target diag --no-pmc --cpu-seconds 8 > $O/${TAG}_c2_bench_line.json 2>> $O/${TAG}_bench.err
-env PFMI_RCCL_LIB=$R/tests/rccl_standin/librccl_standin.so PFMI_COMM_ALLOW_SHARED_GPU=1 PFMI_DEBUG_HOOKS=1 timeout 600 python bench.py --gpus 8 --single-process --steps 10 --warmup 2 --no-pmc --no-cpu-baseline > $O/${TAG}_single_process_8_standin_bench_line.json 2>> $O/${TAG}_bench.err
-env PFMI_DEBUG_HOOKS=1 timeout 600 python bench.py --gpus 1 --single-process --npaths 8 --steps 20 --warmup 2 --no-pmc --no-cpu-baseline > $O/${TAG}_single_process_1_bench_line.json 2>> $O/${TAG}_bench.err
+python bench.py --npaths 8 --dim 100 --target diag --full --no-pmc --cpu-seconds 8 > $O/${TAG}_c2_bench_line.json 2>> $O/${TAG}_bench.err
+env PFMI_RCCL_LIB=$R/tests/rccl_standin/librccl_standin.so PFMI_COMM_ALLOW_SHARED_GPU=1 PFMI_DEBUG_HOOKS=1 timeout 600 python bench.py --gpus 8 --single-process --steps 10 --warmup 2 --full --no-pmc --no-cpu-baseline > $O/${TAG}_single_process_8_standin_bench_line.json 2>> $O/${TAG}_bench.err
+env PFMI_DEBUG_HOOKS=1 timeout 600 python bench.py --gpus 1 --single-process --npaths 8 --steps 20 --warmup 2 --full --no-pmc --no-cpu-baseline > $O/${TAG}_single_process_1_bench_line.json 2>> $O/${TAG}_bench.err
 timeout 600 python tests/probes/fit_tsqr_probe.py small c5 j16 > $O/${TAG}_fit_kernels.txt 2>&1
 ( cd /tmp && export TMPDIR=/tmp
   for c in FETCH_SIZE WRITE_SIZE; do rm -rf $O/ts_$c; rocprofv3 --kernel-trace --pmc $c -d $O/ts_$c -o p -- python $R/tests/probes/fit_tsqr_probe.py c5 > /dev/null 2>&1; done )

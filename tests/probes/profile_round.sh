@@ -1,7 +1,7 @@
 # usage (on the GPU box): bash tests/probes/profile_round.sh <tag>
 # kernel-trace stats, HBM traffic (two separate --pmc passes) and SQ counters of `bench.py`; results under gpurun_out/<tag>_*
 TAG=$1; R=$GRAFT_REPO_ROOT; cd /tmp && export TMPDIR=/tmp
-B="python $R/bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-pmc"
+B="python $R/bench.py --steps 5 --warmup 1 --full --no-cpu-baseline --no-pmc"
 B1="python $R/bench.py --steps 1 --warmup 0 --minimal --with-devcb --no-cpu-baseline --no-pmc"
 rm -rf $R/gpurun_out/prof_stats $R/gpurun_out/prof_fetch $R/gpurun_out/prof_write
 rocprofv3 --kernel-trace --stats -d $R/gpurun_out/prof_stats -o s -- $B > $R/gpurun_out/${TAG}_stats.log 2>&1

@@ -33,6 +33,12 @@ def test_gpus_2_self_launches_two_ranks():
     assert line["n_gpus"] == 2 and line["world_size"] == 2 and line["ranks_in_collective"] == 2
 
 
+def test_full_reaches_every_rank():
+    r = _run(["--gpus", "2", "--steps", "1", "--warmup", "0", "--full"], {"PFMI_BENCH_LAUNCH_ONLY": "1"})
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert _json_line(r.stdout)["ranks_in_collective"] == 2
+
+
 def test_world_size_must_match_gpus():
     r = _run(["--gpus", "2"], {"PFMI_BENCH_LAUNCH_ONLY": "1", "WORLD_SIZE": "1", "RANK": "0"})
     assert r.returncode != 0 and "WORLD_SIZE=1" in r.stderr

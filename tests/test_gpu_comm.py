@@ -208,6 +208,38 @@ def test_bench_dump_outputs_are_the_results_of_the_last_timed_step(tmp_path):
     assert len(a["elbo"]) == len(a["elbo_se"]) == len(fit) > 8 and fit[0] >= 1 and np.all(np.diff(fit) > 0)
 
 
+def test_bench_plain_run_is_the_headline_and_full_adds_the_rest(tmp_path):
+    """A plain bench.py run times the steps and prints the headline; the end-to-end loops, the public-API call, the closure samples and
+    the CPU baselines come with --full alone.  Both runs time the same steps on the same inputs: their dumped outputs are the same bits."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    lines, dumps = {}, {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--no-pmc", "--cpu-seconds", "1"])):
+        out = tmp_path / mode
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--npaths", "8",
+                            "--dim", "100", "--target", "diag", "--ndraws", "300", "--dump-outputs", str(out)] + extra,
+                           capture_output=True, text=True, env=env, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines[mode] = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        dumps[mode] = {f[:-4]: np.load(out / f) for f in os.listdir(out)}
+    plain, full = lines["plain"], lines["full"]
+    for line in (plain, full):
+        assert line["value"] > 0 and line["ms_per_step"] > 0 and line["unit"] == "ELBO draws/s" and line["dtype"] == "f64"
+        assert line["higher_is_better"] is True and line["self_checks"]["ok"] and line["roofline"]["frac"] > 0
+    assert plain["full"] is False and full["full"] is True
+    for k in ("multipathfinder_wall_ms_incl_device_lbfgs", "multipathfinder_api_wall_ms", "streamed_equals_packed", "callback_target",
+              "device_callback_target", "cpu_baseline"):
+        assert plain[k] is None, k
+    assert full["streamed_equals_packed"] is True and full["multipathfinder_api_wall_ms"] > 0
+    assert "error" not in full["callback_target"] and full["device_callback_target"]["max_rel_elbo_diff_vs_builtin_target"] <= 1e-10
+    assert full["cpu_baseline"]["value"] > 0
+    assert plain["pareto_k"] == full["pareto_k"] and sorted(dumps["plain"]) == sorted(dumps["full"])
+    for k, a in dumps["plain"].items():
+        assert np.array_equal(a, dumps["full"][k]), k
+
+
 # ---- ADVICE r3 -----------------------------------------------------------------------------------------------------------------
 def test_context_destroyed_before_its_communicator(pfmi_mod):
     """A host with unordered finalisers (Julia's GC at exit) may destroy a pfmi_ctx before the pfmi_comm that borrows it:

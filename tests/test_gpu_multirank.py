@@ -81,7 +81,7 @@ def test_bench_single_process_drives_several_contexts():
     out = {}
     for G, K in ((1, 8), (2, 8), (3, 8)):                       # (3 contexts x 8 paths: blocks 3 3 2 -- unequal shards through the bench, too)
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(G), "--single-process", "--steps", "2", "--warmup", "1",
-                            "--npaths", str(K), "--dim", "200", "--ndraws-elbo", "256", "--ndraws", "256"], env=env, capture_output=True,
+                            "--npaths", str(K), "--dim", "200", "--ndraws-elbo", "256", "--ndraws", "256", "--full"], env=env, capture_output=True,
                            text=True, timeout=500)
         assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
         out[G] = json.loads(r.stdout.strip().splitlines()[-1])
@@ -94,6 +94,6 @@ def test_bench_single_process_drives_several_contexts():
     assert out[2]["config"]["rccl_version"] == 99999 and out[1]["config"]["rccl_version"] == 0
     assert out[1]["pareto_k"] == out[2]["pareto_k"] and out[1]["config"]["elbo_draws_per_step"] == out[2]["config"]["elbo_draws_per_step"]
     # round 4: the sharded run verifies ITSELF -- all paths recomputed on one context, k-hat / tail length / indices / a hash of the
-    # d x ndraws result compared with the sharded answer (default for G > 1)
+    # d x ndraws result compared with the sharded answer (default for G > 1 with --full)
     assert out[2]["sharded_equals_single"] is True, out[2].get("sharded_equals_single_note")
     assert out[1]["sharded_equals_single"] is None and out[2]["rccl_version"] == 99999
