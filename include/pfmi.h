@@ -288,6 +288,18 @@ int32_t pfmi_draws(pfmi_ctx *ctx, int64_t point, uint64_t seed, int64_t n0, int6
  * (src/resample.jl:85-89 -> src/woodbury.jl:378-382,158-165) */
 int32_t pfmi_logpdf(pfmi_ctx *ctx, int64_t point, int64_t N, const double *X, double *out);
 
+/* Distributions.logpdf(MixtureModel(components), X) without the log K, and componentwise_logpdf, for the uniform mixture of the
+ * fits points[0..K-1] (repeats allowed) of this ctx:  comp[n + N k] = logpdf(fit points[k], X[:, n]) exactly as pfmi_logpdf defines
+ * it (NaN for a fit whose status is not PFMI_FIT_OK), lse[n] = log sum_k exp(comp[n + N k]) in component order (NaN if any
+ * component is NaN, -inf if all are -inf).  X[d*N] column-major; comp may be NULL (not wanted).  The host entry uploads X once for
+ * all K components.  Not fitted: PFMI_ERR_STATE; K < 1, N < 1, a point outside [0, P) or NULL X / lse: PFMI_ERR_ARG. */
+int32_t pfmi_mixture_logpdf(pfmi_ctx *ctx, int32_t K, const int64_t *points, int64_t N, const double *X, double *lse,
+                            double *comp);
+/* the same with X / lse / comp in device memory of the ctx's GPU, enqueued on the ctx stream: the caller orders the writes of X
+ * before the call and calls pfmi_sync before reading lse / comp (points is a host array, read during the call). */
+int32_t pfmi_mixture_logpdf_dev(pfmi_ctx *ctx, int32_t K, const int64_t *points, int64_t N, const void *X_dev, void *lse_dev,
+                                void *comp_dev);
+
 /* ---- remaining WoodburyPDMat / PDMats operator surface of a fitted covariance -------------- */
 /* What the HMC integrations call on a fitted metric (ext/PathfinderAdvancedHMCExt.jl:17-23,
  * ext/PathfinderDynamicHMCExt.jl:7-15).  X is d x N column-major; out is d x N, or N values for the quadratic forms. */

@@ -18,6 +18,7 @@
 //       (src/resample.jl:85-89 -> invquad, src/woodbury.jl:378-382,158-165).
 #include "pfmi_common.h"
 #include "elbo_args.h"
+#include "logpdf_lane.h"
 #include <stdlib.h>
 
 #define ELBO_THREADS 256
@@ -307,8 +308,8 @@ __global__ void pf_pool_pick_kernel(int K, const int64_t *__restrict__ off, cons
 }
 
 // ---------------------------------------------------------------------------------------------------
-// logpdf(MvNormal(mu, W), x) = -(d log2pi + logdet)/2 - |L \ (x - mu)|^2 / 2, one lane per column.
-// ldiv!(L): z = U'^{-1}(x - mu); z <- Q'z = z - Vh T'(Vh' z); z[1:k] <- V'^{-1} z[1:k]  (src/woodbury.jl:158-165)
+// logpdf(MvNormal(mu, W), x), one lane per column: the algebra is pf_logpdf_lane (logpdf_lane.h), shared with the mixture
+// kernels' general path so that both give the same bits.
 template <int KPAD>
 __global__ __launch_bounds__(ELBO_THREADS) void pf_logpdf_kernel(int d, int p, int64_t N, const double *__restrict__ Xall,
                                                                 const double *__restrict__ vh, const double *__restrict__ tmat,
@@ -317,54 +318,7 @@ __global__ __launch_bounds__(ELBO_THREADS) void pf_logpdf_kernel(int d, int p, i
                                                                 const int32_t *__restrict__ status, double *__restrict__ out) {
     const int64_t n = (int64_t)blockIdx.x * ELBO_THREADS + threadIdx.x;
     if (n >= N) return;
-    if (status[p] != PFMI_FIT_OK) { out[n] = NAN; return; }
-    const double *Vh = vh + (size_t)p * d * KPAD, *T = tmat + (size_t)p * KPAD * KPAD, *Vc = vchol + (size_t)p * KPAD * KPAD;
-    const double *sqa = sqrt_alpha + (size_t)p * d, *mu = mu_all + (size_t)p * d;
-    const double *X = Xall + (size_t)n * d;
-    double w[KPAD], tv[KPAD], zh[KPAD];
-#pragma unroll
-    for (int j = 0; j < KPAD; ++j) w[j] = 0.0;
-    for (int i = 0; i < d; ++i) {
-        const double e = (X[i] - mu[i]) / sqa[i];
-        const double *row = Vh + (size_t)i * KPAD;
-#pragma unroll
-        for (int j = 0; j < KPAD; ++j) w[j] += row[j] * e;
-    }
-#pragma unroll
-    for (int a = 0; a < KPAD; ++a) {   // tv = T' w
-        double s = 0.0;
-#pragma unroll
-        for (int b = 0; b <= a; ++b) s += T[b * KPAD + a] * w[b];
-        tv[a] = s;
-    }
-    double ss = 0.0;
-#pragma unroll
-    for (int i = 0; i < KPAD; ++i) {
-        zh[i] = 0.0;
-        if (i < d) {
-            const double *row = Vh + (size_t)i * KPAD;
-            double v = (X[i] - mu[i]) / sqa[i];
-#pragma unroll
-            for (int j = 0; j < KPAD; ++j) v -= row[j] * tv[j];
-            zh[i] = v;
-        }
-    }
-    for (int i = KPAD; i < d; ++i) {
-        const double *row = Vh + (size_t)i * KPAD;
-        double v = (X[i] - mu[i]) / sqa[i];
-#pragma unroll
-        for (int j = 0; j < KPAD; ++j) v -= row[j] * tv[j];
-        ss += v * v;
-    }
-#pragma unroll
-    for (int a = 0; a < KPAD; ++a) {   // forward substitution V' y = zh (identity padded)
-        double v = zh[a];
-#pragma unroll
-        for (int b = 0; b < a; ++b) v -= Vc[b * KPAD + a] * zh[b];
-        zh[a] = v / Vc[a * KPAD + a];
-        ss += zh[a] * zh[a];
-    }
-    out[n] = -((double)d * PF_LOG2PI + logdet[p]) / 2.0 - ss / 2.0;
+    out[n] = pf_logpdf_lane<KPAD>(d, p, Xall + (size_t)n * d, vh, tmat, vchol, sqrt_alpha, mu_all, logdet, status);
 }
 
 // ---------------------------------------------------------------------------------------------------

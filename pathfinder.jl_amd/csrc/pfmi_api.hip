@@ -337,7 +337,7 @@ int32_t pfmi_destroy(pfmi_ctx *c) {
     DevBuf *bufs[] = {&c->theta, &c->grad, &c->d_off, &c->d_path_of, &c->target.mean, &c->target.a, &c->target.wd,
                       &c->target.g, &c->target.wd16, &c->alpha_all, &c->hist_len, &c->hist_src, &c->hist_acc, &c->n_rej, &c->vh, &c->tmat, &c->vchol,
                       &c->rq, &c->dmat, &c->sqrt_alpha, &c->mu, &c->logdet, &c->status, &c->seeds, &c->logp, &c->logq,
-                      &c->elbo, &c->se, &c->best_iter, &c->fit_list, &c->ubuf, &c->xbuf, &c->scratch, &c->qf_share_s[0], &c->qf_share_s[1], &c->fit_scratch, &c->pool,
+                      &c->elbo, &c->se, &c->best_iter, &c->fit_list, &c->ubuf, &c->xbuf, &c->scratch, &c->mix, &c->qf_share_s[0], &c->qf_share_s[1], &c->fit_scratch, &c->pool,
                       &c->pool_lr, &c->pool_lp, &c->pool_lq, &c->pool_points, &c->pool_seeds, &c->lw, &c->w,
                       &c->psis_out, &c->psis_aux, &c->tailbuf, &c->cdf, &c->idx, &c->gbuf, &c->trace_lp, &c->st_theta, &c->st_grad,
                       &c->st_lp, &c->st_npts, &c->lb_hs, &c->lb_hy, &c->lb_x0, &c->sortk, &c->sorti,
@@ -1660,6 +1660,57 @@ int32_t pfmi_logpdf(pfmi_ctx *c, int64_t p, int64_t N, const double *X, double *
     PF_TRY(pf_launch_logpdf(c, p, N, c->xbuf.as<double>(), c->scratch.as<double>()));
     PF_TRY(d2h(c, out, c->scratch.p, sizeof(double) * N));
     return PFMI_OK;
+}
+
+// ---- uniform mixture of fits (mixture_kernels.hip) ----------------------------------------------------------
+// points validated and uploaded to c->mix (int32), behind them room for comp [K][N] (when the caller keeps none) and lse [N]
+static int32_t mixture_stage(pfmi_ctx *c, int32_t K, const int64_t *points, int64_t N, bool own_comp, bool own_lse,
+                             int32_t **d_pts, double **d_comp, double **d_lse) {
+    PF_CHECK(c->fitted, PFMI_ERR_STATE, "mixture_logpdf: call pfmi_fit_batch first");
+    PF_CHECK(K >= 1 && N >= 1 && points, PFMI_ERR_ARG, "mixture_logpdf: bad arguments (K=%d, N=%lld)", (int)K, (long long)N);
+    std::vector<int32_t> pts(K);
+    for (int32_t k = 0; k < K; ++k) {
+        PF_CHECK(points[k] >= 0 && points[k] < c->P, PFMI_ERR_ARG, "mixture_logpdf: point %lld out of range [0, %lld)",
+                 (long long)points[k], (long long)c->P);
+        pts[k] = (int32_t)points[k];
+    }
+    const size_t pbytes = ((sizeof(int32_t) * (size_t)K + 7) / 8) * 8;
+    const size_t cbytes = own_comp ? sizeof(double) * (size_t)K * N : 0, lbytes = own_lse ? sizeof(double) * (size_t)N : 0;
+    PF_TRY(c->mix.ensure(pbytes + cbytes + lbytes));
+    char *base = c->mix.as<char>();
+    PF_TRY(h2d(c, base, pts.data(), sizeof(int32_t) * (size_t)K));
+    *d_pts = reinterpret_cast<int32_t *>(base);
+    *d_comp = own_comp ? reinterpret_cast<double *>(base + pbytes) : nullptr;
+    *d_lse = own_lse ? reinterpret_cast<double *>(base + pbytes + cbytes) : nullptr;
+    return PFMI_OK;
+}
+
+int32_t pfmi_mixture_logpdf(pfmi_ctx *c, int32_t K, const int64_t *points, int64_t N, const double *X, double *lse, double *comp) {
+    PF_CTX_MUT(c);
+    PF_CHECK(c->fitted, PFMI_ERR_STATE, "mixture_logpdf: call pfmi_fit_batch first");
+    PF_CHECK(X && lse, PFMI_ERR_ARG, "mixture_logpdf: null X or lse");
+    int32_t *d_pts;
+    double *d_comp, *d_lse;
+    PF_TRY(mixture_stage(c, K, points, N, true, true, &d_pts, &d_comp, &d_lse));
+    PF_TRY(c->xbuf.ensure(sizeof(double) * (size_t)c->d * N));
+    PF_TRY(h2d(c, c->xbuf.p, X, sizeof(double) * (size_t)c->d * N));       // once for all K components
+    PF_TRY(pf_launch_mixture_logpdf(c, K, d_pts, N, c->xbuf.as<double>(), d_lse, d_comp));
+    if (comp) PF_TRY(d2h_async(c, comp, d_comp, sizeof(double) * (size_t)K * N));
+    PF_TRY(d2h(c, lse, d_lse, sizeof(double) * N));
+    return PFMI_OK;
+}
+
+int32_t pfmi_mixture_logpdf_dev(pfmi_ctx *c, int32_t K, const int64_t *points, int64_t N, const void *X_dev, void *lse_dev,
+                                void *comp_dev) {
+    PF_CTX_MUT(c);
+    PF_CHECK(c->fitted, PFMI_ERR_STATE, "mixture_logpdf: call pfmi_fit_batch first");
+    PF_CHECK(X_dev && lse_dev, PFMI_ERR_ARG, "mixture_logpdf: null X or lse");
+    int32_t *d_pts;
+    double *d_comp, *d_lse;
+    PF_TRY(mixture_stage(c, K, points, N, comp_dev == nullptr, false, &d_pts, &d_comp, &d_lse));
+    if (comp_dev) d_comp = reinterpret_cast<double *>(comp_dev);
+    return pf_launch_mixture_logpdf(c, K, d_pts, N, reinterpret_cast<const double *>(X_dev), reinterpret_cast<double *>(lse_dev),
+                                    d_comp);
 }
 
 // ---- remaining Woodbury operator surface ------------------------------------------------------------------

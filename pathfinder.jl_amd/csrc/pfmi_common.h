@@ -197,6 +197,7 @@ struct pfmi_ctx {
     DevBuf ubuf;        // parity-mode normals
     DevBuf xbuf;        // scratch draws (callback path / pfmi_draws)
     DevBuf scratch;     // misc
+    DevBuf mix;         // pfmi_mixture_logpdf: int32 points [K] (padded to 8 bytes), comp [K][N] when not the caller's, lse [N] (host entry)
     DevBuf qf_share_s[2];   // scan: per-fit constants handed from a tail fit's first piece to its other pieces, + one flag per tail fit
     uint32_t qf_epoch_s[2] = {0, 0};   // launch counter of the shared-constants scan: a flag equal to it means "published in THIS launch"
                                        // (one hand-over buffer + counter per scan stream: launches on different streams overlap)
@@ -273,6 +274,8 @@ int32_t pf_launch_elbo_draws(pfmi_ctx *c, const int32_t *d_points, const uint64_
                              int64_t log_stride, bool with_target, bool by_point);
 int32_t pf_launch_elbo_reduce(pfmi_ctx *c);
 int32_t pf_launch_logpdf(pfmi_ctx *c, int64_t point, int64_t N, const double *d_x, double *d_out);
+int32_t pf_launch_mixture_logpdf(pfmi_ctx *c, int K, const int32_t *d_points, int64_t N, const double *d_x, double *d_lse,
+                                 double *d_comp);
 int32_t pf_launch_psis(pfmi_ctx *c, const double *d_lr, int64_t S);
 // Test / tuning hooks (kernel selection, the RCCL stand-in, ...): a value set with pfmi_debug_set(), or -- ONLY when the process was
 // started with PFMI_DEBUG_HOOKS=1 -- the environment variable of that name.  A production process therefore never has its numerics or

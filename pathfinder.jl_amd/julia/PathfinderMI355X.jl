@@ -785,6 +785,68 @@ function resample(result::Pathfinder.MultiPathfinderResult, ndraws::Int; rng::Ra
                                             result.fit_distribution, draws_, ids, result.fit_distribution, draws_, runs, psis_out)
 end
 
+# ---- the mixture density of fit_distribution on the device (pfmi_mixture_logpdf) ------------------------------------------------------
+# `result.fit_distribution` stays the host `Distributions.MixtureModel`; these two evaluate the same mixture without materialising its
+# components: each engine evaluates the fits of its own block of runs in one call (X uploaded once), the per-engine log-sum-exps are
+# combined with logaddexp in engine order and normalised by the number of components.
+
+"(batch, run indices, 0-based fit points) of every engine, engines in order of first appearance (the contiguous blocks)"
+function _mixture_blocks(result::Pathfinder.MultiPathfinderResult)
+    groups = Tuple{Batch,Vector{Int},Vector{Int64}}[]
+    for (k, r) in enumerate(result.pathfinder_results)
+        b = r.fit_distributions.b
+        _live(b.eng, b.gen)
+        p = Int64(b.offsets[r.fit_distributions.k] + r.fit_iteration)           # fit_distributions[fit_iteration + 1]
+        i = findfirst(g -> g[1].eng === b.eng, groups)
+        if i === nothing
+            push!(groups, (b, [k], [p]))
+        else
+            push!(groups[i][2], k); push!(groups[i][3], p)
+        end
+    end
+    return groups
+end
+
+function _mixture_call(b::Batch, pts::Vector{Int64}, X::AbstractMatrix{<:Real}, componentwise::Bool)
+    size(X, 1) == b.dim || throw(DimensionMismatch("X has $(size(X, 1)) rows, the fits dimension $(b.dim)"))
+    Xc = Matrix{Float64}(X); N = size(Xc, 2); K = length(pts)
+    lse = Vector{Float64}(undef, N)
+    comp = componentwise ? Matrix{Float64}(undef, N, K) : Matrix{Float64}(undef, 0, 0)
+    check(ccall((:pfmi_mixture_logpdf, libpfmi), Int32, (Ptr{Cvoid}, Int32, Ptr{Int64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                b.eng.ptr, K, pts, N, Xc, lse, componentwise ? pointer(comp) : Ptr{Float64}(C_NULL)))
+    return lse, comp
+end
+
+_logaddexp(a::Float64, b::Float64) = (a == b == -Inf) ? -Inf : max(a, b) + log1p(exp(-abs(a - b)))
+
+"""
+    mixture_logpdf(result::Pathfinder.MultiPathfinderResult, X::AbstractMatrix) -> Vector{Float64}
+
+`Distributions.logpdf(result.fit_distribution, X)` for the columns of X (dim x N), computed on the device.
+"""
+function mixture_logpdf(result::Pathfinder.MultiPathfinderResult, X::AbstractMatrix{<:Real})
+    lse = nothing
+    for (b, _, pts) in _mixture_blocks(result)
+        l, _ = _mixture_call(b, pts, X, false)
+        lse = lse === nothing ? l : _logaddexp.(lse, l)
+    end
+    return lse .- log(length(result.pathfinder_results))
+end
+
+"""
+    componentwise_logpdf(result::Pathfinder.MultiPathfinderResult, X::AbstractMatrix) -> Matrix{Float64}
+
+`Distributions.componentwise_logpdf(result.fit_distribution, X)`: N x K, column k the log density of run k's fit.
+"""
+function componentwise_logpdf(result::Pathfinder.MultiPathfinderResult, X::AbstractMatrix{<:Real})
+    out = Matrix{Float64}(undef, size(X, 2), length(result.pathfinder_results))
+    for (b, ks, pts) in _mixture_blocks(result)
+        _, c = _mixture_call(b, pts, X, true)
+        out[:, ks] = c
+    end
+    return out
+end
+
 # ---- multi-GPU collectives (the `Comm` type itself is defined next to `Engine`) ---------------------------------------------------------
 """
     psis_resample(c, dim, ndraws; importance, replace, seed) -> (pareto_shape, tail_length, idx0, draws)

@@ -4,7 +4,7 @@ The product path has NO CPU fallback: importing this package is cheap, but creat
 requires the built HIP library and a visible MI355X, and raises otherwise.
 """
 from ._lib import PfmiError, build, lib  # noqa: F401
-from .api import (DEFAULT_HISTORY_LENGTH, DEFAULT_NDRAWS_ELBO, ELBOEstimate, MultiPathfinderResult,  # noqa: F401
+from .api import (DEFAULT_HISTORY_LENGTH, DEFAULT_NDRAWS_ELBO, ELBOEstimate, MixtureModel, MultiPathfinderResult,  # noqa: F401
                   MvNormal, PathfinderResult, PosDefException, PSISResult, UniformSampler, WoodburyPDMat,
                   fit_mvnormals, maximize_elbo, multipathfinder, pathfinder, resample)
 from .core import Comm, Engine, StaleHandleError  # noqa: F401

@@ -190,6 +190,88 @@ class MvNormal:
         return self.engine.draws(self.point, seed, n, n0)[0]
 
 
+class MixtureModel(list):
+    """Distributions.MixtureModel of the K runs' fits with uniform prior (src/multipath.jl:215-216).  It IS the list of the MvNormal
+    components, so every use of fit_distribution as a list stays valid.  Densities run on the device: each engine evaluates its
+    own components in one call (Engine.mixture_logpdf, include/pfmi.h pfmi_mixture_logpdf) and the per-engine sums are combined
+    with logaddexp in engine order.  A component whose engine has been refitted raises StaleHandleError."""
+
+    @property
+    def ncomponents(self): return len(self)
+
+    @property
+    def components(self): return list(self)
+
+    @property
+    def probs(self): return np.full(len(self), 1.0 / len(self))
+
+    def _live(self):
+        if len(self) == 0:
+            raise ValueError("MixtureModel without components")
+        for c in self:
+            c._live()
+
+    def _engine_groups(self):
+        """[(engine, [component indices])], engines in order of first appearance: multipathfinder's contiguous engine blocks"""
+        groups = []
+        for k, c in enumerate(self):
+            for eng, ks in groups:
+                if eng is c.engine:
+                    ks.append(k)
+                    break
+            else:
+                groups.append((c.engine, [k]))
+        return groups
+
+    def _lse(self, X, componentwise):
+        self._live()
+        X = np.asarray(X, dtype=np.float64)
+        vec = X.ndim == 1
+        X2 = np.asfortranarray(X.reshape(X.shape[0], -1, order="F"))
+        lse, comp = None, (np.empty((X2.shape[1], len(self)), order="F") if componentwise else None)
+        for eng, ks in self._engine_groups():
+            r = eng.mixture_logpdf([self[k].point for k in ks], X2, componentwise=componentwise)
+            part = r[0] if componentwise else r
+            if componentwise:
+                comp[:, ks] = r[1]
+            lse = part if lse is None else np.logaddexp(lse, part)
+        return lse, comp, vec
+
+    def mean(self):
+        self._live()
+        return np.mean(np.stack([np.asarray(c.mu) for c in self]), axis=0)
+
+    def logpdf(self, X):
+        """log((1/K) sum_k pdf_k(x)) of each column of X (d, N); a vector x gives a number"""
+        lse, _, vec = self._lse(X, False)
+        out = lse - np.log(len(self))
+        return float(out[0]) if vec else out
+
+    def pdf(self, X):
+        return np.exp(self.logpdf(X))
+
+    def componentwise_logpdf(self, X):
+        """(N, K): column k is logpdf(components[k], X) (Distributions.componentwise_logpdf); a vector x gives (K,)"""
+        _, comp, vec = self._lse(X, True)
+        return comp[0] if vec else comp
+
+    def rand(self, rng, n):
+        """(X (d, n), component_ids): ids = min(floor(K u), K - 1) + 1 for u = rng.rand(n) (1-based like the reference's
+        draw_component_ids), then K draw seeds rng.rand_u64(K); the columns with id k + 1 are, in order, the draws of component
+        k from its seed (the pool's draw kernel, Engine.draws)."""
+        self._live()
+        K = len(self)
+        u = rng.rand(n)
+        ids = np.minimum(np.floor(K * u).astype(np.int64), K - 1) + 1
+        seeds = rng.rand_u64(K)
+        X = np.empty((self[0].engine.d, n), order="F")
+        for k, c in enumerate(self):
+            cols = np.flatnonzero(ids == k + 1)
+            if len(cols):
+                X[:, cols] = c.engine.draws(c.point, int(seeds[k]), len(cols))[0]
+        return X, ids
+
+
 @dataclass
 class ELBOEstimate:                 # src/elbo.jl:22-29
     value: float
@@ -272,7 +354,7 @@ class MultiPathfinderResult:        # src/multipath.jl:31-44
     input: Any
     rng: Any
     logp: Any
-    fit_distribution: List[MvNormal]        # components of the uniform mixture (src/multipath.jl:215-216)
+    fit_distribution: List[MvNormal]        # MixtureModel: the list of the uniform mixture's components (src/multipath.jl:215-216)
     draws: np.ndarray
     draw_component_ids: np.ndarray          # 1-based like the reference
     pathfinder_results: List[PathfinderResult]
@@ -820,7 +902,7 @@ def multipathfinder(target, ndraws, *, init=None, nruns=-1, ndraws_elbo=DEFAULT_
         psis_result = PSISResult(w, lw, pooled["psis"]["pareto_shape"], pooled["psis"]["tail_length"])
     ids = pooled["idx"] // ndraws_per_run + 1                                                   # cld.(inds, N) with 1-based inds
     return MultiPathfinderResult(input if input is not None else target, rng, target.logp,
-                                 [r.fit_distribution for r in results], pooled["draws"], ids, results, psis_result, engs[0],
+                                 MixtureModel([r.fit_distribution for r in results]), pooled["draws"], ids, results, psis_result, engs[0],
                                  ndraws_per_run, engs)
 
 

@@ -2,6 +2,7 @@
 libpfmi.so on the MI355X; this file only marshals arrays across the C ABI."""
 import ctypes as C
 import os
+import sys
 import weakref
 
 import numpy as np
@@ -17,6 +18,12 @@ _u64p = C.POINTER(C.c_uint64)
 
 def _d(a):
     return a.ctypes.data_as(_dp) if a is not None else None
+
+
+def _is_torch(x):
+    """x is a torch tensor (without importing torch when the caller never did)"""
+    torch = sys.modules.get("torch")
+    return torch is not None and isinstance(x, torch.Tensor)
 
 
 # ---- large result arrays live in page-locked memory (include/pfmi.h: pfmi_host_alloc) --------------------------------------------
@@ -405,6 +412,39 @@ class Engine:
         out = np.empty(N)
         check(self.L.pfmi_logpdf(self.ctx, C.c_int64(p), C.c_int64(N), _d(X), _d(out)))
         return out
+
+    def mixture_logpdf(self, points, X, componentwise=False):
+        """Unnormalised log density of the uniform mixture of the fits `points` (repeats allowed) at the columns of X (d, N):
+        lse[n] = log sum_k exp(logpdf(points[k], X[:, n])) -- no - log K, so that the sums of several engines combine --
+        and, with componentwise=True, also comp (N, K) with comp[:, k] = logpdf(points[k], X).  X is a host array or a torch
+        tensor of shape (d, N) in column-major order on this engine's device (then so are the results)."""
+        pts = np.ascontiguousarray(points, dtype=np.int64).reshape(-1)
+        K = len(pts)
+        if _is_torch(X):
+            import torch
+            if X.device.type != "cuda" or X.device.index != self.device:
+                raise ValueError(f"mixture_logpdf: X is on {X.device}, the engine on cuda:{self.device}")
+            Xc = X.t().contiguous().t() if X.dim() == 2 else X   # column-major storage, (d, N) view
+            if Xc.dtype != torch.float64 or Xc.dim() != 2 or Xc.shape[0] != self.d:
+                raise ValueError(f"mixture_logpdf: X must be a float64 (d={self.d}, N) tensor")
+            N = Xc.shape[1]
+            lse = torch.empty(N, dtype=torch.float64, device=Xc.device)
+            comp = torch.empty((K, N), dtype=torch.float64, device=Xc.device) if componentwise else None
+            torch.cuda.current_stream(Xc.device).synchronize()  # X written by torch's stream before the ctx stream reads it
+            check(self.L.pfmi_mixture_logpdf_dev(self.ctx, C.c_int32(K), pts.ctypes.data_as(_i64p), C.c_int64(N),
+                                                 C.c_void_p(Xc.data_ptr()), C.c_void_p(lse.data_ptr()),
+                                                 C.c_void_p(comp.data_ptr() if comp is not None else None)))
+            self.sync()
+            return (lse, comp.t()) if componentwise else lse
+        X = np.asfortranarray(X, dtype=np.float64)
+        if X.ndim != 2:
+            raise ValueError("mixture_logpdf: X must be (d, N)")
+        N = X.shape[1]
+        lse = np.empty(N)
+        comp = np.empty((N, K), order="F") if componentwise else None
+        check(self.L.pfmi_mixture_logpdf(self.ctx, C.c_int32(K), pts.ctypes.data_as(_i64p), C.c_int64(N), _d(X), _d(lse),
+                                         _d(comp)))
+        return (lse, comp) if componentwise else lse
 
     # ---- remaining WoodburyPDMat operator surface -------------------------------------------------------
     OPS = dict(unwhiten=0, whiten=1, rmul=2, invunwhiten=3, mul=4, solve=5, quad=6, invquad=7)
