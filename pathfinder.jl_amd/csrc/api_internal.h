@@ -1,0 +1,69 @@
+// api_internal.h -- what the api_*.hip translation units (the extern "C" boundary of include/pfmi.h) share: the entry-point prologues,
+// the drains of calls that were never waited for, and the ONE statement of every buffer layout and sizing rule more than one entry
+// point relies on.  Each function is defined in the component it belongs to (named behind its declaration).
+#pragma once
+#include "pfmi_common.h"
+#include <stdlib.h>
+#include <string.h>
+
+#define PF_CTX(c)                                                          \
+    do {                                                                   \
+        PF_CHECK((c) != nullptr, PFMI_ERR_ARG, "null pfmi_ctx");           \
+        PF_HIP(hipSetDevice((c)->device));                                 \
+        pf_download_forget(c);                                             \
+    } while (0)
+// Entry points that enqueue work which REWRITES (or may reallocate) result buffers: the staged downloads still pending -- entries queued under
+// pfmi_defer_downloads survive several entry points, and their copy is only issued by the gather kernel of the next wait -- are issued NOW, in
+// stream order in front of the new work, so that they deliver the values of the call they were queued for (a source must be a
+// snapshot at queueing time, as it was when every download was its own stream-ordered copy).  No pending entry: no launch.
+#define PF_CTX_MUT(c)                                                      \
+    do {                                                                   \
+        PF_CTX(c);                                                         \
+        PF_TRY(pf_dl_flush(c));                                            \
+    } while (0)
+
+// a download the caller reads on return: queued like every other one, then the wait that delivers it
+inline int32_t d2h(pfmi_ctx *c, void *dst, const void *src, size_t bytes) {
+    if (bytes == 0) return PFMI_OK;
+    PF_TRY(pf_download(c, dst, src, bytes));
+    return pf_stream_sync(c);
+}
+
+struct StreamSwap {                       // the launch helpers enqueue on c->stream: point it at a side stream for the scope
+    pfmi_ctx *c; hipStream_t keep; int slot; bool seg;
+    StreamSwap(pfmi_ctx *c_, hipStream_t s, int qf_slot = 0, bool seg_mode = false) : c(c_), keep(c_->stream), slot(c_->qf_slot), seg(c_->qf_seg_mode) {
+        c->stream = s; c->qf_slot = qf_slot; c->qf_seg_mode = seg_mode;
+    }
+    ~StreamSwap() { c->stream = keep; c->qf_slot = slot; c->qf_seg_mode = seg; }
+};
+
+// what a new trace invalidates (entry points that clear another set of flags spell theirs out)
+inline void results_reset(pfmi_ctx *c) { c->fitted = false; c->elbo_done = false; c->pooled = false; c->have_trace_lp = false; }
+
+// ---- api_ctx.hip
+void stream_abandon(pfmi_ctx *c);          // drain and forget a streaming call that was never waited for
+void lbc_abandon(pfmi_ctx *c);             // the same for a packed closure optimisation
+int32_t ensure_pinned(pfmi_ctx *c, size_t x_bytes, size_t lp_bytes);
+
+// ---- api_inputs.hip
+// the packed layout of K paths with counts[k] >= 1 points each: off / path_of on the host and the device, K, d, P
+int32_t set_packed_layout(pfmi_ctx *c, int32_t K, int32_t d, const int64_t *counts);
+// the optimisers' fixed-stride staging trace [K][cap] (theta, grad, logp, point counts) and their starting points
+int32_t staging_reserve(pfmi_ctx *c, int32_t K, size_t cap, int32_t d);
+void lbc_begin(pfmi_ctx *c, int32_t K, int32_t J, int32_t maxiters, double g_tol, int32_t *prog);
+int32_t lbc_issue_rounds(pfmi_ctx *c, hipStream_t s);
+
+// ---- api_fit.hip
+// the per-point fit state of P points (slots) in K paths at column padding kpad; clears hist_src on the ctx stream
+int32_t fit_reserve(pfmi_ctx *c, size_t P, int32_t K, size_t d, int32_t J, int32_t kpad);
+
+// ---- api_elbo.hip
+int32_t elbo_reserve(pfmi_ctx *c, size_t P, int32_t K, int64_t N);       // the ELBO tables: logp / logq [P][N], elbo / se [P], best_iter [K]
+int64_t devcb_chunk_fits(const pfmi_ctx *c, int64_t per_fit_doubles, int64_t nf, int64_t N);
+// One block of a DEVICE_CALLBACK scan on stream `ss` (the ctx stream for the scope: StreamSwap): the draws of the `n` fits list[i] with
+// seeds[i] (parity mode: the normals d_u, ustride apart) into bx, the user's closure on them into blp, its rows scattered into the
+// point-indexed logp table (a failed fit's rows become NaN there).
+int32_t devcb_scan_block(pfmi_ctx *c, hipStream_t ss, const int32_t *list, const uint64_t *seeds, int64_t n, int64_t N, const double *d_u,
+                         int64_t ustride, double *bx, double *blp);
+int32_t callback_logp(pfmi_ctx *c, const double *d_x, int64_t n, double *d_lp);
+int32_t devcb_logp(pfmi_ctx *c, const double *d_x, int64_t n, double *d_lp, const int32_t *d_points, int64_t npts, int64_t N);

@@ -1,0 +1,198 @@
+// api_pool.hip -- the pooled stage: pool of draws, PSIS, resampling, gather.
+#include "api_internal.h"
+
+#include <vector>
+
+// ---- pool / PSIS / resample ---------------------------------------------------------------------------
+static int32_t pool_alloc(pfmi_ctx *c, int64_t N_r) {
+    const int K = c->K, d = c->d;
+    c->N_r = N_r;
+    const size_t S = (size_t)K * N_r;
+    PF_TRY(c->pool.ensure(sizeof(double) * S * d));
+    PF_TRY(c->pool_lr.ensure(sizeof(double) * S));
+    PF_TRY(c->pool_lp.ensure(sizeof(double) * S));
+    PF_TRY(c->pool_lq.ensure(sizeof(double) * S));
+    PF_TRY(c->pool_points.ensure(sizeof(int32_t) * K));
+    PF_TRY(c->pool_seeds.ensure(sizeof(uint64_t) * K));
+    return PFMI_OK;
+}
+
+// draws of the K fits in pool_points / pool_seeds (device) -> pool, log ratios
+static int32_t pool_fill(pfmi_ctx *c) {
+    const int K = c->K, d = c->d;
+    const int64_t N_r = c->N_r;
+    const size_t S = (size_t)K * N_r;
+    const bool cb = c->target.kind == PFMI_TARGET_HOST_CALLBACK, dcb = c->target.kind == PFMI_TARGET_DEVICE_CALLBACK;
+    PF_TRY(pf_launch_elbo_draws(c, c->pool_points.as<int32_t>(), c->pool_seeds.as<uint64_t>(), K, 0, N_r, nullptr, 0,
+                                c->pool.as<double>(), (int64_t)N_r * d, c->pool_lp.as<double>(),
+                                c->pool_lq.as<double>(), N_r, !cb && !dcb, false));
+    if (cb) PF_TRY(callback_logp(c, c->pool.as<double>(), (int64_t)S, c->pool_lp.as<double>()));
+    if (dcb) PF_TRY(devcb_logp(c, c->pool.as<double>(), (int64_t)S, c->pool_lp.as<double>(), c->pool_points.as<int32_t>(), K, N_r));
+    PF_TRY(pf_launch_logratio(c, (int64_t)S));
+    c->pooled = true;
+    return PFMI_OK;
+}
+
+extern "C" {
+
+int32_t pfmi_pool_build(pfmi_ctx *c, int64_t N_r, const int64_t *points, const uint64_t *seeds) {
+    PF_CTX_MUT(c);
+    PF_CHECK(c->fitted, PFMI_ERR_STATE, "pool_build: call pfmi_fit_batch first");
+    PF_CHECK(c->target.kind >= 0, PFMI_ERR_STATE, "pool_build: call pfmi_set_target first");
+    PF_CHECK(N_r >= 1 && points && seeds, PFMI_ERR_ARG, "pool_build: bad arguments");
+    const int K = c->K;
+    std::vector<int32_t> pts((size_t)K);
+    for (int k = 0; k < K; ++k) {
+        PF_CHECK(points[k] >= c->off[k] && points[k] < c->off[k] + c->path_npts(k), PFMI_ERR_ARG,
+                 "pool_build: point %lld does not belong to path %d", (long long)points[k], k);
+        pts[(size_t)k] = (int32_t)points[k];
+    }
+    PF_TRY(pool_alloc(c, N_r));
+    PF_TRY(pf_upload(c, c->pool_points.p, pts.data(), sizeof(int32_t) * K));
+    PF_TRY(pf_upload(c, c->pool_seeds.p, seeds, sizeof(uint64_t) * K));
+    c->pool_from_best = false;
+    return pool_fill(c);
+}
+
+int32_t pfmi_pool_build_best(pfmi_ctx *c, int64_t N_r, const uint64_t *fail_seeds) {
+    PF_CTX_MUT(c);
+    PF_CHECK(c->elbo_done, PFMI_ERR_STATE, "pool_build_best: call pfmi_elbo_batch[_enqueue] first");
+    PF_CHECK(N_r >= 1, PFMI_ERR_ARG, "pool_build_best: bad arguments");
+    PF_TRY(pool_alloc(c, N_r));
+    PF_TRY(c->pool_ok.ensure(sizeof(int32_t) * c->K));
+    if (fail_seeds) {
+        PF_TRY(c->fail_seeds.ensure(sizeof(uint64_t) * c->K));
+        PF_TRY(pf_upload(c, c->fail_seeds.p, fail_seeds, sizeof(uint64_t) * c->K));
+    }
+    PF_TRY(pf_launch_pool_pick(c, fail_seeds != nullptr));
+    c->pool_from_best = true;
+    return pool_fill(c);
+}
+
+int32_t pfmi_pool_winners(pfmi_ctx *c, int64_t *points, uint64_t *seeds, int32_t *success) {
+    PF_CTX(c);
+    PF_CHECK(c->pooled, PFMI_ERR_STATE, "pool_winners: call pfmi_pool_build[_best] first");
+    std::vector<int32_t> pts((size_t)c->K);
+    if (points) PF_TRY(pf_download(c, pts.data(), c->pool_points.p, sizeof(int32_t) * c->K));
+    if (seeds) PF_TRY(pf_download(c, seeds, c->pool_seeds.p, sizeof(uint64_t) * c->K));
+    if (success) {
+        PF_CHECK(c->pool_from_best, PFMI_ERR_STATE, "pool_winners: success flags exist only after pfmi_pool_build_best");
+        PF_TRY(pf_download(c, success, c->pool_ok.p, sizeof(int32_t) * c->K));
+    }
+    PF_TRY(pf_stream_sync(c));
+    if (points)
+        for (int k = 0; k < c->K; ++k) points[k] = pts[(size_t)k];
+    return PFMI_OK;
+}
+
+int32_t pfmi_pool_get(pfmi_ctx *c, double *draws, double *log_ratios) {
+    PF_CTX(c);
+    PF_CHECK(c->pooled, PFMI_ERR_STATE, "pool_get: call pfmi_pool_build first");
+    const size_t S = (size_t)c->K * c->N_r;
+    if (draws) PF_TRY(d2h(c, draws, c->pool.p, sizeof(double) * S * c->d));
+    if (log_ratios) PF_TRY(d2h(c, log_ratios, c->pool_lr.p, sizeof(double) * S));
+    return PFMI_OK;
+}
+
+int32_t pfmi_pool_log_ratios_dev(pfmi_ctx *c, void **dev_ptr, int64_t *count) {
+    PF_CTX(c);
+    PF_CHECK(c->pooled, PFMI_ERR_STATE, "pool_log_ratios_dev: call pfmi_pool_build first");
+    PF_HIP(hipStreamSynchronize(c->stream));
+    if (dev_ptr) *dev_ptr = c->pool_lr.p;
+    if (count) *count = (int64_t)c->K * c->N_r;
+    return PFMI_OK;
+}
+
+int32_t pfmi_psis_dev(pfmi_ctx *c, const void *lr_dev, int64_t S, double *weights, double *log_weights,
+                      double *pareto_k, int64_t *tail_len) {
+    PF_CTX_MUT(c);
+    PF_CHECK(lr_dev != nullptr && S > 0, PFMI_ERR_ARG, "psis: bad arguments");
+    PF_TRY(pf_launch_psis(c, reinterpret_cast<const double *>(lr_dev), S));
+    double out[4];
+    PF_TRY(d2h(c, out, c->psis_out.p, sizeof(out)));
+    if (pareto_k) *pareto_k = out[0];
+    if (tail_len) *tail_len = (int64_t)out[1];
+    if (weights) PF_TRY(d2h(c, weights, c->w.p, sizeof(double) * S));
+    if (log_weights) PF_TRY(d2h(c, log_weights, c->lw.p, sizeof(double) * S));
+    return PFMI_OK;
+}
+
+int32_t pfmi_psis_weights(pfmi_ctx *c, int64_t S, double *weights, double *log_weights) {
+    PF_CTX(c);
+    PF_CHECK(S > 0 && c->S_w == S, PFMI_ERR_STATE, "psis_weights: no PSIS result for S=%lld on this ctx", (long long)S);
+    if (weights) PF_TRY(pf_download(c, weights, c->w.p, sizeof(double) * S));
+    if (log_weights) PF_TRY(pf_download(c, log_weights, c->lw.p, sizeof(double) * S));
+    if (c->defer) return PFMI_OK;
+    return pf_stream_sync(c);
+}
+
+int32_t pfmi_psis(pfmi_ctx *c, const double *lr, int64_t S, double *weights, double *log_weights, double *pareto_k,
+                  int64_t *tail_len) {
+    PF_CTX_MUT(c);
+    PF_CHECK(lr != nullptr && S > 0, PFMI_ERR_ARG, "psis: bad arguments");
+    PF_TRY(c->gbuf.ensure(sizeof(double) * S));
+    PF_TRY(pf_upload(c, c->gbuf.p, lr, sizeof(double) * S));
+    return pfmi_psis_dev(c, c->gbuf.p, S, weights, log_weights, pareto_k, tail_len);
+}
+
+int32_t pfmi_resample_indices(pfmi_ctx *c, int64_t S, int64_t ndraws, int32_t importance, int32_t replace,
+                              uint64_t seed, const double *uniforms, int64_t *idx) {
+    PF_CTX_MUT(c);
+    PF_CHECK(S > 0 && ndraws >= 0, PFMI_ERR_ARG, "resample: bad arguments");
+    PF_CHECK(!importance || c->S_w == S, PFMI_ERR_STATE,
+             "resample: importance weights for S=%lld not available (run pfmi_psis first)", (long long)S);
+    const double *d_uni = nullptr;
+    if (uniforms && ndraws > 0) {
+        PF_TRY(c->tailbuf.ensure(sizeof(double) * ndraws));
+        PF_TRY(pf_upload(c, c->tailbuf.p, uniforms, sizeof(double) * ndraws));
+        d_uni = c->tailbuf.as<double>();
+    }
+    PF_TRY(pf_launch_resample(c, S, ndraws, importance, replace, seed, d_uni));
+    if (idx && ndraws > 0) PF_TRY(d2h(c, idx, c->idx.p, sizeof(int64_t) * ndraws));
+    return PFMI_OK;
+}
+
+int32_t pfmi_resample_indices_direct(pfmi_ctx *c, int64_t S, int64_t ndraws, const double *uniforms, int64_t *idx) {
+    PF_CTX_MUT(c);
+    PF_CHECK(S > 0 && ndraws >= 0 && (uniforms != nullptr || ndraws == 0), PFMI_ERR_ARG, "resample_direct: bad arguments");
+    PF_CHECK(c->S_w == S, PFMI_ERR_STATE, "resample_direct: importance weights for S=%lld not available (run pfmi_psis first)",
+             (long long)S);
+    if (ndraws == 0) return PFMI_OK;
+    for (int64_t t = 0; t < ndraws; ++t)
+        PF_CHECK(uniforms[t] >= 0.0 && uniforms[t] < 1.0, PFMI_ERR_ARG, "resample_direct: uniforms[%lld] = %g is not in [0, 1)", (long long)t,
+                 uniforms[t]);
+    PF_TRY(c->tailbuf.ensure(sizeof(double) * ndraws));
+    PF_TRY(pf_upload(c, c->tailbuf.p, uniforms, sizeof(double) * ndraws));
+    PF_TRY(pf_launch_resample_direct(c, S, ndraws, c->tailbuf.as<double>()));
+    if (idx) PF_TRY(d2h(c, idx, c->idx.p, sizeof(int64_t) * ndraws));
+    return PFMI_OK;
+}
+
+int32_t pfmi_pool_gather_dev(pfmi_ctx *c, int64_t ndraws, const int64_t *idx, int64_t col_offset, void *draws_dev) {
+    PF_CTX(c);
+    PF_CHECK(c->pooled, PFMI_ERR_STATE, "pool_gather: call pfmi_pool_build first");
+    PF_CHECK(ndraws >= 0 && idx && draws_dev, PFMI_ERR_ARG, "pool_gather: bad arguments");
+    PF_TRY(c->idx.ensure(sizeof(int64_t) * (ndraws > 0 ? ndraws : 1)));
+    PF_TRY(pf_upload(c, c->idx.p, idx, sizeof(int64_t) * ndraws));
+    PF_TRY(pf_launch_gather(c, ndraws, c->idx.as<int64_t>(), col_offset, reinterpret_cast<double *>(draws_dev)));
+    PF_HIP(hipStreamSynchronize(c->stream));
+    return PFMI_OK;
+}
+
+int32_t pfmi_pool_gather(pfmi_ctx *c, int64_t ndraws, const int64_t *idx, int64_t col_offset, double *draws) {
+    PF_CTX(c);
+    PF_CHECK(draws != nullptr, PFMI_ERR_ARG, "pool_gather: null output");
+    PF_CHECK(c->pooled, PFMI_ERR_STATE, "pool_gather: call pfmi_pool_build first");
+    PF_CHECK(ndraws >= 0 && (idx != nullptr || ndraws == 0), PFMI_ERR_ARG, "pool_gather: bad arguments");
+    const int64_t owned = (int64_t)c->K * c->N_r;
+    for (int64_t t = 0; t < ndraws; ++t)   // the host variant hands back real columns only: no silent zero fill
+        PF_CHECK(idx[t] >= col_offset && idx[t] < col_offset + owned, PFMI_ERR_ARG,
+                 "pool_gather: index %lld (position %lld) is outside this pool's columns [%lld, %lld)", (long long)idx[t],
+                 (long long)t, (long long)col_offset, (long long)(col_offset + owned));
+    PF_TRY(c->gbuf.ensure(sizeof(double) * (size_t)(ndraws > 0 ? ndraws : 1) * c->d));
+    PF_TRY(pfmi_pool_gather_dev(c, ndraws, idx, col_offset, c->gbuf.p));
+    PF_TRY(d2h(c, draws, c->gbuf.p, sizeof(double) * (size_t)ndraws * c->d));
+    return PFMI_OK;
+}
+
+}  // extern "C"

@@ -409,15 +409,9 @@ int32_t pf_launch_elbo_draws(pfmi_ctx *c, const int32_t *d_points, const uint64_
         dim3 grid((unsigned)gx, (unsigned)ns);
         pf_kernel_begin(c);
         int32_t rc = PFMI_OK;
-        switch (c->kpad) {
-            case 4: rc = launch_draws_k<4>(b, grid, c->stream, mem, tgt, rpad); break;
-            case 8: rc = launch_draws_k<8>(b, grid, c->stream, mem, tgt, rpad); break;
-            case 12: rc = launch_draws_k<12>(b, grid, c->stream, mem, tgt, rpad); break;
-            case 16: rc = launch_draws_k<16>(b, grid, c->stream, mem, tgt, rpad); break;
-            case 20: rc = launch_draws_k<20>(b, grid, c->stream, mem, tgt, rpad); break;
-            case 32: rc = launch_draws_k<32>(b, grid, c->stream, mem, tgt, rpad); break;
-            case 64: rc = launch_draws_k<64>(b, grid, c->stream, mem, tgt, rpad); break;     // history_length 17 .. 32: this kernel only
-            default: pf_set_error("unsupported kpad %d", c->kpad); rc = PFMI_ERR_UNSUPPORTED;
+        // (64 = history_length 17 .. 32: this kernel only)
+        if (!pf_dispatch_kpad<4, 8, 12, 16, 20, 32, 64>(c->kpad, [&](auto KP) { rc = launch_draws_k<KP()>(b, grid, c->stream, mem, tgt, rpad); })) {
+            pf_set_error("unsupported kpad %d", c->kpad); rc = PFMI_ERR_UNSUPPORTED;
         }
         pf_kernel_end(c, d_x ? "elbo_draws_x" : "elbo_draws");
         PF_TRY(rc);
@@ -484,22 +478,13 @@ int32_t pf_launch_logratio(pfmi_ctx *c, int64_t n) {
 int32_t pf_launch_logpdf(pfmi_ctx *c, int64_t point, int64_t N, const double *d_x, double *d_out) {
     if (N <= 0) return PFMI_OK;
     dim3 grid((unsigned)((N + ELBO_THREADS - 1) / ELBO_THREADS));
-#define PF_LPDF(KP)                                                                                         \
-    hipLaunchKernelGGL(pf_logpdf_kernel<KP>, grid, dim3(ELBO_THREADS), 0, c->stream, c->d, (int)point, N, d_x, \
-                       c->vh.as<double>(), c->tmat.as<double>(), c->vchol.as<double>(),                     \
-                       c->sqrt_alpha.as<double>(), c->mu.as<double>(), c->logdet.as<double>(),              \
-                       c->status.as<int32_t>(), d_out)
-    switch (c->kpad) {
-        case 4: PF_LPDF(4); break;
-        case 8: PF_LPDF(8); break;
-        case 12: PF_LPDF(12); break;
-        case 16: PF_LPDF(16); break;
-        case 20: PF_LPDF(20); break;
-        case 32: PF_LPDF(32); break;
-        case 64: PF_LPDF(64); break;
-        default: PF_CHECK(false, PFMI_ERR_UNSUPPORTED, "unsupported kpad %d", c->kpad);
-    }
-#undef PF_LPDF
+    const bool ok = pf_dispatch_kpad<4, 8, 12, 16, 20, 32, 64>(c->kpad, [&](auto KP) {
+        hipLaunchKernelGGL(pf_logpdf_kernel<KP()>, grid, dim3(ELBO_THREADS), 0, c->stream, c->d, (int)point, N, d_x,
+                           c->vh.as<double>(), c->tmat.as<double>(), c->vchol.as<double>(),
+                           c->sqrt_alpha.as<double>(), c->mu.as<double>(), c->logdet.as<double>(),
+                           c->status.as<int32_t>(), d_out);
+    });
+    PF_CHECK(ok, PFMI_ERR_UNSUPPORTED, "unsupported kpad %d", c->kpad);
     PF_HIP(hipGetLastError());
     return PFMI_OK;
 }

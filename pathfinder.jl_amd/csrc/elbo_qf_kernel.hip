@@ -911,14 +911,7 @@ static int32_t launch_qf_t(pfmi_ctx *c, const ElboArgs &a, int64_t nfits, int tg
 int32_t pf_launch_elbo_qf(pfmi_ctx *c, const ElboArgs &a, int64_t nfits, int tgt, int rpad, bool *handled) {
     *handled = false;
     if (a.u != nullptr || a.x != nullptr) return PFMI_OK;
-    *handled = true;
-    switch (c->kpad) {
-        case 4: return launch_qf_t<4>(c, a, nfits, tgt, rpad);
-        case 8: return launch_qf_t<8>(c, a, nfits, tgt, rpad);
-        case 12: return launch_qf_t<12>(c, a, nfits, tgt, rpad);
-        case 16: return launch_qf_t<16>(c, a, nfits, tgt, rpad);
-        case 20: return launch_qf_t<20>(c, a, nfits, tgt, rpad);
-        case 32: return launch_qf_t<32>(c, a, nfits, tgt, rpad);
-        default: *handled = false; return PFMI_OK;
-    }
+    int32_t rc = PFMI_OK;
+    *handled = pf_dispatch_kpad<4, 8, 12, 16, 20, 32>(c->kpad, [&](auto KP) { rc = launch_qf_t<KP()>(c, a, nfits, tgt, rpad); });
+    return rc;
 }

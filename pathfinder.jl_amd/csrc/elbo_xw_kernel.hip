@@ -510,14 +510,7 @@ static int32_t launch_xw(pfmi_ctx *c, const ElboArgs &a, int64_t nfits) {
 int32_t pf_launch_elbo_xw(pfmi_ctx *c, const ElboArgs &a, int64_t nfits, bool *handled) {
     *handled = false;
     if (a.u != nullptr || a.x == nullptr) return PFMI_OK;
-    *handled = true;
-    switch (c->kpad) {
-        case 4: return launch_xw<4>(c, a, nfits);
-        case 8: return launch_xw<8>(c, a, nfits);
-        case 12: return launch_xw<12>(c, a, nfits);
-        case 16: return launch_xw<16>(c, a, nfits);
-        case 20: return launch_xw<20>(c, a, nfits);
-        case 32: return launch_xw<32>(c, a, nfits);
-        default: *handled = false; return PFMI_OK;
-    }
+    int32_t rc = PFMI_OK;
+    *handled = pf_dispatch_kpad<4, 8, 12, 16, 20, 32>(c->kpad, [&](auto KP) { rc = launch_xw<KP()>(c, a, nfits); });
+    return rc;
 }

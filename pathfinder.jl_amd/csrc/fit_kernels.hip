@@ -1269,20 +1269,12 @@ int32_t pf_launch_fit(pfmi_ctx *c, int seg_l0, int seg_len) {
             return PFMI_OK;
         }
     }
-    switch (c->kpad) {
-        case 4: launch_fit_t<4>(c, a); break;
-        case 8: launch_fit_t<8>(c, a); break;
-        case 12: launch_fit_t<12>(c, a); break;
-        case 16: launch_fit_t<16>(c, a); break;
-        case 20: launch_fit_t<20>(c, a); break;
-        case 32: launch_fit_t<32>(c, a); break;
-        case 64:
-            PF_TRY(c->fit_scratch.ensure(sizeof(double) * (size_t)a.P * 64 * 64));
-            a.big = c->fit_scratch.as<double>();
-            launch_fit_t<64>(c, a);
-            break;
-        default: PF_CHECK(false, PFMI_ERR_UNSUPPORTED, "unsupported kpad %d", c->kpad);
+    if (c->kpad == 64) {                                     // its small matrices live in global memory
+        PF_TRY(c->fit_scratch.ensure(sizeof(double) * (size_t)a.P * 64 * 64));
+        a.big = c->fit_scratch.as<double>();
     }
+    PF_CHECK((pf_dispatch_kpad<4, 8, 12, 16, 20, 32, 64>(c->kpad, [&](auto KP) { launch_fit_t<KP()>(c, a); })), PFMI_ERR_UNSUPPORTED,
+             "unsupported kpad %d", c->kpad);
     pf_kernel_end(c, "fit");
     PF_HIP(hipGetLastError());
     return PFMI_OK;

@@ -276,21 +276,12 @@ int32_t pf_launch_mixture_logpdf(pfmi_ctx *c, int K, const int32_t *d_points, in
     if (lane) {
         PF_CHECK((N + MX_LANE_THREADS - 1) / MX_LANE_THREADS <= INT32_MAX, PFMI_ERR_ARG, "mixture_logpdf: N too large");
         dim3 grid((unsigned)((N + MX_LANE_THREADS - 1) / MX_LANE_THREADS), (unsigned)K);
-#define PF_MXL(KP)                                                                                                             \
-    hipLaunchKernelGGL(pf_mixture_lane_kernel<KP>, grid, dim3(MX_LANE_THREADS), 0, c->stream, d, N, d_x, d_points,             \
-                       c->vh.as<double>(), c->tmat.as<double>(), c->vchol.as<double>(), c->sqrt_alpha.as<double>(), c->mu.as<double>(), \
-                       c->logdet.as<double>(), c->status.as<int32_t>(), d_comp)
-        switch (kp) {
-            case 4: PF_MXL(4); break;
-            case 8: PF_MXL(8); break;
-            case 12: PF_MXL(12); break;
-            case 16: PF_MXL(16); break;
-            case 20: PF_MXL(20); break;
-            case 32: PF_MXL(32); break;
-            case 64: PF_MXL(64); break;
-            default: PF_CHECK(false, PFMI_ERR_UNSUPPORTED, "unsupported kpad %d", kp);
-        }
-#undef PF_MXL
+        const bool ok = pf_dispatch_kpad<4, 8, 12, 16, 20, 32, 64>(kp, [&](auto KP) {
+            hipLaunchKernelGGL(pf_mixture_lane_kernel<KP()>, grid, dim3(MX_LANE_THREADS), 0, c->stream, d, N, d_x, d_points,
+                               c->vh.as<double>(), c->tmat.as<double>(), c->vchol.as<double>(), c->sqrt_alpha.as<double>(), c->mu.as<double>(),
+                               c->logdet.as<double>(), c->status.as<int32_t>(), d_comp);
+        });
+        PF_CHECK(ok, PFMI_ERR_UNSUPPORTED, "unsupported kpad %d", kp);
     } else {
         const int64_t ntiles = (N + 15) / 16;
         PF_CHECK(ntiles <= INT32_MAX, PFMI_ERR_ARG, "mixture_logpdf: N too large");
@@ -302,32 +293,25 @@ int32_t pf_launch_mixture_logpdf(pfmi_ctx *c, int K, const int32_t *d_points, in
         const int cpb = (int)((K + ng - 1) / ng);
         const int ngroups = (K + cpb - 1) / cpb;
         dim3 grid((unsigned)ntiles, (unsigned)ngroups);
-#define PF_MXM(KP)                                                                                                             \
-    {                                                                                                                          \
-        const size_t dyn = sizeof(double) * (size_t)32 * ((d + 31) / 32) * ((KP) + 2);                                           \
-        const bool stage = dyn + sizeof(double) * mx_static_lds(KP) <= MX_LDS_MAX;                                               \
-        const void *kern = stage ? reinterpret_cast<const void *>(pf_mixture_mfma_kernel<KP, true>)                             \
-                                 : reinterpret_cast<const void *>(pf_mixture_mfma_kernel<KP, false>);                           \
-        if (stage) PF_TRY(pf_raise_lds_limit(c, kern, (int)(MX_LDS_MAX - sizeof(double) * mx_static_lds(KP))));                \
-        if (stage)                                                                                                             \
-            hipLaunchKernelGGL((pf_mixture_mfma_kernel<KP, true>), grid, dim3(MX_THREADS), dyn, c->stream, d, N, K, cpb, d_x,     \
-                               d_points, c->vh.as<double>(), c->tmat.as<double>(), c->vchol.as<double>(),                       \
-                               c->sqrt_alpha.as<double>(), c->mu.as<double>(), c->logdet.as<double>(), c->status.as<int32_t>(), d_comp); \
-        else                                                                                                                   \
-            hipLaunchKernelGGL((pf_mixture_mfma_kernel<KP, false>), grid, dim3(MX_THREADS), 0, c->stream, d, N, K, cpb, d_x,      \
-                               d_points, c->vh.as<double>(), c->tmat.as<double>(), c->vchol.as<double>(),                       \
-                               c->sqrt_alpha.as<double>(), c->mu.as<double>(), c->logdet.as<double>(), c->status.as<int32_t>(), d_comp); \
-    }
-        switch (kp) {
-            case 4: PF_MXM(4); break;
-            case 8: PF_MXM(8); break;
-            case 12: PF_MXM(12); break;
-            case 16: PF_MXM(16); break;
-            case 20: PF_MXM(20); break;
-            case 32: PF_MXM(32); break;
-            default: PF_CHECK(false, PFMI_ERR_UNSUPPORTED, "unsupported kpad %d", kp);
-        }
-#undef PF_MXM
+        int32_t rc = PFMI_OK;
+        const bool ok = pf_dispatch_kpad<4, 8, 12, 16, 20, 32>(kp, [&](auto KPc) {
+            constexpr int KP = KPc();
+            const size_t dyn = sizeof(double) * (size_t)32 * ((d + 31) / 32) * (KP + 2);
+            if (dyn + sizeof(double) * mx_static_lds(KP) <= MX_LDS_MAX) {           // the factor block staged in LDS
+                rc = pf_raise_lds_limit(c, reinterpret_cast<const void *>(pf_mixture_mfma_kernel<KP, true>),
+                                        (int)(MX_LDS_MAX - sizeof(double) * mx_static_lds(KP)));
+                if (rc != PFMI_OK) return;
+                hipLaunchKernelGGL((pf_mixture_mfma_kernel<KP, true>), grid, dim3(MX_THREADS), dyn, c->stream, d, N, K, cpb, d_x,
+                                   d_points, c->vh.as<double>(), c->tmat.as<double>(), c->vchol.as<double>(),
+                                   c->sqrt_alpha.as<double>(), c->mu.as<double>(), c->logdet.as<double>(), c->status.as<int32_t>(), d_comp);
+            } else {
+                hipLaunchKernelGGL((pf_mixture_mfma_kernel<KP, false>), grid, dim3(MX_THREADS), 0, c->stream, d, N, K, cpb, d_x,
+                                   d_points, c->vh.as<double>(), c->tmat.as<double>(), c->vchol.as<double>(),
+                                   c->sqrt_alpha.as<double>(), c->mu.as<double>(), c->logdet.as<double>(), c->status.as<int32_t>(), d_comp);
+            }
+        });
+        PF_CHECK(ok, PFMI_ERR_UNSUPPORTED, "unsupported kpad %d", kp);
+        PF_TRY(rc);
     }
     PF_HIP(hipGetLastError());
     pf_kernel_end(c, "mixture_logpdf");

@@ -8,6 +8,7 @@
 #include <string>
 #include <map>
 #include <set>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/pfmi.h"
@@ -38,10 +39,15 @@ void pf_set_error(const char *fmt, ...);
         if (rc__ != PFMI_OK) return rc__;                                                         \
     } while (0)
 
-// ---- growable device buffer ------------------------------------------------------------------------
+// ---- growable device buffer: owns its memory (freed with its owner; the owner makes the device current and idle first) ----
 struct DevBuf {
     void *p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }     // (std::vector<DevBuf>::resize)
+    ~DevBuf() { release(); }
     int32_t ensure(size_t bytes) {
         if (bytes <= cap) return PFMI_OK;
         if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
@@ -54,10 +60,23 @@ struct DevBuf {
     template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
 };
 
+// ---- column padding of a fit (kpad): the one run-time -> compile-time switch of the launch helpers --------------------------
+// pf_dispatch_kpad<4, 8, ...>(kpad, [&](auto KP) { ... KP() ... }) calls the generic lambda with std::integral_constant<int, K> for the
+// K of the list that equals kpad; false when none does (the caller keeps its own answer to an unsupported padding).
+template <int... KS, typename F>
+inline bool pf_dispatch_kpad(int kpad, F &&f) {
+    return ((kpad == KS ? (f(std::integral_constant<int, KS>{}), true) : false) || ...);
+}
+// the padding pfmi_fit_batch / pfmi_stream_enqueue give history_length J (2 J columns); 0: none (J > 32)
+inline int pf_kpad_for(int J) {
+    for (int o : {4, 8, 12, 16, 20, 32, 64}) if (2 * J <= o) return o;
+    return 0;
+}
+
 struct KernelStat { double ms = 0.0; int64_t launches = 0; };
 
 // pinned host arena of a ctx: small host -> device uploads are staged here and copied asynchronously on the ctx stream, so that an
-// upload never forces a stream synchronisation in the middle of an enqueued pipeline (pf_upload in pfmi_api.hip).  Bump allocated;
+// upload never forces a stream synchronisation in the middle of an enqueued pipeline (pf_upload in api_ctx.hip).  Bump allocated;
 // rewound whenever the stream is known to be idle (pf_arena_reset after a full synchronisation).
 struct PinArena { char *base = nullptr; size_t cap = 0, off = 0; };
 // a small device -> host download staged in the ctx's pinned download arena: delivered to `dst` by pf_stream_sync

@@ -190,26 +190,20 @@ __global__ void pf_woodbury_diag_kernel(int d, int J, int p, int64_t p0, const d
 template <int KPAD>
 static void launch_wb(pfmi_ctx *c, int mode, int64_t p, int64_t N, const double *in, double *out) {
     dim3 grid((unsigned)((N + WB_THREADS - 1) / WB_THREADS)), block(WB_THREADS);
-#define PF_WB(M)                                                                                                   \
-    hipLaunchKernelGGL((pf_woodbury_kernel<KPAD, M>), grid, block, 0, c->stream, c->d, (int)p, N, in, out,          \
-                       c->vh.as<double>(), c->tmat.as<double>(), c->vchol.as<double>(), c->sqrt_alpha.as<double>(), \
-                       c->status.as<int32_t>())
-    if (mode == 0) PF_WB(0); else if (mode == 1) PF_WB(1); else if (mode == 2) PF_WB(2); else PF_WB(3);
-#undef PF_WB
+    auto go = [&](auto M) {
+        hipLaunchKernelGGL((pf_woodbury_kernel<KPAD, M()>), grid, block, 0, c->stream, c->d, (int)p, N, in, out,
+                           c->vh.as<double>(), c->tmat.as<double>(), c->vchol.as<double>(), c->sqrt_alpha.as<double>(),
+                           c->status.as<int32_t>());
+    };
+    using std::integral_constant;
+    if (mode == 0) go(integral_constant<int, 0>{}); else if (mode == 1) go(integral_constant<int, 1>{});
+    else if (mode == 2) go(integral_constant<int, 2>{}); else go(integral_constant<int, 3>{});
 }
 
 int32_t pf_launch_woodbury_prim(pfmi_ctx *c, int mode, int64_t p, int64_t N, const double *d_in, double *d_out) {
     if (N <= 0) return PFMI_OK;
-    switch (c->kpad) {
-        case 4: launch_wb<4>(c, mode, p, N, d_in, d_out); break;
-        case 8: launch_wb<8>(c, mode, p, N, d_in, d_out); break;
-        case 12: launch_wb<12>(c, mode, p, N, d_in, d_out); break;
-        case 16: launch_wb<16>(c, mode, p, N, d_in, d_out); break;
-        case 20: launch_wb<20>(c, mode, p, N, d_in, d_out); break;
-        case 32: launch_wb<32>(c, mode, p, N, d_in, d_out); break;
-        case 64: launch_wb<64>(c, mode, p, N, d_in, d_out); break;
-        default: PF_CHECK(false, PFMI_ERR_UNSUPPORTED, "unsupported kpad %d", c->kpad);
-    }
+    PF_CHECK((pf_dispatch_kpad<4, 8, 12, 16, 20, 32, 64>(c->kpad, [&](auto KP) { launch_wb<KP()>(c, mode, p, N, d_in, d_out); })),
+             PFMI_ERR_UNSUPPORTED, "unsupported kpad %d", c->kpad);
     PF_HIP(hipGetLastError());
     return PFMI_OK;
 }
@@ -224,21 +218,12 @@ int32_t pf_launch_colsumsq(pfmi_ctx *c, int64_t N, const double *d_x, double *d_
 int32_t pf_launch_woodbury_diag(pfmi_ctx *c, int64_t p, double *d_out) {
     const int64_t p0 = c->off[(size_t)c->path_of[(size_t)p]];
     dim3 grid((unsigned)((c->d + 255) / 256)), block(256);
-#define PF_WD(KP)                                                                                                   \
-    hipLaunchKernelGGL(pf_woodbury_diag_kernel<KP>, grid, block, 0, c->stream, c->d, c->J, (int)p, p0,               \
-                       c->th(), c->gr(), c->alpha_all.as<double>(),                       \
-                       c->hist_len.as<int32_t>(), c->hist_src.as<int32_t>(), c->dmat.as<double>(), d_out)
-    switch (c->kpad) {
-        case 4: PF_WD(4); break;
-        case 8: PF_WD(8); break;
-        case 12: PF_WD(12); break;
-        case 16: PF_WD(16); break;
-        case 20: PF_WD(20); break;
-        case 32: PF_WD(32); break;
-        case 64: PF_WD(64); break;
-        default: PF_CHECK(false, PFMI_ERR_UNSUPPORTED, "unsupported kpad %d", c->kpad);
-    }
-#undef PF_WD
+    const bool ok = pf_dispatch_kpad<4, 8, 12, 16, 20, 32, 64>(c->kpad, [&](auto KP) {
+        hipLaunchKernelGGL(pf_woodbury_diag_kernel<KP()>, grid, block, 0, c->stream, c->d, c->J, (int)p, p0,
+                           c->th(), c->gr(), c->alpha_all.as<double>(),
+                           c->hist_len.as<int32_t>(), c->hist_src.as<int32_t>(), c->dmat.as<double>(), d_out);
+    });
+    PF_CHECK(ok, PFMI_ERR_UNSUPPORTED, "unsupported kpad %d", c->kpad);
     PF_HIP(hipGetLastError());
     return PFMI_OK;
 }

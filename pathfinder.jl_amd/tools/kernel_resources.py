@@ -20,7 +20,7 @@ LIB = os.path.join(os.path.dirname(HERE), "lib", "libpfmi.so")
 LLVM = "/opt/rocm/lib/llvm/bin"
 MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 _KEYS = ("vgpr_count", "agpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size",
-         "group_segment_fixed_size", "max_flat_workgroup_size")
+         "group_segment_fixed_size", "max_flat_workgroup_size", "kernarg_segment_size")
 
 
 def code_objects(lib=LIB):
