@@ -329,6 +329,18 @@ int32_t pfmi_pool_build(pfmi_ctx *ctx, int64_t N_r, const int64_t *points, const
 int32_t pfmi_pool_build_best(pfmi_ctx *ctx, int64_t N_r, const uint64_t *fail_seeds);
 int32_t pfmi_pool_winners(pfmi_ctx *ctx, int64_t *points, uint64_t *seeds, int32_t *success);
 int32_t pfmi_pool_get(pfmi_ctx *ctx, double *draws, double *log_ratios);
+/* Weighted moments of the pool on the device, per local run k and coordinate i (run-major outputs, any of them may be NULL).  With
+ * t = x_i - center[i] (center NULL: 0) and the sums over the N_r draws n of run k:
+ *   s1[k*d + i] = sum w t      s2[k*d + i] = sum w t^2      s2w[k*d + i] = sum w^2 t^2      wsum[2k], wsum[2k + 1] = sum w, sum w^2
+ * importance != 0: w = the ctx's current PSIS weight of global pool column col_offset + k*N_r + n (pfmi_psis / pfmi_comm_pool_psis;
+ * replicated on every GPU); a column whose weight is exactly 0 is skipped, whatever it holds (a non-finite draw there contributes
+ * nothing).  importance == 0: w = 1 and nothing is skipped (a non-finite draw gives a non-finite sum).
+ * Ordering guarantee: no atomics, and the order in which the terms of one run are added depends on (d, N_r) only -- not on K, col_offset
+ * or the run's position -- so a run's sums have the same bits on whichever ctx owns it, and two calls return identical results.
+ * No pool: PFMI_ERR_STATE; importance != 0 without a PSIS result covering [col_offset, col_offset + K*N_r): PFMI_ERR_STATE;
+ * col_offset < 0: PFMI_ERR_ARG. */
+int32_t pfmi_pool_moments(pfmi_ctx *ctx, int64_t col_offset, int32_t importance, const double *center, double *wsum, double *s1,
+                          double *s2, double *s2w);
 /* device pointer to the local log-ratio shard (K_local * N_r doubles) for the RCCL all-gather */
 int32_t pfmi_pool_log_ratios_dev(pfmi_ctx *ctx, void **dev_ptr, int64_t *count);
 

@@ -94,6 +94,28 @@ int32_t pfmi_pool_get(pfmi_ctx *c, double *draws, double *log_ratios) {
     return PFMI_OK;
 }
 
+int32_t pfmi_pool_moments(pfmi_ctx *c, int64_t col_offset, int32_t importance, const double *center, double *wsum, double *s1,
+                          double *s2, double *s2w) {
+    PF_CTX_MUT(c);
+    PF_CHECK(c->pooled, PFMI_ERR_STATE, "pool_moments: call pfmi_pool_build first");
+    PF_CHECK(col_offset >= 0, PFMI_ERR_ARG, "pool_moments: negative col_offset");
+    const size_t K = (size_t)c->K, d = (size_t)c->d;
+    PF_CHECK(!importance || (c->S_w > 0 && col_offset + (int64_t)K * c->N_r <= c->S_w), PFMI_ERR_STATE,
+             "pool_moments: no PSIS weights for columns [%lld, %lld) on this ctx (run pfmi_psis / pfmi_comm_pool_psis first)",
+             (long long)col_offset, (long long)(col_offset + (int64_t)K * c->N_r));
+    if (center) {
+        PF_TRY(c->mom_center.ensure(sizeof(double) * d));
+        PF_TRY(pf_upload(c, c->mom_center.p, center, sizeof(double) * d));
+    }
+    PF_TRY(pf_launch_pool_moments(c, col_offset, importance, center ? c->mom_center.as<double>() : nullptr));
+    const double *m = c->mom.as<double>();
+    if (wsum) PF_TRY(pf_download(c, wsum, m, sizeof(double) * 2 * K));
+    if (s1) PF_TRY(pf_download(c, s1, m + 2 * K, sizeof(double) * K * d));
+    if (s2) PF_TRY(pf_download(c, s2, m + 2 * K + K * d, sizeof(double) * K * d));
+    if (s2w) PF_TRY(pf_download(c, s2w, m + 2 * K + 2 * K * d, sizeof(double) * K * d));
+    return pf_stream_sync(c);
+}
+
 int32_t pfmi_pool_log_ratios_dev(pfmi_ctx *c, void **dev_ptr, int64_t *count) {
     PF_CTX(c);
     PF_CHECK(c->pooled, PFMI_ERR_STATE, "pool_log_ratios_dev: call pfmi_pool_build first");

@@ -267,6 +267,9 @@ struct pfmi_ctx {
     DevBuf pool_ok;               // int32 [K]: 1 = the path's winning fit was a success (pfmi_pool_build_best)
     DevBuf fail_seeds;            // u64 [K]
     DevBuf rs_err;                // int32: error flag of the last enqueued index selection
+    DevBuf mom;                   // pfmi_pool_moments: [wsum K 2][s1 K d][s2 K d][s2w K d]
+    DevBuf mom_part;              // its per-chunk partial sums (pool_moments_kernels.hip)
+    DevBuf mom_center;            // its centre vector [d]
 };
 
 // small host -> device upload on the ctx stream WITHOUT synchronising it (pinned arena); large blocks take the synchronous path
@@ -296,6 +299,8 @@ int32_t pf_launch_logpdf(pfmi_ctx *c, int64_t point, int64_t N, const double *d_
 int32_t pf_launch_mixture_logpdf(pfmi_ctx *c, int K, const int32_t *d_points, int64_t N, const double *d_x, double *d_lse,
                                  double *d_comp);
 int32_t pf_launch_psis(pfmi_ctx *c, const double *d_lr, int64_t S);
+// weighted moments of the ctx's pool into c->mom (weights c->w + col_offset when importance != 0; d_center: device, d doubles or NULL)
+int32_t pf_launch_pool_moments(pfmi_ctx *c, int64_t col_offset, int importance, const double *d_center);
 // Test / tuning hooks (kernel selection, the RCCL stand-in, ...): a value set with pfmi_debug_set(), or -- ONLY when the process was
 // started with PFMI_DEBUG_HOOKS=1 -- the environment variable of that name.  A production process therefore never has its numerics or
 // its dlopen path changed by a stray environment variable.  NULL when unset.

@@ -847,6 +847,65 @@ function componentwise_logpdf(result::Pathfinder.MultiPathfinderResult, X::Abstr
     return out
 end
 
+# ---- importance-weighted summaries from the pooled candidates (pfmi_pool_moments) -----------------------------------------------------
+"""
+    pool_moments(b::Batch, K; col_offset=0, importance=true, center=nothing) -> (wsum, s1, s2, s2w)
+
+Weighted moments of the engine's pool reduced on the device, per local run (columns of the d x K results; `wsum` is 2 x K =
+(Σw, Σw²)): with t = x - center over a run's draws, s1 = Σ w t, s2 = Σ w t², s2w = Σ w² t².  `w` are the engine's current PSIS
+weights of global pool columns `col_offset + (k-1) N_r + n`, or 1 with `importance=false`; zero-weight columns are skipped.
+"""
+function pool_moments(b::Batch, K::Int; col_offset::Integer=0, importance::Bool=true, center::Union{Nothing,Vector{Float64}}=nothing)
+    _live(b.eng, b.gen)
+    wsum = Matrix{Float64}(undef, 2, K)
+    s1 = Matrix{Float64}(undef, b.dim, K); s2 = similar(s1); s2w = similar(s1)
+    check(ccall((:pfmi_pool_moments, libpfmi), Int32,
+                (Ptr{Cvoid}, Int64, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                b.eng.ptr, col_offset, importance, center === nothing ? Ptr{Float64}(C_NULL) : pointer(center), wsum, s1, s2, s2w))
+    return wsum, s1, s2, s2w
+end
+
+"columns of the engines' blocks, concatenated in global run order and added one by one in that order"
+function _combine_moments(blocks)
+    rows = reduce(hcat, blocks)
+    total = zeros(Float64, size(rows, 1))
+    for k in axes(rows, 2)
+        total = total .+ rows[:, k]
+    end
+    return total
+end
+
+"""
+    importance_summary(result::Pathfinder.MultiPathfinderResult; importance=true)
+
+Posterior `mean`, `var`, `std`, `mcse_mean`, `ess`, `run_weights`, `ncandidates` and `pareto_shape` from ALL pooled candidates under
+their PSIS weights (uniform weights with `importance=false` or without a `psis_result`).  Every engine re-pools its runs' stored
+draws from their seeds, the pooled PSIS is re-run, and two moment passes (about the origin, then about the mean) run on the
+device; only the host adds across runs, in run order, so the summary does not depend on the number of engines.
+"""
+function importance_summary(result::Pathfinder.MultiPathfinderResult; importance::Bool=true)
+    runs = result.pathfinder_results
+    groups = _mixture_blocks(result)
+    N_r = first(runs).ndraws
+    for (b, ks, pts) in groups
+        seeds = UInt64[runs[k].draw_seed for k in ks]
+        check(ccall((:pfmi_pool_build, libpfmi), Int32, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{UInt64}), b.eng.ptr, N_r, pts, seeds))
+    end
+    weighted = importance && result.psis_result !== nothing
+    k̂ = weighted ? pool_psis(comm_for(Engine[g[1].eng for g in groups]))[1] : NaN
+    pass(center) = [pool_moments(b, length(ks); col_offset=(first(ks) - 1) * N_r, importance=weighted, center) for (b, ks, _) in groups]
+    p1 = pass(nothing)
+    wtot = _combine_moments([p[1] for p in p1])
+    W = wtot[1]
+    μ = _combine_moments([p[2] for p in p1]) ./ W
+    p2 = pass(μ)
+    v = _combine_moments([p[3] for p in p2]) ./ W .- (_combine_moments([p[2] for p in p2]) ./ W) .^ 2
+    mcse = sqrt.(_combine_moments([p[4] for p in p2])) ./ W
+    run_weights = reduce(vcat, [p[1][1, :] for p in p1]) ./ W
+    return (mean=μ, var=v, std=sqrt.(v), mcse_mean=mcse, ess=W^2 / wtot[2], run_weights=run_weights,
+            ncandidates=length(runs) * N_r, pareto_shape=k̂)
+end
+
 # ---- multi-GPU collectives (the `Comm` type itself is defined next to `Engine`) ---------------------------------------------------------
 """
     psis_resample(c, dim, ndraws; importance, replace, seed) -> (pareto_shape, tail_length, idx0, draws)

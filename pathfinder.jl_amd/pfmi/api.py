@@ -368,6 +368,10 @@ class MultiPathfinderResult:        # src/multipath.jl:31-44
     @property
     def draws_transformed(self): return self.draws
 
+    def summary(self, importance=True):
+        """importance-weighted posterior summaries from ALL pooled candidates, reduced on the device: importance_summary(self)"""
+        return importance_summary(self, importance=importance)
+
     def __str__(self):                  # Base.show, src/multipath.jl:46-65
         lines = ["Multi-path Pathfinder result", f"  runs: {len(self.pathfinder_results)}", f"  draws: {self.draws.shape[1]}"]
         if self.psis_result is not None:
@@ -904,6 +908,68 @@ def multipathfinder(target, ndraws, *, init=None, nruns=-1, ndraws_elbo=DEFAULT_
     return MultiPathfinderResult(input if input is not None else target, rng, target.logp,
                                  MixtureModel([r.fit_distribution for r in results]), pooled["draws"], ids, results, psis_result, engs[0],
                                  ndraws_per_run, engs)
+
+
+@dataclass
+class ImportanceSummary:
+    """Posterior summaries from the S = nruns * ndraws_per_run pooled candidates under their PSIS weights (importance_summary)."""
+    mean: np.ndarray                # (d,) sum w x / W
+    var: np.ndarray                 # (d,) sum w (x - mean)^2 / W
+    std: np.ndarray                 # (d,) sqrt(var)
+    mcse_mean: np.ndarray           # (d,) sqrt(sum w^2 (x - mean)^2) / W: Monte Carlo standard error of `mean`
+    ess: float                      # W^2 / sum w^2
+    run_weights: np.ndarray         # (nruns,) share of the mass each run carries
+    ncandidates: int                # S
+    pareto_shape: float             # k-hat of the pooled PSIS (NaN for uniform weights)
+
+
+def _combine_moments(blocks):
+    """Totals over runs of per-run arrays that arrive in blocks (one per engine, in global run order): the blocks are concatenated
+    along the run axis and the rows added one by one in that order.  Only this function adds across runs, so the totals do not
+    depend on how the runs are split into blocks."""
+    rows = np.concatenate([np.asarray(b, dtype=np.float64) for b in blocks], axis=0)
+    total = np.zeros(rows.shape[1:], dtype=np.float64)
+    for row in rows:
+        total = total + row
+    return total
+
+
+def importance_summary(result, *, importance=True):
+    """Importance-weighted posterior mean, variance, Monte Carlo standard error, effective sample size and per-run mass from ALL
+    candidates of a multipathfinder result -- not from the resampled `result.draws`, which only add resampling noise to the
+    estimator the PSIS weights already define.  The pool stays on the device: every engine of `result.engines` rebuilds its block of
+    the pool from the runs' stored (fit, draw_seed, ndraws_per_run) exactly as resample() does for stored draws, the pooled PSIS is
+    re-run, and two moment passes (Engine.pool_moments: about the origin, then about the mean) return 3 d numbers per run.  Across
+    runs only the host adds, in run order, so the summary is bit-identical for any number of engines.  importance=False, or a
+    result without psis_result: uniform weights.  Raises StaleHandleError when the engines hold newer fits."""
+    engs = result.engines or [result.engine]
+    runs = result.pathfinder_results
+    K = len(runs)
+    blocks = _blocks(K, len(engs))
+    for r in runs:
+        r.fit_distribution._live()                                  # the fits must still be the engine's current ones
+    npr = runs[0].ndraws_per_run
+    seeds = [r.draw_seed for r in runs]
+    for eng, (k0, k1) in zip(engs, blocks):
+        eng.pool_build(npr, [r.fit_distribution.point for r in runs[k0:k1]], seeds[k0:k1])
+    weighted = bool(importance) and result.psis_result is not None
+    pareto_shape = float("nan")
+    if weighted:                                                    # weights of the rebuilt pool, replicated on every engine
+        pareto_shape = _comm_for(engs).pool_psis()["pareto_shape"]
+
+    def moment_pass(center):
+        parts = [eng.pool_moments(k0 * npr, weighted, center) for eng, (k0, _) in zip(engs, blocks)]
+        return [[p[j] for p in parts] for j in range(4)]            # wsum, s1, s2, s2w: one block per engine each
+
+    wsum_b, s1_b, _, _ = moment_pass(None)
+    wtot = _combine_moments(wsum_b)                                 # (sum w, sum w^2) over all runs
+    W = wtot[0]
+    mean = _combine_moments(s1_b) / W
+    _, c1_b, c2_b, c2w_b = moment_pass(mean)
+    var = _combine_moments(c2_b) / W - (_combine_moments(c1_b) / W) ** 2
+    mcse = np.sqrt(_combine_moments(c2w_b)) / W
+    run_weights = np.concatenate([b[:, 0] for b in wsum_b]) / W
+    return ImportanceSummary(mean, var, np.sqrt(var), mcse, float(W * W / wtot[1]), run_weights, K * npr, pareto_shape)
 
 
 def _resample(rng, comm, psis, ndraws_per_component, ndraws, replace=True):

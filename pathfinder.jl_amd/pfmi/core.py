@@ -507,6 +507,22 @@ class Engine:
         check(self.L.pfmi_pool_get(self.ctx, _d(X), _d(lr)))
         return X, lr
 
+    def pool_moments(self, col_offset=0, importance=True, center=None):
+        """Weighted moments of this engine's pool, reduced on the device (include/pfmi.h pfmi_pool_moments): per local run k and
+        coordinate i, with t = x_i - center_i over the run's N_r draws, s1 = sum w t, s2 = sum w t^2, s2w = sum w^2 t^2 (each (K, d))
+        and wsum (K, 2) = (sum w, sum w^2).  importance=True: w are the engine's current PSIS weights of global pool columns
+        col_offset + k N_r + n (zero-weight columns are skipped); False: w = 1.  A run's rows have the same bits on whichever
+        engine owns the run."""
+        K, d = self.K, self.d
+        if center is not None:
+            center = np.ascontiguousarray(center, dtype=np.float64)
+            if center.shape != (d,):
+                raise ValueError(f"pool_moments: center must have shape ({d},)")
+        wsum = np.empty((K, 2))
+        s1, s2, s2w = np.empty((K, d)), np.empty((K, d)), np.empty((K, d))
+        check(self.L.pfmi_pool_moments(self.ctx, int(col_offset), int(bool(importance)), _d(center), _d(wsum), _d(s1), _d(s2), _d(s2w)))
+        return wsum, s1, s2, s2w
+
     def pool_log_ratios_dev(self):
         p, n = C.c_void_p(), C.c_int64()
         check(self.L.pfmi_pool_log_ratios_dev(self.ctx, C.byref(p), C.byref(n)))
