@@ -341,6 +341,28 @@ int32_t pfmi_pool_get(pfmi_ctx *ctx, double *draws, double *log_ratios);
  * col_offset < 0: PFMI_ERR_ARG. */
 int32_t pfmi_pool_moments(pfmi_ctx *ctx, int64_t col_offset, int32_t importance, const double *center, double *wsum, double *s1,
                           double *s2, double *s2w);
+/* Weighted empirical CDF of the pool on the device at nthr thresholds per coordinate, T[j*d + i] (1 <= nthr <= 32; any doubles,
+ * +-inf included).  Counted columns and their weights w are those of pfmi_pool_moments: importance != 0 takes the ctx's PSIS weight of
+ * global pool column col_offset + k*N_r + n and skips a column whose weight is exactly 0 whatever it holds; importance == 0 takes
+ * w = 1 and skips nothing.  Per threshold j and coordinate i, over the counted columns of the ctx's runs (any output may be NULL):
+ *   wle[j*d + i]   = sum of w over the columns with x_i <= T     below[j*d + i] = max of the x_i <= T, -inf if there is none
+ *   nanflag[i]     = 1 if a counted column holds a NaN in row i  above[j*d + i] = min of the x_i >  T, +inf if there is none
+ * A NaN compares false on both sides: it enters neither wle, below nor above.
+ * Ordering guarantee: no atomics; the terms of one run are added in an order that depends on (d, N_r) only, the runs are added in run
+ * order on top of wle_in[nthr*d] (NULL: zeros), which is added first.  So contexts chained in run order, each passing its wle to the
+ * next as wle_in, return the bits of one context that holds all the runs; below / above / nanflag of the parts combine exactly by
+ * max / min / or.
+ * THE QUANTILE built on it (pfmi.importance_quantiles): with U_i(v) = sum of w over the counted columns of the GLOBAL pool with
+ * x_i <= v and W the total counted weight, the weighted type-1 (inverted-CDF) quantile of coordinate i at probability p is the
+ * smallest pool value v of row i with U_i(v) >= p * W (that double product, formed once on the host); if no value satisfies it
+ * (rounding at p = 1) the largest counted value; NaN if nanflag[i] or W == 0.  Always an element of the pool, never an interpolation.
+ * No pool: PFMI_ERR_STATE; importance != 0 without a PSIS result covering [col_offset, col_offset + K*N_r): PFMI_ERR_STATE;
+ * col_offset < 0, nthr outside [1, 32] or thresholds NULL: PFMI_ERR_ARG. */
+int32_t pfmi_pool_cdf(pfmi_ctx *ctx, int64_t col_offset, int32_t importance, int32_t nthr, const double *thresholds,
+                      const double *wle_in, double *wle, double *below, double *above, int32_t *nanflag);
+/* device pointer to the local pool's draws (d x K_local*N_r doubles, column-major, a column per draw; count = their number), for hosts
+ * that keep the pool on the GPU.  The stream is idle on return.  Valid until the next pfmi_pool_build* on this ctx. */
+int32_t pfmi_pool_draws_dev(pfmi_ctx *ctx, void **dev_ptr, int64_t *count);
 /* device pointer to the local log-ratio shard (K_local * N_r doubles) for the RCCL all-gather */
 int32_t pfmi_pool_log_ratios_dev(pfmi_ctx *ctx, void **dev_ptr, int64_t *count);
 

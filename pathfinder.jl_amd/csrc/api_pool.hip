@@ -116,6 +116,40 @@ int32_t pfmi_pool_moments(pfmi_ctx *c, int64_t col_offset, int32_t importance, c
     return pf_stream_sync(c);
 }
 
+int32_t pfmi_pool_cdf(pfmi_ctx *c, int64_t col_offset, int32_t importance, int32_t nthr, const double *thresholds, const double *wle_in,
+                      double *wle, double *below, double *above, int32_t *nanflag) {
+    PF_CTX_MUT(c);
+    PF_CHECK(c->pooled, PFMI_ERR_STATE, "pool_cdf: call pfmi_pool_build first");
+    PF_CHECK(col_offset >= 0, PFMI_ERR_ARG, "pool_cdf: negative col_offset");
+    PF_CHECK(nthr >= 1 && nthr <= 32 && thresholds, PFMI_ERR_ARG, "pool_cdf: nthr must be in [1, 32] and thresholds non-NULL");
+    const size_t K = (size_t)c->K, plane = (size_t)nthr * (size_t)c->d;
+    PF_CHECK(!importance || (c->S_w > 0 && col_offset + (int64_t)K * c->N_r <= c->S_w), PFMI_ERR_STATE,
+             "pool_cdf: no PSIS weights for columns [%lld, %lld) on this ctx (run pfmi_psis / pfmi_comm_pool_psis first)",
+             (long long)col_offset, (long long)(col_offset + (int64_t)K * c->N_r));
+    PF_TRY(c->pcdf_thr.ensure(sizeof(double) * plane));
+    PF_TRY(pf_upload(c, c->pcdf_thr.p, thresholds, sizeof(double) * plane));
+    if (wle_in) {
+        PF_TRY(c->pcdf_carry.ensure(sizeof(double) * plane));
+        PF_TRY(pf_upload(c, c->pcdf_carry.p, wle_in, sizeof(double) * plane));
+    }
+    PF_TRY(pf_launch_pool_cdf(c, col_offset, importance, nthr, c->pcdf_thr.as<double>(), wle_in ? c->pcdf_carry.as<double>() : nullptr));
+    const double *o = c->pcdf.as<double>();
+    if (wle) PF_TRY(pf_download(c, wle, o, sizeof(double) * plane));
+    if (below) PF_TRY(pf_download(c, below, o + plane, sizeof(double) * plane));
+    if (above) PF_TRY(pf_download(c, above, o + 2 * plane, sizeof(double) * plane));
+    if (nanflag) PF_TRY(pf_download(c, nanflag, o + 3 * plane, sizeof(int32_t) * (size_t)c->d));
+    return pf_stream_sync(c);
+}
+
+int32_t pfmi_pool_draws_dev(pfmi_ctx *c, void **dev_ptr, int64_t *count) {
+    PF_CTX(c);
+    PF_CHECK(c->pooled, PFMI_ERR_STATE, "pool_draws_dev: call pfmi_pool_build first");
+    PF_HIP(hipStreamSynchronize(c->stream));
+    if (dev_ptr) *dev_ptr = c->pool.p;
+    if (count) *count = (int64_t)c->d * c->K * c->N_r;
+    return PFMI_OK;
+}
+
 int32_t pfmi_pool_log_ratios_dev(pfmi_ctx *c, void **dev_ptr, int64_t *count) {
     PF_CTX(c);
     PF_CHECK(c->pooled, PFMI_ERR_STATE, "pool_log_ratios_dev: call pfmi_pool_build first");

@@ -270,6 +270,10 @@ struct pfmi_ctx {
     DevBuf mom;                   // pfmi_pool_moments: [wsum K 2][s1 K d][s2 K d][s2w K d]
     DevBuf mom_part;              // its per-chunk partial sums (pool_moments_kernels.hip)
     DevBuf mom_center;            // its centre vector [d]
+    DevBuf pcdf;                   // pfmi_pool_cdf: [wle nthr d][below nthr d][above nthr d][nanflag d (int32)]
+    DevBuf pcdf_part;              // its per-chunk partial results (pool_cdf_kernels.hip)
+    DevBuf pcdf_thr;               // its thresholds [nthr d]
+    DevBuf pcdf_carry;             // its carry-in vector [nthr d]
 };
 
 // small host -> device upload on the ctx stream WITHOUT synchronising it (pinned arena); large blocks take the synchronous path
@@ -301,6 +305,8 @@ int32_t pf_launch_mixture_logpdf(pfmi_ctx *c, int K, const int32_t *d_points, in
 int32_t pf_launch_psis(pfmi_ctx *c, const double *d_lr, int64_t S);
 // weighted moments of the ctx's pool into c->mom (weights c->w + col_offset when importance != 0; d_center: device, d doubles or NULL)
 int32_t pf_launch_pool_moments(pfmi_ctx *c, int64_t col_offset, int importance, const double *d_center);
+// weighted CDF of the ctx's pool at nthr thresholds per row into c->pcdf (d_thr, d_carry: device, nthr d doubles; d_carry may be NULL)
+int32_t pf_launch_pool_cdf(pfmi_ctx *c, int64_t col_offset, int importance, int nthr, const double *d_thr, const double *d_carry);
 // Test / tuning hooks (kernel selection, the RCCL stand-in, ...): a value set with pfmi_debug_set(), or -- ONLY when the process was
 // started with PFMI_DEBUG_HOOKS=1 -- the environment variable of that name.  A production process therefore never has its numerics or
 // its dlopen path changed by a stray environment variable.  NULL when unset.

@@ -875,6 +875,20 @@ function _combine_moments(blocks)
     return total
 end
 
+"the preamble of the pooled summaries: every engine re-pools its runs, the pooled PSIS is re-run; (groups, N_r, weighted, k̂)"
+function _rebuild_pool(result::Pathfinder.MultiPathfinderResult, importance::Bool)
+    runs = result.pathfinder_results
+    groups = _mixture_blocks(result)
+    N_r = first(runs).ndraws
+    for (b, ks, pts) in groups
+        seeds = UInt64[runs[k].draw_seed for k in ks]
+        check(ccall((:pfmi_pool_build, libpfmi), Int32, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{UInt64}), b.eng.ptr, N_r, pts, seeds))
+    end
+    weighted = importance && result.psis_result !== nothing
+    k̂ = weighted ? pool_psis(comm_for(Engine[g[1].eng for g in groups]))[1] : NaN
+    return groups, N_r, weighted, k̂
+end
+
 """
     importance_summary(result::Pathfinder.MultiPathfinderResult; importance=true)
 
@@ -885,14 +899,7 @@ device; only the host adds across runs, in run order, so the summary does not de
 """
 function importance_summary(result::Pathfinder.MultiPathfinderResult; importance::Bool=true)
     runs = result.pathfinder_results
-    groups = _mixture_blocks(result)
-    N_r = first(runs).ndraws
-    for (b, ks, pts) in groups
-        seeds = UInt64[runs[k].draw_seed for k in ks]
-        check(ccall((:pfmi_pool_build, libpfmi), Int32, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{UInt64}), b.eng.ptr, N_r, pts, seeds))
-    end
-    weighted = importance && result.psis_result !== nothing
-    k̂ = weighted ? pool_psis(comm_for(Engine[g[1].eng for g in groups]))[1] : NaN
+    groups, N_r, weighted, k̂ = _rebuild_pool(result, importance)
     pass(center) = [pool_moments(b, length(ks); col_offset=(first(ks) - 1) * N_r, importance=weighted, center) for (b, ks, _) in groups]
     p1 = pass(nothing)
     wtot = _combine_moments([p[1] for p in p1])
@@ -904,6 +911,124 @@ function importance_summary(result::Pathfinder.MultiPathfinderResult; importance
     run_weights = reduce(vcat, [p[1][1, :] for p in p1]) ./ W
     return (mean=μ, var=v, std=sqrt.(v), mcse_mean=mcse, ess=W^2 / wtot[2], run_weights=run_weights,
             ncandidates=length(runs) * N_r, pareto_shape=k̂)
+end
+
+# ---- importance-weighted quantiles from the pooled candidates (pfmi_pool_cdf; definition: include/pfmi.h) -------------------------------
+"""
+    pool_cdf(b::Batch, thresholds; col_offset=0, importance=true, carry=nothing) -> (wle, below, above, nanflag)
+
+Weighted empirical CDF of the engine's pool at `thresholds` (d x nthr, 1 <= nthr <= 32) in one pass on the device.  `carry`
+(d x nthr): the `wle` of the engines that own the earlier runs, added first.
+"""
+function pool_cdf(b::Batch, thresholds::Matrix{Float64}; col_offset::Integer=0, importance::Bool=true,
+                  carry::Union{Nothing,Matrix{Float64}}=nothing)
+    _live(b.eng, b.gen)
+    size(thresholds, 1) == b.dim || throw(ArgumentError("pool_cdf: thresholds must be d x nthr"))
+    carry === nothing || size(carry) == size(thresholds) || throw(ArgumentError("pool_cdf: carry must have the size of thresholds"))
+    nthr = size(thresholds, 2)
+    wle = similar(thresholds); below = similar(thresholds); above = similar(thresholds)
+    nanflag = Vector{Int32}(undef, b.dim)
+    check(ccall((:pfmi_pool_cdf, libpfmi), Int32,
+                (Ptr{Cvoid}, Int64, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+                b.eng.ptr, col_offset, importance, nthr, thresholds, carry === nothing ? Ptr{Float64}(C_NULL) : pointer(carry),
+                wle, below, above, nanflag))
+    return wle, below, above, nanflag
+end
+
+"order-preserving map of doubles onto UInt64 and its inverse"
+_f64_key(x::Float64) = (b = reinterpret(UInt64, x); (b >> 63) == 1 ? ~b : b | (UInt64(1) << 63))
+_f64_unkey(k::UInt64) = reinterpret(Float64, (k >> 63) == 1 ? k & ((UInt64(1) << 63) - 1) : ~k)
+_quantile_pass_cap(B::Int) = 2 + ceil(Int, 64 / log2(B))
+function _key_passes_needed(diff::UInt64, B::Int)
+    need = 1
+    while diff > B
+        diff = cld(diff, UInt64(B)); need += 1
+    end
+    return need
+end
+
+"the bracket search of pfmi/api.py `_quantile_search`: `cdf_pass(T)` (T: d x nthr) -> (wle, below, above, nanflag) of the whole pool"
+function _quantile_search(cdf_pass, d::Int, targets::Vector{Float64}, B::Int)
+    nq = length(targets); cap = _quantile_pass_cap(B)
+    wle, below, above, nanflag = cdf_pass(hcat(fill(-Inf, d), fill(Inf, d)))
+    passes = 1
+    total = wle[:, 2]
+    hi = repeat(below[:, 2], 1, nq); lo = repeat(above[:, 1], 1, nq)
+    done = falses(d, nq)
+    for a in 1:nq, i in 1:d
+        if wle[i, 1] >= targets[a] && wle[i, 1] > 0
+            hi[i, a] = -Inf; done[i, a] = true
+        end
+        done[i, a] |= total[i] < targets[a] || lo[i, a] == hi[i, a] || !(total[i] > 0)
+    end
+    while !all(done)
+        passes < cap || error("quantile search did not close within $cap passes")
+        T = Matrix{Float64}(undef, d, nq * B)
+        for a in 1:nq, i in 1:d
+            l, h = lo[i, a], hi[i, a]
+            diff = done[i, a] ? UInt64(0) : _f64_key(h) - _f64_key(l)
+            by_key = _key_passes_needed(diff, B) > cap - passes - 1 || !isfinite(l) || !isfinite(h)
+            step = cld(diff, UInt64(B))
+            for m in 0:B-1
+                t = by_key ? _f64_unkey(_f64_key(l) + min(UInt64(m) * step, max(diff, UInt64(1)) - 1)) : l + (h - l) * (m / B)
+                T[i, (a - 1) * B + m + 1] = (t >= l && t < h) ? t : l
+            end
+        end
+        wle, below, above, nf = cdf_pass(T)
+        passes += 1
+        nanflag = nanflag .| nf
+        for a in 1:nq, i in 1:d
+            done[i, a] && continue
+            for m in 1:B
+                c = (a - 1) * B + m
+                if wle[i, c] >= targets[a] && wle[i, c] > 0
+                    hi[i, a] = min(hi[i, a], below[i, c])
+                else
+                    lo[i, a] = max(lo[i, a], above[i, c])
+                end
+            end
+            done[i, a] = lo[i, a] == hi[i, a]
+        end
+    end
+    q = copy(hi)
+    for i in 1:d
+        (nanflag[i] != 0 || !(total[i] > 0)) && (q[i, :] .= NaN)
+    end
+    return q, passes
+end
+
+"""
+    importance_quantiles(result::Pathfinder.MultiPathfinderResult, probs=[0.025, 0.25, 0.5, 0.75, 0.975]; importance=true)
+
+Returns `(q, passes)`: the weighted type-1 (inverted-CDF) quantiles of every coordinate from ALL pooled candidates under their PSIS
+weights as a d x length(probs) matrix (column-major, the transpose of the Python array), and the number of CDF passes.  The pool
+stays on the device; every pass is one `pool_cdf` per engine, chained in run order.  Probabilities are searched in groups of at
+most `thresholds_per_pass ÷ 4`, as in pfmi/api.py, so any number of them may be given.
+"""
+function importance_quantiles(result::Pathfinder.MultiPathfinderResult, probs::Vector{Float64}=[0.025, 0.25, 0.5, 0.75, 0.975];
+                              importance::Bool=true, thresholds_per_pass::Int=32)
+    groups, N_r, weighted, _ = _rebuild_pool(result, importance)
+    W = _combine_moments([pool_moments(b, length(ks); col_offset=(first(ks) - 1) * N_r, importance=weighted)[1] for (b, ks, _) in groups])[1]
+    function cdf_pass(T)
+        wle = nothing; below = nothing; above = nothing; nan = nothing
+        for (b, ks, _) in groups
+            w, lo, hi, f = pool_cdf(b, T; col_offset=(first(ks) - 1) * N_r, importance=weighted, carry=wle)
+            wle = w
+            below = below === nothing ? lo : max.(below, lo)
+            above = above === nothing ? hi : min.(above, hi)
+            nan = nan === nothing ? f : nan .| f
+        end
+        return wle, below, above, nan
+    end
+    d = first(groups)[1].dim
+    group = max(1, thresholds_per_pass ÷ 4)
+    qs = Matrix{Float64}[]; passes = 0
+    for g0 in 1:group:length(probs)
+        p = probs[g0:min(g0 + group - 1, length(probs))]
+        q, n = _quantile_search(cdf_pass, d, p .* W, max(2, thresholds_per_pass ÷ length(p)))
+        push!(qs, q); passes += n
+    end
+    return reduce(hcat, qs), passes
 end
 
 # ---- multi-GPU collectives (the `Comm` type itself is defined next to `Engine`) ---------------------------------------------------------

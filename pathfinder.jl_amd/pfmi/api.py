@@ -372,6 +372,11 @@ class MultiPathfinderResult:        # src/multipath.jl:31-44
         """importance-weighted posterior summaries from ALL pooled candidates, reduced on the device: importance_summary(self)"""
         return importance_summary(self, importance=importance)
 
+    def quantiles(self, probs=(0.025, 0.25, 0.5, 0.75, 0.975), importance=True):
+        """importance-weighted quantiles (len(probs), d) from ALL pooled candidates, searched on the device:
+        importance_quantiles(self, probs)"""
+        return importance_quantiles(self, probs, importance=importance)
+
     def __str__(self):                  # Base.show, src/multipath.jl:46-65
         lines = ["Multi-path Pathfinder result", f"  runs: {len(self.pathfinder_results)}", f"  draws: {self.draws.shape[1]}"]
         if self.psis_result is not None:
@@ -934,14 +939,10 @@ def _combine_moments(blocks):
     return total
 
 
-def importance_summary(result, *, importance=True):
-    """Importance-weighted posterior mean, variance, Monte Carlo standard error, effective sample size and per-run mass from ALL
-    candidates of a multipathfinder result -- not from the resampled `result.draws`, which only add resampling noise to the
-    estimator the PSIS weights already define.  The pool stays on the device: every engine of `result.engines` rebuilds its block of
-    the pool from the runs' stored (fit, draw_seed, ndraws_per_run) exactly as resample() does for stored draws, the pooled PSIS is
-    re-run, and two moment passes (Engine.pool_moments: about the origin, then about the mean) return 3 d numbers per run.  Across
-    runs only the host adds, in run order, so the summary is bit-identical for any number of engines.  importance=False, or a
-    result without psis_result: uniform weights.  Raises StaleHandleError when the engines hold newer fits."""
+def _rebuild_pool(result, importance):
+    """The preamble of the pooled summaries: every engine of `result` rebuilds its block of the pool from the runs' stored
+    (fit, draw_seed, ndraws_per_run) and, with importance weighting, the pooled PSIS is re-run so that every engine holds the weights
+    of the global pool.  Returns (engines, run blocks, ndraws_per_run, weighted, pareto_shape)."""
     engs = result.engines or [result.engine]
     runs = result.pathfinder_results
     K = len(runs)
@@ -956,6 +957,19 @@ def importance_summary(result, *, importance=True):
     pareto_shape = float("nan")
     if weighted:                                                    # weights of the rebuilt pool, replicated on every engine
         pareto_shape = _comm_for(engs).pool_psis()["pareto_shape"]
+    return engs, blocks, npr, weighted, pareto_shape
+
+
+def importance_summary(result, *, importance=True):
+    """Importance-weighted posterior mean, variance, Monte Carlo standard error, effective sample size and per-run mass from ALL
+    candidates of a multipathfinder result -- not from the resampled `result.draws`, which only add resampling noise to the
+    estimator the PSIS weights already define.  The pool stays on the device: every engine of `result.engines` rebuilds its block of
+    the pool from the runs' stored (fit, draw_seed, ndraws_per_run) exactly as resample() does for stored draws, the pooled PSIS is
+    re-run, and two moment passes (Engine.pool_moments: about the origin, then about the mean) return 3 d numbers per run.  Across
+    runs only the host adds, in run order, so the summary is bit-identical for any number of engines.  importance=False, or a
+    result without psis_result: uniform weights.  Raises StaleHandleError when the engines hold newer fits."""
+    engs, blocks, npr, weighted, pareto_shape = _rebuild_pool(result, importance)
+    K = len(result.pathfinder_results)
 
     def moment_pass(center):
         parts = [eng.pool_moments(k0 * npr, weighted, center) for eng, (k0, _) in zip(engs, blocks)]
@@ -970,6 +984,134 @@ def importance_summary(result, *, importance=True):
     mcse = np.sqrt(_combine_moments(c2w_b)) / W
     run_weights = np.concatenate([b[:, 0] for b in wsum_b]) / W
     return ImportanceSummary(mean, var, np.sqrt(var), mcse, float(W * W / wtot[1]), run_weights, K * npr, pareto_shape)
+
+
+def _f64_key(x):
+    """order-preserving map of doubles onto uint64: x < y implies key(x) < key(y) (-0.0 sorts just below +0.0)"""
+    b = np.ascontiguousarray(x, dtype=np.float64).view(np.uint64)
+    neg = (b >> np.uint64(63)).astype(bool)
+    return np.where(neg, ~b, b | np.uint64(1 << 63))
+
+
+def _f64_unkey(k):
+    """inverse of _f64_key"""
+    k = np.ascontiguousarray(k, dtype=np.uint64)
+    top = (k >> np.uint64(63)).astype(bool)
+    return np.where(top, k & np.uint64((1 << 63) - 1), ~k).view(np.float64)
+
+
+def _quantile_pass_cap(B):
+    """hard cap on the passes of _quantile_search with B thresholds per probability: the pass at +-inf, then key splitting alone
+    divides the at most 2^64 keys of a bracket by B per pass and the last pass tests the remaining keys one by one"""
+    return 2 + int(np.ceil(64.0 / np.log2(B)))
+
+
+def _key_passes_needed(diff, B):
+    """passes of key splitting that certainly close a bracket of `diff` keys (uint64 array): a pass leaves fewer than ceil(diff / B)
+    keys, and at most B keys are tested one by one"""
+    diff = diff.copy()
+    Bu = np.uint64(B)
+    need = np.ones(diff.shape, dtype=np.int64)
+    while True:
+        big = diff > Bu
+        if not big.any():
+            return need
+        diff = np.where(big, diff // Bu + (diff % Bu != 0).astype(np.uint64), diff)
+        need += big
+
+
+def _quantile_search(cdf_pass, d, targets, B):
+    """The bracket search of the weighted type-1 quantiles (definition: include/pfmi.h, pfmi_pool_cdf) on top of a CDF primitive.
+    cdf_pass(T) takes thresholds (nthr, d) and returns (wle, below, above, nanflag) of the whole pool; targets (nq,) holds p * W per
+    probability; every pass evaluates B thresholds per probability (nq * B <= 32).  Per (probability, coordinate) the bracket is
+    (lo, hi]: lo = the smallest pool value above a threshold with U < p W, hi = a pool value with U >= p W; it is closed when
+    lo == hi, the only pool value left.  Thresholds split [lo, hi) evenly in value space as long as the bracket, were it to make no
+    progress, could still be closed by key splitting within the cap; otherwise they split the order-preserving keys.
+    Returns (quantiles (nq, d), passes)."""
+    targets = np.asarray(targets, dtype=np.float64)
+    nq = targets.shape[0]
+    cap = _quantile_pass_cap(B)
+    t = targets[:, None]
+    wle, below, above, nanflag = cdf_pass(np.stack([np.full(d, -np.inf), np.full(d, np.inf)]))
+    passes = 1
+    total, vmax = wle[1], below[1]
+    # no value reaches p W (rounding at p = 1): the largest counted value; pool values of -inf that reach it: -inf
+    hi = np.broadcast_to(vmax, (nq, d)).copy()
+    lo = np.broadcast_to(above[0], (nq, d)).copy()
+    done = (total[None, :] < t) | ((wle[0][None, :] >= t) & (wle[0][None, :] > 0))
+    hi[(wle[0][None, :] >= t) & (wle[0][None, :] > 0)] = -np.inf
+    done |= (lo == hi) | ~(total > 0)[None, :]                      # (no counted weight: NaN below)
+    frac = (np.arange(B, dtype=np.float64) / B)[None, :, None]
+    steps = np.arange(B, dtype=np.uint64)[None, :, None]
+    while not done.all():
+        if passes >= cap:
+            raise RuntimeError(f"quantile search did not close within {cap} passes")       # (unreachable: see _quantile_pass_cap)
+        klo, khi = _f64_key(lo), _f64_key(hi)
+        diff = np.where(done, np.uint64(0), khi - klo)
+        by_key = (_key_passes_needed(diff, B) > cap - passes - 1) | ~np.isfinite(lo) | ~np.isfinite(hi)
+        with np.errstate(over="ignore", invalid="ignore"):
+            Tv = lo[:, None, :] + (hi - lo)[:, None, :] * frac
+        step = diff // np.uint64(B) + (diff % np.uint64(B) != 0).astype(np.uint64)
+        off = np.minimum(steps * step[:, None, :], np.maximum(diff, np.uint64(1))[:, None, :] - np.uint64(1))
+        Tk = _f64_unkey(klo[:, None, :] + off)
+        T = np.where(by_key[:, None, :], Tk, Tv)
+        T = np.where((T >= lo[:, None, :]) & (T < hi[:, None, :]), T, lo[:, None, :])       # (a closed bracket repeats its value)
+        wle, below, above, nf = cdf_pass(T.reshape(nq * B, d))
+        passes += 1
+        nanflag = nanflag | nf
+        wle, below, above = wle.reshape(nq, B, d), below.reshape(nq, B, d), above.reshape(nq, B, d)
+        up = (wle >= t[:, :, None]) & (wle > 0)
+        hi_new = np.minimum(hi, np.min(np.where(up, below, np.inf), axis=1))
+        lo_new = np.maximum(lo, np.max(np.where(up, -np.inf, above), axis=1))
+        hi, lo = np.where(done, hi, hi_new), np.where(done, lo, lo_new)
+        done |= lo == hi
+    q = hi.copy()
+    q[:, (nanflag != 0) | ~(total > 0)] = np.nan
+    return q, passes
+
+
+CDF_THRESHOLDS_PER_PASS = 32        # thresholds of one pool_cdf call (profiles/pool_quantiles.md)
+
+
+def importance_quantiles(result, probs=(0.025, 0.25, 0.5, 0.75, 0.975), *, importance=True, return_passes=False):
+    """Importance-weighted quantiles of every coordinate from ALL candidates of a multipathfinder result: a (len(probs), d) array of
+    the weighted type-1 (inverted-CDF) quantiles defined in include/pfmi.h (pfmi_pool_cdf) -- each an element of the pool, never an
+    interpolation; NaN for a coordinate with a counted NaN or when the total weight is 0.  The pool is rebuilt and weighted as in
+    importance_summary and stays on the device: W comes from one moment pass, then every pass of the bracket search
+    (_quantile_search) is one Engine.pool_cdf call per engine, the engines chained in run order through the carry, so the result
+    is bit-identical for any number of engines.  importance=False, or a result without psis_result: uniform weights (then equal to
+    np.quantile(pool, probs, method="inverted_cdf")).  return_passes=True: also the number of CDF passes over the pool."""
+    probs = np.atleast_1d(np.asarray(probs, dtype=np.float64))
+    if probs.ndim != 1 or probs.size == 0 or not np.all((probs >= 0) & (probs <= 1)):
+        raise ValueError("importance_quantiles: probs must be a non-empty sequence of numbers in [0, 1]")
+    engs, blocks, npr, weighted, _ = _rebuild_pool(result, importance)
+    q, passes = _quantiles_of_pool(engs, blocks, npr, weighted, probs)
+    return (q, passes) if return_passes else q
+
+
+def _quantiles_of_pool(engs, blocks, npr, weighted, probs):
+    """importance_quantiles after its preamble: the quantiles of the pool the engines hold now, (q, passes)"""
+    d = engs[0].d
+    W = _combine_moments([eng.pool_moments(k0 * npr, weighted, None)[0] for eng, (k0, _) in zip(engs, blocks)])[0]
+
+    def cdf_pass(T):
+        wle, below, above, nan = None, None, None, None
+        for eng, (k0, _) in zip(engs, blocks):
+            w, b, a, f = eng.pool_cdf(k0 * npr, weighted, T, wle)
+            wle = w                                                 # the carry of the next engine
+            below = b if below is None else np.maximum(below, b)
+            above = a if above is None else np.minimum(above, a)
+            nan = f if nan is None else nan | f
+        return wle, below, above, nan
+
+    group = max(1, CDF_THRESHOLDS_PER_PASS // 4)                     # at least 4 thresholds per probability
+    out, passes = [], 0
+    for g0 in range(0, probs.size, group):
+        p = probs[g0:g0 + group]
+        q, n = _quantile_search(cdf_pass, d, p * W, max(2, CDF_THRESHOLDS_PER_PASS // p.size))
+        out.append(q)
+        passes += n
+    return np.concatenate(out, axis=0), passes
 
 
 def _resample(rng, comm, psis, ndraws_per_component, ndraws, replace=True):

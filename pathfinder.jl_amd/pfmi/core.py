@@ -523,6 +523,32 @@ class Engine:
         check(self.L.pfmi_pool_moments(self.ctx, int(col_offset), int(bool(importance)), _d(center), _d(wsum), _d(s1), _d(s2), _d(s2w)))
         return wsum, s1, s2, s2w
 
+    def pool_cdf(self, col_offset, importance, thresholds, carry=None):
+        """Weighted empirical CDF of this engine's pool at thresholds (nthr, d), 1 <= nthr <= 32, in one pass on the device
+        (include/pfmi.h pfmi_pool_cdf): returns (wle, below, above, nanflag), the first three (nthr, d), nanflag (d,) int32.
+        carry (nthr, d): the wle of the engines that own the earlier runs, added first; chaining engines in run order gives the bits
+        of one engine that holds all the runs."""
+        d = self.d
+        thresholds = np.ascontiguousarray(thresholds, dtype=np.float64)
+        if thresholds.ndim != 2 or thresholds.shape[1] != d:
+            raise ValueError(f"pool_cdf: thresholds must have shape (nthr, {d})")
+        nthr = thresholds.shape[0]
+        if carry is not None:
+            carry = np.ascontiguousarray(carry, dtype=np.float64)
+            if carry.shape != (nthr, d):
+                raise ValueError(f"pool_cdf: carry must have shape ({nthr}, {d})")
+        wle, below, above = np.empty((nthr, d)), np.empty((nthr, d)), np.empty((nthr, d))
+        nanflag = np.empty(d, dtype=np.int32)
+        check(self.L.pfmi_pool_cdf(self.ctx, int(col_offset), int(bool(importance)), nthr, _d(thresholds), _d(carry), _d(wle), _d(below),
+                                   _d(above), nanflag.ctypes.data_as(C.POINTER(C.c_int32))))
+        return wle, below, above, nanflag
+
+    def pool_draws_dev(self):
+        """(device pointer, count) of this engine's pool draws: d x K N_r doubles, column-major (pfmi_pool_draws_dev)"""
+        p, n = C.c_void_p(), C.c_int64()
+        check(self.L.pfmi_pool_draws_dev(self.ctx, C.byref(p), C.byref(n)))
+        return p.value, n.value
+
     def pool_log_ratios_dev(self):
         p, n = C.c_void_p(), C.c_int64()
         check(self.L.pfmi_pool_log_ratios_dev(self.ctx, C.byref(p), C.byref(n)))
