@@ -360,6 +360,22 @@ int32_t pfmi_pool_moments(pfmi_ctx *ctx, int64_t col_offset, int32_t importance,
  * col_offset < 0, nthr outside [1, 32] or thresholds NULL: PFMI_ERR_ARG. */
 int32_t pfmi_pool_cdf(pfmi_ctx *ctx, int64_t col_offset, int32_t importance, int32_t nthr, const double *thresholds,
                       const double *wle_in, double *wle, double *below, double *above, int32_t *nanflag);
+/* Weighted cross moments of the pool on the device: the d x d matrix C, row i at c_out + i*d.  With t_i = x_i - center[i] (center NULL:
+ * 0), over the N_r draws n of the ctx's runs k and for i >= j:
+ *   C[i][j] = c_in[i*d + j] + sum_k (in run order) sum_n (w t_i) t_j              (c_in NULL: zeros)
+ * each term being fl(w * fl(x_i - center[i])) times fl(x_j - center[j]), accumulated by a fused multiply-add.  Columns and weights w
+ * are those of pfmi_pool_moments: importance != 0 takes the ctx's PSIS weight of global pool column col_offset + k*N_r + n and skips a
+ * column whose weight is exactly 0 whatever it holds (a non-finite draw there contributes nothing); importance == 0 takes w = 1 and
+ * skips nothing.  A NaN in row r of a counted column makes exactly row r and column r of C NaN.
+ * Symmetry guarantee: only entries with i >= j are computed (and only those of c_in are read); C[j][i] is written as a copy of C[i][j],
+ * so the two triangles have the same bits ((w t_i) t_j and (w t_j) t_i round differently).
+ * Ordering guarantee: no atomics; the terms of one run are added in an order that depends on (d, N_r) only -- not on K, col_offset, the
+ * run's position or the device; the runs are added in run order on top of c_in, which is added first.  So contexts chained in run order,
+ * each passing its c_out to the next as c_in, return the bits of one context that holds all the runs.
+ * d is not capped (entries are addressed with size_t); the device buffer of d*d doubles failing to allocate: PFMI_ERR_HIP.
+ * No pool: PFMI_ERR_STATE; importance != 0 without a PSIS result covering [col_offset, col_offset + K*N_r): PFMI_ERR_STATE;
+ * col_offset < 0 or c_out NULL: PFMI_ERR_ARG. */
+int32_t pfmi_pool_cross(pfmi_ctx *ctx, int64_t col_offset, int32_t importance, const double *center, const double *c_in, double *c_out);
 /* device pointer to the local pool's draws (d x K_local*N_r doubles, column-major, a column per draw; count = their number), for hosts
  * that keep the pool on the GPU.  The stream is idle on return.  Valid until the next pfmi_pool_build* on this ctx. */
 int32_t pfmi_pool_draws_dev(pfmi_ctx *ctx, void **dev_ptr, int64_t *count);

@@ -141,6 +141,26 @@ int32_t pfmi_pool_cdf(pfmi_ctx *c, int64_t col_offset, int32_t importance, int32
     return pf_stream_sync(c);
 }
 
+int32_t pfmi_pool_cross(pfmi_ctx *c, int64_t col_offset, int32_t importance, const double *center, const double *c_in, double *c_out) {
+    PF_CTX_MUT(c);
+    PF_CHECK(c->pooled, PFMI_ERR_STATE, "pool_cross: call pfmi_pool_build first");
+    PF_CHECK(col_offset >= 0 && c_out, PFMI_ERR_ARG, "pool_cross: negative col_offset or NULL c_out");
+    const size_t K = (size_t)c->K, d = (size_t)c->d;
+    PF_CHECK(!importance || (c->S_w > 0 && col_offset + (int64_t)K * c->N_r <= c->S_w), PFMI_ERR_STATE,
+             "pool_cross: no PSIS weights for columns [%lld, %lld) on this ctx (run pfmi_psis / pfmi_comm_pool_psis first)",
+             (long long)col_offset, (long long)(col_offset + (int64_t)K * c->N_r));
+    if (center) {
+        PF_TRY(c->cross_center.ensure(sizeof(double) * d));
+        PF_TRY(pf_upload(c, c->cross_center.p, center, sizeof(double) * d));
+    }
+    PF_TRY(c->cross.ensure(sizeof(double) * d * d));
+    if (c_in) PF_TRY(pf_upload(c, c->cross.p, c_in, sizeof(double) * d * d));      // accumulated in place
+    PF_TRY(pf_launch_pool_cross(c, col_offset, importance, center ? c->cross_center.as<double>() : nullptr,
+                                c_in ? c->cross.as<double>() : nullptr));
+    PF_TRY(pf_download(c, c_out, c->cross.p, sizeof(double) * d * d));
+    return pf_stream_sync(c);
+}
+
 int32_t pfmi_pool_draws_dev(pfmi_ctx *c, void **dev_ptr, int64_t *count) {
     PF_CTX(c);
     PF_CHECK(c->pooled, PFMI_ERR_STATE, "pool_draws_dev: call pfmi_pool_build first");

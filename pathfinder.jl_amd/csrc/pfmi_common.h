@@ -274,6 +274,8 @@ struct pfmi_ctx {
     DevBuf pcdf_part;              // its per-chunk partial results (pool_cdf_kernels.hip)
     DevBuf pcdf_thr;               // its thresholds [nthr d]
     DevBuf pcdf_carry;             // its carry-in vector [nthr d]
+    DevBuf cross;                  // pfmi_pool_cross: C [d d], both triangles (a carry-in is uploaded here and accumulated in place)
+    DevBuf cross_center;           // its centre vector [d]
 };
 
 // small host -> device upload on the ctx stream WITHOUT synchronising it (pinned arena); large blocks take the synchronous path
@@ -307,6 +309,9 @@ int32_t pf_launch_psis(pfmi_ctx *c, const double *d_lr, int64_t S);
 int32_t pf_launch_pool_moments(pfmi_ctx *c, int64_t col_offset, int importance, const double *d_center);
 // weighted CDF of the ctx's pool at nthr thresholds per row into c->pcdf (d_thr, d_carry: device, nthr d doubles; d_carry may be NULL)
 int32_t pf_launch_pool_cdf(pfmi_ctx *c, int64_t col_offset, int importance, int nthr, const double *d_thr, const double *d_carry);
+// weighted cross moments of the ctx's pool into c->cross (d_center: device, d doubles or NULL; d_carry: device, d d doubles -- it may be
+// c->cross itself -- or NULL for zeros)
+int32_t pf_launch_pool_cross(pfmi_ctx *c, int64_t col_offset, int importance, const double *d_center, const double *d_carry);
 // Test / tuning hooks (kernel selection, the RCCL stand-in, ...): a value set with pfmi_debug_set(), or -- ONLY when the process was
 // started with PFMI_DEBUG_HOOKS=1 -- the environment variable of that name.  A production process therefore never has its numerics or
 // its dlopen path changed by a stray environment variable.  NULL when unset.

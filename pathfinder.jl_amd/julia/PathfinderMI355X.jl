@@ -1031,6 +1031,60 @@ function importance_quantiles(result::Pathfinder.MultiPathfinderResult, probs::V
     return reduce(hcat, qs), passes
 end
 
+# ---- importance-weighted covariance from the pooled candidates (pfmi_pool_cross; definition: include/pfmi.h) ----------------------------
+"""
+    pool_cross(b::Batch; col_offset=0, importance=true, center=nothing, carry=nothing) -> C (d x d)
+
+Weighted cross moments of the engine's pool in one pass on the device: C = carry + Σ (w t) t' with t = x - center, the runs added in
+run order on top of `carry` (the C of the engines that own the earlier runs).  Only one triangle is computed and the other is its
+copy, so C is symmetric bit for bit (and the row-major matrix of the C ABI is this column-major one).
+"""
+function pool_cross(b::Batch; col_offset::Integer=0, importance::Bool=true, center::Union{Nothing,Vector{Float64}}=nothing,
+                    carry::Union{Nothing,Matrix{Float64}}=nothing)
+    _live(b.eng, b.gen)
+    center === nothing || length(center) == b.dim || throw(ArgumentError("pool_cross: center must have length d"))
+    carry === nothing || size(carry) == (b.dim, b.dim) || throw(ArgumentError("pool_cross: carry must be d x d"))
+    # (the C side reads c_in[i*d + j] for i >= j only, the upper triangle of this column-major `carry`: a symmetric carry, such as an
+    # earlier result, is read as itself)
+    C = Matrix{Float64}(undef, b.dim, b.dim)
+    check(ccall((:pfmi_pool_cross, libpfmi), Int32,
+                (Ptr{Cvoid}, Int64, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                b.eng.ptr, col_offset, importance, center === nothing ? Ptr{Float64}(C_NULL) : pointer(center),
+                carry === nothing ? Ptr{Float64}(C_NULL) : pointer(carry), C))
+    return C
+end
+
+"""
+    importance_covariance(result::Pathfinder.MultiPathfinderResult; importance=true)
+
+Posterior `mean`, `cov`, `corr`, `ess`, `ncandidates` and `pareto_shape` from ALL pooled candidates under their PSIS weights (uniform
+weights with `importance=false` or without a `psis_result`): two moment passes give W, the mean and the centred first moment δ, one
+`pool_cross` pass per engine about the mean, chained in run order through the carry, gives C; cov = C / W - δ δ'.  The host only
+forwards the carry across engines, so the result does not depend on their number.
+"""
+function importance_covariance(result::Pathfinder.MultiPathfinderResult; importance::Bool=true)
+    runs = result.pathfinder_results
+    groups, N_r, weighted, k̂ = _rebuild_pool(result, importance)
+    pass(center) = [pool_moments(b, length(ks); col_offset=(first(ks) - 1) * N_r, importance=weighted, center) for (b, ks, _) in groups]
+    p1 = pass(nothing)
+    wtot = _combine_moments([p[1] for p in p1])
+    W = wtot[1]
+    μ = _combine_moments([p[2] for p in p1]) ./ W
+    δ = _combine_moments([p[2] for p in pass(μ)]) ./ W
+    C = nothing
+    for (b, ks, _) in groups
+        C = pool_cross(b; col_offset=(first(ks) - 1) * N_r, importance=weighted, center=μ, carry=C)
+    end
+    Σ = C ./ W .- δ .* δ'
+    v = [Σ[i, i] for i in axes(Σ, 1)]
+    sd = [x > 0 ? sqrt(x) : NaN for x in v]
+    R = Σ ./ (sd .* sd')
+    for i in axes(R, 1)
+        R[i, i] = v[i] > 0 ? 1.0 : NaN
+    end
+    return (mean=μ, cov=Σ, corr=R, ess=W^2 / wtot[2], ncandidates=length(runs) * N_r, pareto_shape=k̂)
+end
+
 # ---- multi-GPU collectives (the `Comm` type itself is defined next to `Engine`) ---------------------------------------------------------
 """
     psis_resample(c, dim, ndraws; importance, replace, seed) -> (pareto_shape, tail_length, idx0, draws)

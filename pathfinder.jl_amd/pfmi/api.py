@@ -377,6 +377,15 @@ class MultiPathfinderResult:        # src/multipath.jl:31-44
         importance_quantiles(self, probs)"""
         return importance_quantiles(self, probs, importance=importance)
 
+    def covariance(self, importance=True):
+        """importance-weighted posterior covariance (with mean and correlation) from ALL pooled candidates, reduced on the device:
+        importance_covariance(self)"""
+        return importance_covariance(self, importance=importance)
+
+    def correlation(self, importance=True):
+        """the (d, d) correlation matrix of covariance(): importance_covariance(self).corr"""
+        return importance_covariance(self, importance=importance).corr
+
     def __str__(self):                  # Base.show, src/multipath.jl:46-65
         lines = ["Multi-path Pathfinder result", f"  runs: {len(self.pathfinder_results)}", f"  draws: {self.draws.shape[1]}"]
         if self.psis_result is not None:
@@ -984,6 +993,59 @@ def importance_summary(result, *, importance=True):
     mcse = np.sqrt(_combine_moments(c2w_b)) / W
     run_weights = np.concatenate([b[:, 0] for b in wsum_b]) / W
     return ImportanceSummary(mean, var, np.sqrt(var), mcse, float(W * W / wtot[1]), run_weights, K * npr, pareto_shape)
+
+
+@dataclass
+class ImportanceCovariance:
+    """Posterior covariance from the S = nruns * ndraws_per_run pooled candidates under their PSIS weights (importance_covariance)."""
+    mean: np.ndarray                # (d,) sum w x / W
+    cov: np.ndarray                 # (d, d) sum w (x - mean)(x - mean)' / W, symmetric bit for bit; its diagonal is ImportanceSummary.var
+    corr: np.ndarray                # (d, d) cov / sqrt(diag x diag), unit diagonal; NaN rows and columns where var <= 0
+    ess: float                      # W^2 / sum w^2
+    ncandidates: int                # S
+    pareto_shape: float             # k-hat of the pooled PSIS (NaN for uniform weights)
+
+
+def _covariance_from_sums(C, c1, W):
+    """(cov, corr) from the cross moments C about the mean, the centred first moments c1 and the total weight W:
+    cov = C / W - delta delta' with delta = c1 / W -- on the diagonal exactly importance_summary's var -- and
+    corr = cov / sqrt(diag x diag) with a unit diagonal, NaN where a variance is not positive."""
+    delta = c1 / W
+    cov = C / W - delta[:, None] * delta[None, :]
+    var = np.diagonal(cov)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        sd = np.sqrt(np.where(var > 0, var, np.nan))
+        corr = cov / (sd[:, None] * sd[None, :])
+    corr[np.diag_indices_from(corr)] = np.where(var > 0, 1.0, np.nan)
+    return cov, corr
+
+
+def _cross_of_pool(cross_passes, center):
+    """the engines' cross passes chained in run order through the carry: cross_passes[e](center, carry) -> (d, d)"""
+    C = None
+    for cross_pass in cross_passes:
+        C = cross_pass(center, C)                                   # the carry of the next engine
+    return C
+
+
+def importance_covariance(result, *, importance=True):
+    """Importance-weighted posterior mean, covariance and correlation from ALL candidates of a multipathfinder result -- the dense
+    summary a mixture of fits has no single Sigma for (an initial metric for HMC, say).  The pool is rebuilt and weighted as in
+    importance_summary and stays on the device: two moment passes give W, the mean and the centred first moment, then one
+    Engine.pool_cross pass per engine about the mean forms the d x d cross moments on the matrix cores, the engines chained in run
+    order through the carry.  Across engines the host only forwards the carry, so the result is bit-identical for any number of
+    engines; cov is symmetric bit for bit and its diagonal is importance_summary's var.  importance=False, or a result without
+    psis_result: uniform weights (then np.cov(pool, ddof=0) to rounding).  Raises StaleHandleError when the engines hold newer fits."""
+    engs, blocks, npr, weighted, pareto_shape = _rebuild_pool(result, importance)
+    K = len(result.pathfinder_results)
+    parts = [eng.pool_moments(k0 * npr, weighted, None) for eng, (k0, _) in zip(engs, blocks)]
+    wtot = _combine_moments([p[0] for p in parts])
+    W = wtot[0]
+    mean = _combine_moments([p[1] for p in parts]) / W
+    c1 = _combine_moments([eng.pool_moments(k0 * npr, weighted, mean)[1] for eng, (k0, _) in zip(engs, blocks)])
+    passes = [(lambda cen, carry, eng=eng, k0=k0: eng.pool_cross(k0 * npr, weighted, cen, carry)) for eng, (k0, _) in zip(engs, blocks)]
+    cov, corr = _covariance_from_sums(_cross_of_pool(passes, mean), c1, W)
+    return ImportanceCovariance(mean, cov, corr, float(W * W / wtot[1]), K * npr, pareto_shape)
 
 
 def _f64_key(x):

@@ -543,6 +543,25 @@ class Engine:
                                    _d(above), nanflag.ctypes.data_as(C.POINTER(C.c_int32))))
         return wle, below, above, nanflag
 
+    def pool_cross(self, col_offset=0, importance=True, center=None, carry=None):
+        """Weighted cross moments of this engine's pool in one pass on the device (include/pfmi.h pfmi_pool_cross): the (d, d) matrix
+        C[i][j] = carry[i][j] + sum over the local runs, in run order, of sum_n (w t_i) t_j with t = x - center, weights and the
+        zero-weight rule as in pool_moments.  Only i >= j is computed (and read from carry); the other triangle is its copy, so C is
+        symmetric bit for bit.  carry (d, d): the C of the engines that own the earlier runs, added first; chaining engines in run
+        order gives the bits of one engine that holds all the runs."""
+        d = self.d
+        if center is not None:
+            center = np.ascontiguousarray(center, dtype=np.float64)
+            if center.shape != (d,):
+                raise ValueError(f"pool_cross: center must have shape ({d},)")
+        if carry is not None:
+            carry = np.ascontiguousarray(carry, dtype=np.float64)
+            if carry.shape != (d, d):
+                raise ValueError(f"pool_cross: carry must have shape ({d}, {d})")
+        out = np.empty((d, d))
+        check(self.L.pfmi_pool_cross(self.ctx, int(col_offset), int(bool(importance)), _d(center), _d(carry), _d(out)))
+        return out
+
     def pool_draws_dev(self):
         """(device pointer, count) of this engine's pool draws: d x K N_r doubles, column-major (pfmi_pool_draws_dev)"""
         p, n = C.c_void_p(), C.c_int64()
