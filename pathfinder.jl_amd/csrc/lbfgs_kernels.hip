@@ -50,7 +50,7 @@ struct LbfgsArgs {
     int pub_mask;
 };
 
-// XGM (the 1024-thread variants, 128 registers per thread): the gradient g of the current point and the target's mean / diagonal are
+// XGM (the 512-thread variants, 20 or 32 elements per thread): the gradient g of the current point and the target's mean / diagonal are
 // not held in registers but re-read where they are used -- g from the trace row the kernel has just written (record() stores -g of
 // every accepted point; an L2 hit, needed once per iteration), so that x, p, xn, gn (4 EPT doubles) are the vectors a thread carries.
 template <int EPT, int NT, int RPAD>

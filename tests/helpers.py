@@ -31,9 +31,10 @@ STANDIN_LIB = __import__("os").path.join(ROOT, "tests", "rccl_standin", "librccl
 DEMO_LIB = __import__("os").environ.get("PFMI_DEMO_CLOSURE_LIB") or __import__("os").path.join(ROOT, "examples", "device_logp", "liblogp_demo.so")   # (the override: experiment builds of the example closure)
 
 
-def demo_device_target(tg):
+def demo_device_target(tg, grad=False):
     """The user-side HIP closure of examples/device_logp for a built-in target `tg` (same parameters): a
-    PFMI_TARGET_DEVICE_CALLBACK target whose kernel reads the materialised draws from HBM."""
+    PFMI_TARGET_DEVICE_CALLBACK target whose kernel reads the materialised draws from HBM.  grad=True: with the example's
+    value-and-gradient closure attached, so that optimize_batch runs the closure L-BFGS (lbfgs_closure_kernel.hip)."""
     import ctypes as C
     import pfmi
     pfmi.lib()                                            # one HIP runtime per process: libpfmi (and torch) first
@@ -41,14 +42,16 @@ def demo_device_target(tg):
     dp = C.POINTER(C.c_double)
     if tg.kind == 1:
         fn = C.cast(L.pfx_funnel_logp, C.c_void_p).value
-        return pfmi.DeviceCallbackTarget(tg.d, fn, None, host=tg, keepalive=L)
+        return pfmi.DeviceCallbackTarget(tg.d, fn, None, host=tg, keepalive=L,
+                                         grad_fn=C.cast(L.pfx_funnel_logp_grad, C.c_void_p).value if grad else None)
     L.pfx_gauss_create.restype = C.c_void_p
     L.pfx_gauss_create.argtypes = [C.c_int32, C.c_int32, dp, dp, dp, dp, C.c_double]
     h = L.pfx_gauss_create(tg.d, tg.r, tg.mean.ctypes.data_as(dp), tg.a.ctypes.data_as(dp),
                            tg.Wd.ctypes.data_as(dp) if tg.r else None, tg.G.ctypes.data_as(dp) if tg.r else None, tg.offset)
     assert h, "pfx_gauss_create failed"
     fn = C.cast(L.pfx_gauss_logp, C.c_void_p).value
-    return pfmi.DeviceCallbackTarget(tg.d, fn, C.c_void_p(h), host=tg, keepalive=(L, h))
+    return pfmi.DeviceCallbackTarget(tg.d, fn, C.c_void_p(h), host=tg, keepalive=(L, h),
+                                     grad_fn=C.cast(L.pfx_gauss_logp_grad, C.c_void_p).value if grad else None)
 
 
 def demo_host_target(tg):
