@@ -33,6 +33,32 @@ static int32_t pool_fill(pfmi_ctx *c) {
     return PFMI_OK;
 }
 
+// what the passes over the pool (pfmi_pool_moments / _cdf / _cross) check first: a pool, the entry point's own arguments (arg_error:
+// its complaint, or NULL), a col_offset >= 0 and, with importance weighting, PSIS weights on this ctx that cover the pool's columns
+// [col_offset, col_offset + K N_r) of the global pool.  arg_error exists to keep each entry point's message and the place of its
+// check between the pool's and the weights'; pfmi_pool_cross words the offset and its NULL output as ONE complaint, so for it the
+// col_offset check below never fires.
+static int32_t pool_pass_check(pfmi_ctx *c, const char *name, int64_t col_offset, int32_t importance, const char *arg_error = nullptr) {
+    PF_CHECK(c->pooled, PFMI_ERR_STATE, "%s: call pfmi_pool_build first", name);
+    PF_CHECK(!arg_error, PFMI_ERR_ARG, "%s: %s", name, arg_error);
+    PF_CHECK(col_offset >= 0, PFMI_ERR_ARG, "%s: negative col_offset", name);
+    const int64_t end = col_offset + (int64_t)c->K * c->N_r;
+    PF_CHECK(!importance || (c->S_w > 0 && end <= c->S_w), PFMI_ERR_STATE,
+             "%s: no PSIS weights for columns [%lld, %lld) on this ctx (run pfmi_psis / pfmi_comm_pool_psis first)", name,
+             (long long)col_offset, (long long)end);
+    return PFMI_OK;
+}
+
+// an optional host vector of n doubles on the device: *dev = buf, grown and filled on the ctx stream, or NULL when host is NULL
+static int32_t upload_optional(pfmi_ctx *c, DevBuf &buf, const double *host, size_t n, const double **dev) {
+    *dev = nullptr;
+    if (!host) return PFMI_OK;
+    PF_TRY(buf.ensure(sizeof(double) * n));
+    PF_TRY(pf_upload(c, buf.p, host, sizeof(double) * n));
+    *dev = buf.as<double>();
+    return PFMI_OK;
+}
+
 extern "C" {
 
 int32_t pfmi_pool_build(pfmi_ctx *c, int64_t N_r, const int64_t *points, const uint64_t *seeds) {
@@ -97,17 +123,11 @@ int32_t pfmi_pool_get(pfmi_ctx *c, double *draws, double *log_ratios) {
 int32_t pfmi_pool_moments(pfmi_ctx *c, int64_t col_offset, int32_t importance, const double *center, double *wsum, double *s1,
                           double *s2, double *s2w) {
     PF_CTX_MUT(c);
-    PF_CHECK(c->pooled, PFMI_ERR_STATE, "pool_moments: call pfmi_pool_build first");
-    PF_CHECK(col_offset >= 0, PFMI_ERR_ARG, "pool_moments: negative col_offset");
+    PF_TRY(pool_pass_check(c, "pool_moments", col_offset, importance));
     const size_t K = (size_t)c->K, d = (size_t)c->d;
-    PF_CHECK(!importance || (c->S_w > 0 && col_offset + (int64_t)K * c->N_r <= c->S_w), PFMI_ERR_STATE,
-             "pool_moments: no PSIS weights for columns [%lld, %lld) on this ctx (run pfmi_psis / pfmi_comm_pool_psis first)",
-             (long long)col_offset, (long long)(col_offset + (int64_t)K * c->N_r));
-    if (center) {
-        PF_TRY(c->mom_center.ensure(sizeof(double) * d));
-        PF_TRY(pf_upload(c, c->mom_center.p, center, sizeof(double) * d));
-    }
-    PF_TRY(pf_launch_pool_moments(c, col_offset, importance, center ? c->mom_center.as<double>() : nullptr));
+    const double *d_center;
+    PF_TRY(upload_optional(c, c->pool_center, center, d, &d_center));
+    PF_TRY(pf_launch_pool_moments(c, col_offset, importance, d_center));
     const double *m = c->mom.as<double>();
     if (wsum) PF_TRY(pf_download(c, wsum, m, sizeof(double) * 2 * K));
     if (s1) PF_TRY(pf_download(c, s1, m + 2 * K, sizeof(double) * K * d));
@@ -119,20 +139,13 @@ int32_t pfmi_pool_moments(pfmi_ctx *c, int64_t col_offset, int32_t importance, c
 int32_t pfmi_pool_cdf(pfmi_ctx *c, int64_t col_offset, int32_t importance, int32_t nthr, const double *thresholds, const double *wle_in,
                       double *wle, double *below, double *above, int32_t *nanflag) {
     PF_CTX_MUT(c);
-    PF_CHECK(c->pooled, PFMI_ERR_STATE, "pool_cdf: call pfmi_pool_build first");
-    PF_CHECK(col_offset >= 0, PFMI_ERR_ARG, "pool_cdf: negative col_offset");
-    PF_CHECK(nthr >= 1 && nthr <= 32 && thresholds, PFMI_ERR_ARG, "pool_cdf: nthr must be in [1, 32] and thresholds non-NULL");
-    const size_t K = (size_t)c->K, plane = (size_t)nthr * (size_t)c->d;
-    PF_CHECK(!importance || (c->S_w > 0 && col_offset + (int64_t)K * c->N_r <= c->S_w), PFMI_ERR_STATE,
-             "pool_cdf: no PSIS weights for columns [%lld, %lld) on this ctx (run pfmi_psis / pfmi_comm_pool_psis first)",
-             (long long)col_offset, (long long)(col_offset + (int64_t)K * c->N_r));
-    PF_TRY(c->pcdf_thr.ensure(sizeof(double) * plane));
-    PF_TRY(pf_upload(c, c->pcdf_thr.p, thresholds, sizeof(double) * plane));
-    if (wle_in) {
-        PF_TRY(c->pcdf_carry.ensure(sizeof(double) * plane));
-        PF_TRY(pf_upload(c, c->pcdf_carry.p, wle_in, sizeof(double) * plane));
-    }
-    PF_TRY(pf_launch_pool_cdf(c, col_offset, importance, nthr, c->pcdf_thr.as<double>(), wle_in ? c->pcdf_carry.as<double>() : nullptr));
+    PF_TRY(pool_pass_check(c, "pool_cdf", col_offset, importance,
+                           nthr >= 1 && nthr <= 32 && thresholds ? nullptr : "nthr must be in [1, 32] and thresholds non-NULL"));
+    const size_t plane = (size_t)nthr * (size_t)c->d;
+    const double *d_thr, *d_carry;
+    PF_TRY(upload_optional(c, c->pcdf_thr, thresholds, plane, &d_thr));
+    PF_TRY(upload_optional(c, c->pcdf_carry, wle_in, plane, &d_carry));
+    PF_TRY(pf_launch_pool_cdf(c, col_offset, importance, nthr, d_thr, d_carry));
     const double *o = c->pcdf.as<double>();
     if (wle) PF_TRY(pf_download(c, wle, o, sizeof(double) * plane));
     if (below) PF_TRY(pf_download(c, below, o + plane, sizeof(double) * plane));
@@ -143,20 +156,12 @@ int32_t pfmi_pool_cdf(pfmi_ctx *c, int64_t col_offset, int32_t importance, int32
 
 int32_t pfmi_pool_cross(pfmi_ctx *c, int64_t col_offset, int32_t importance, const double *center, const double *c_in, double *c_out) {
     PF_CTX_MUT(c);
-    PF_CHECK(c->pooled, PFMI_ERR_STATE, "pool_cross: call pfmi_pool_build first");
-    PF_CHECK(col_offset >= 0 && c_out, PFMI_ERR_ARG, "pool_cross: negative col_offset or NULL c_out");
-    const size_t K = (size_t)c->K, d = (size_t)c->d;
-    PF_CHECK(!importance || (c->S_w > 0 && col_offset + (int64_t)K * c->N_r <= c->S_w), PFMI_ERR_STATE,
-             "pool_cross: no PSIS weights for columns [%lld, %lld) on this ctx (run pfmi_psis / pfmi_comm_pool_psis first)",
-             (long long)col_offset, (long long)(col_offset + (int64_t)K * c->N_r));
-    if (center) {
-        PF_TRY(c->cross_center.ensure(sizeof(double) * d));
-        PF_TRY(pf_upload(c, c->cross_center.p, center, sizeof(double) * d));
-    }
-    PF_TRY(c->cross.ensure(sizeof(double) * d * d));
-    if (c_in) PF_TRY(pf_upload(c, c->cross.p, c_in, sizeof(double) * d * d));      // accumulated in place
-    PF_TRY(pf_launch_pool_cross(c, col_offset, importance, center ? c->cross_center.as<double>() : nullptr,
-                                c_in ? c->cross.as<double>() : nullptr));
+    PF_TRY(pool_pass_check(c, "pool_cross", col_offset, importance, col_offset >= 0 && c_out ? nullptr : "negative col_offset or NULL c_out"));
+    const size_t d = (size_t)c->d;
+    const double *d_center, *d_carry;
+    PF_TRY(upload_optional(c, c->pool_center, center, d, &d_center));
+    PF_TRY(upload_optional(c, c->cross, c_in, d * d, &d_carry));                   // accumulated in place
+    PF_TRY(pf_launch_pool_cross(c, col_offset, importance, d_center, d_carry));
     PF_TRY(pf_download(c, c_out, c->cross.p, sizeof(double) * d * d));
     return pf_stream_sync(c);
 }

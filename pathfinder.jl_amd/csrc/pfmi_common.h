@@ -269,13 +269,12 @@ struct pfmi_ctx {
     DevBuf rs_err;                // int32: error flag of the last enqueued index selection
     DevBuf mom;                   // pfmi_pool_moments: [wsum K 2][s1 K d][s2 K d][s2w K d]
     DevBuf mom_part;              // its per-chunk partial sums (pool_moments_kernels.hip)
-    DevBuf mom_center;            // its centre vector [d]
     DevBuf pcdf;                   // pfmi_pool_cdf: [wle nthr d][below nthr d][above nthr d][nanflag d (int32)]
     DevBuf pcdf_part;              // its per-chunk partial results (pool_cdf_kernels.hip)
     DevBuf pcdf_thr;               // its thresholds [nthr d]
     DevBuf pcdf_carry;             // its carry-in vector [nthr d]
     DevBuf cross;                  // pfmi_pool_cross: C [d d], both triangles (a carry-in is uploaded here and accumulated in place)
-    DevBuf cross_center;           // its centre vector [d]
+    DevBuf pool_center;            // the centre vector [d] of pfmi_pool_moments / pfmi_pool_cross (the calls are serialised on the ctx stream)
 };
 
 // small host -> device upload on the ctx stream WITHOUT synchronising it (pinned arena); large blocks take the synchronous path

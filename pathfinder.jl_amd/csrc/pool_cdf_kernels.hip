@@ -6,11 +6,10 @@
 // two compares, three selects of a double, one add, one max and one min per threshold.  The cut of a run into workgroups is the moments kernel's
 // (pool_geometry.h): NS column slots per workgroup, chunks of L columns, slots combined through LDS in slot order, chunks and runs
 // added in order by pf_pool_cdf_combine_kernel.  No atomics.
-//   d >= 64   lanes run along rows.  The 4 waves are NS slots x 4 / NS row waves; a lane holds V consecutive rows (V = 2, 16-byte
-//             loads, when d is even and >= 128 and NT <= CDF_NT_PAIRED: two rows of more thresholds do not fit the register file at
-//             more than one wave per SIMD; V = 1 otherwise).  The row tiling is free: the order in which a row's terms are added is
-//             fixed by (NS, L) alone.
-//   d <  64   a wave holds G = 64 / d whole columns, as in the moments kernel.
+// The thread layout and the column walk are the ones stated in pool_geometry.h, with two choices of this file: the 4 waves are NS slots
+// x 4 / NS row waves whatever V is (the row tiling is free: the order in which a row's terms are added is fixed by (NS, L) alone), and
+// a lane holds two rows (V = 2) only when NT <= CDF_NT_PAIRED: two rows of more thresholds do not fit the register file at more than
+// one wave per SIMD.
 // Instantiations: NT = 4, 8, 16 thresholds per thread; nthr is padded up with +inf thresholds whose results are never written.  32
 // thresholds with their accumulators exceed the 256 VGPRs a thread can address, so above 16 the workgroup is doubled (TS = 2): its
 // second 4 waves repeat the first 4 waves' loads and own thresholds 16 to 31: the pool still leaves HBM once, but a CU loads every
@@ -32,33 +31,18 @@ __global__ __launch_bounds__(MOM_THREADS * TS) void pf_pool_cdf_kernel(int d, in
                                                                   const double *__restrict__ pool, const double *__restrict__ wts,
                                                                   const double *__restrict__ thr, double *__restrict__ part,
                                                                   int32_t *__restrict__ pnan) {
-    constexpr int U = MOM_BYTES_IN_FLIGHT / (8 * V);
     __shared__ __attribute__((aligned(16))) double red_all[TS * 3 * MOM_THREADS * V];   // per threshold group: [q][slot][row of the tile]
     __shared__ int32_t nred[MOM_THREADS * V];                                  // [row of the tile]: a counted NaN in any slot
-    const int tid = threadIdx.x % MOM_THREADS, wave = tid >> 6, lane = tid & 63;
+    const int tid = threadIdx.x % MOM_THREADS;
     const int joff = (threadIdx.x / MOM_THREADS) * NT;             // this thread's thresholds: joff + [0, NT)
     const int jmax = nthr < NT ? nthr : NT;                        // (uniform over the workgroup)
     double *red = red_all + (threadIdx.x / MOM_THREADS) * 3 * MOM_THREADS * V;
     const int k = blockIdx.z;
     const int64_t C = gridDim.y, n0 = (int64_t)blockIdx.y * L, n1 = (n0 + L < N_r) ? n0 + L : N_r;
     const double inf = __builtin_huge_val();
-    int slot, rloc, rows_per_wg;
-    bool active;
-    if (G == 0) {                      // d >= 64: lanes along rows
-        const int RW = MOM_WAVES / NS, rw = wave % RW;
-        slot = wave / RW;
-        rloc = (rw * 64 + lane) * V;
-        rows_per_wg = RW * 64 * V;
-        active = (int64_t)blockIdx.x * rows_per_wg + rloc < d;      // (V = 2: d is even, so the pair is inside too)
-    } else {                           // d < 64: G whole columns per wave
-        const int g = lane / d;
-        slot = wave * G + g;
-        rloc = lane - g * d;
-        rows_per_wg = d;
-        active = g < G;
-    }
-    const int row = blockIdx.x * rows_per_wg + rloc;
-    const bool imp = wts != nullptr;
+    const PoolLane p = pool_lane<V>(d, G, NS);
+    const int slot = p.slot, rloc = p.rloc, rows_per_wg = p.rows_per_wg, row = p.row;
+    const bool active = p.active;
     double T[NT][V], wle[NT][V], below[NT][V], above[NT][V];
     int32_t nan[V];
 #pragma unroll
@@ -74,42 +58,22 @@ __global__ __launch_bounds__(MOM_THREADS * TS) void pf_pool_cdf_kernel(int d, in
         }
     }
     if (active) {
-        const double *col = pool + (size_t)k * N_r * d + row;       // column n of the run: col + n d
-        const double *wk = imp ? wts + (size_t)k * N_r : nullptr;
-        for (int64_t n = n0 + slot; n < n1; n += (int64_t)U * NS) {
-            double x[U][V], w[U];
-            bool use[U];
+        pool_walk<V>(pool + (size_t)k * N_r * d + row, wts ? wts + (size_t)k * N_r : nullptr, d, n0 + slot, n1, NS,
+                     [&](const double (&x)[V], double w, bool on) {
 #pragma unroll
-            for (int u = 0; u < U; ++u) {                           // every load of the trip is issued before the first use
-                const int64_t nu = n + (int64_t)u * NS;
-                use[u] = nu < n1;
-                const int64_t nc = use[u] ? nu : n;                 // (clamped: an in-range column)
-                if constexpr (V == 2) {
-                    const double2 t = *reinterpret_cast<const double2 *>(col + (size_t)nc * d);
-                    x[u][0] = t.x; x[u][V - 1] = t.y;
-                } else {
-                    x[u][0] = col[(size_t)nc * d];
-                }
-                w[u] = imp ? wk[nc] : 1.0;
-            }
+                         for (int v = 0; v < V; ++v) {
+                             nan[v] |= (on && x[v] != x[v]) ? 1 : 0;
+                             // a skipped column becomes a NaN here, once per element: like a counted NaN it compares false on both sides
+                             const double xv = on ? x[v] : __builtin_nan("");
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const bool on = use[u] && !(imp && w[u] == 0.0);    // a zero weight skips the column whatever it holds
-#pragma unroll
-                for (int v = 0; v < V; ++v) {
-                    nan[v] |= (on && x[u][v] != x[u][v]) ? 1 : 0;
-                    // a skipped column becomes a NaN here, once per element: like a counted NaN it compares false on both sides
-                    const double xv = on ? x[u][v] : __builtin_nan("");
-#pragma unroll
-                    for (int j = 0; j < NT; ++j) {
-                        const bool le = xv <= T[j][v], gt = xv > T[j][v];
-                        wle[j][v] += le ? w[u] : 0.0;
-                        below[j][v] = fmax(below[j][v], le ? xv : -inf);
-                        above[j][v] = fmin(above[j][v], gt ? xv : inf);
-                    }
-                }
-            }
-        }
+                             for (int j = 0; j < NT; ++j) {
+                                 const bool le = xv <= T[j][v], gt = xv > T[j][v];
+                                 wle[j][v] += le ? w : 0.0;
+                                 below[j][v] = fmax(below[j][v], le ? xv : -inf);
+                                 above[j][v] = fmin(above[j][v], gt ? xv : inf);
+                             }
+                         }
+                     });
     }
     if (NS > 1) {                      // slots in slot order, one threshold at a time (3 NT sets of a tile's slots exceed the LDS)
         __syncthreads();
@@ -150,15 +114,15 @@ __global__ __launch_bounds__(MOM_THREADS * TS) void pf_pool_cdf_kernel(int d, in
     }
     if (active && slot == 0) {
         const size_t kc = (size_t)k * C + blockIdx.y, plane = (size_t)nthr * d;
-        double *p = part + kc * 3 * plane + row;
+        double *o = part + kc * 3 * plane + row;
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
             if (joff + j < nthr) {
 #pragma unroll
                 for (int v = 0; v < V; ++v) {
-                    p[(size_t)(joff + j) * d + v] = wle[j][v];
-                    p[plane + (size_t)(joff + j) * d + v] = below[j][v];
-                    p[2 * plane + (size_t)(joff + j) * d + v] = above[j][v];
+                    o[(size_t)(joff + j) * d + v] = wle[j][v];
+                    o[plane + (size_t)(joff + j) * d + v] = below[j][v];
+                    o[2 * plane + (size_t)(joff + j) * d + v] = above[j][v];
                 }
             }
         }
@@ -210,13 +174,13 @@ static void cdf_launch(pfmi_ctx *c, const MomGeom &g, int nthr, const double *wt
 int32_t pf_launch_pool_cdf(pfmi_ctx *c, int64_t col_offset, int importance, int nthr, const double *d_thr, const double *d_carry) {
     const int K = c->K, d = c->d;
     const MomGeom g = mom_geometry(d, c->N_r, CDF_WG_PER_RUN);
-    PF_CHECK(K <= 65535 && g.C <= 65535, PFMI_ERR_ARG, "pool_cdf: too many runs for one launch");
+    PF_CHECK(mom_grid_fits(K, g), PFMI_ERR_ARG, "pool_cdf: too many runs for one launch");
     const size_t plane = (size_t)nthr * d, kc = (size_t)K * g.C;
     PF_TRY(c->pcdf.ensure(sizeof(double) * 3 * plane + sizeof(int32_t) * d));
     PF_TRY(c->pcdf_part.ensure(sizeof(double) * kc * 3 * plane + sizeof(int32_t) * kc * d));
     double *part = c->pcdf_part.as<double>(), *out = c->pcdf.as<double>();
     int32_t *pnan = reinterpret_cast<int32_t *>(part + kc * 3 * plane), *onan = reinterpret_cast<int32_t *>(out + 3 * plane);
-    const double *wts = importance ? c->w.as<double>() + col_offset : nullptr;
+    const double *wts = pf_pool_weights(c, col_offset, importance);
     const bool paired = g.G == 0 && g.V == 2 && nthr <= CDF_NT_PAIRED;
     pf_kernel_begin(c);
     if (nthr <= 4) {

@@ -3,8 +3,8 @@
 //
 // For the ctx's pool (d x (K N_r), column-major, one column per draw), t = x - center and i >= j:
 //   C[i][j] = C_in[i][j] + sum_runs k (in run order) sum_n fl(w fl(x_i - c_i)) * fl(x_j - c_j)
-// w as in pool_moments_kernels.hip: weights[col_offset + k N_r + n], or 1 without importance weighting; a column whose weight is exactly
-// 0 is skipped by a select (both operands become 0, never 0 * NaN).
+// w and the zero-weight rule are those of every pass over the pool (pool_geometry.h: pf_pool_weights, pool_weight, pool_counts): weights[col_offset +
+// k N_r + n], or 1 without importance weighting; a skipped column makes both operands 0.
 //
 // One workgroup (256 threads = 4 waves) owns one T x T tile of the lower triangle, diagonal tiles included, for the whole launch.  The
 // tile is cut 2 x 2 among the waves; a wave holds its T/2 x T/2 quarter as (T/32)^2 accumulators of v_mfma_f64_16x16x4_f64 (C/D: lane
@@ -13,7 +13,7 @@
 // is t of a 16-row block of the tile's columns (lane: B[n0 + q][column c]).
 //   staging   the workgroup walks the runs in order and each run in chunks of NC = 2048 / T columns.  A chunk's two slabs (T rows of the
 //             row block, T rows of the column block) are loaded with lanes along rows (V = 2, 16-byte loads, when d is even: the
-//             alignment rule of pool_moments_kernels.hip; tiles start at even rows), centred and weighted ONCE, and written to LDS as
+//             alignment rule of pool_geometry.h; tiles start at even rows), centred and weighted ONCE, and written to LDS as
 //             [column][row] with rows of T + 16 doubles (the 4 columns a wave reads together then fall on different banks).  The loads of
 //             chunk c + 1 are in flight while the MFMAs of chunk c run (16 doubles per thread whatever T and V are).
 //   tails     rows >= d are 0 in both slabs.  A run's last chunk holds N_r % NC columns; its groups of 4 are completed with zero
@@ -31,6 +31,7 @@
 //   - So contexts chained in run order, each passing its result to the next, return the bits of one context holding all the runs.
 // Small d gives few workgroups (one at d <= 64) and a slow pass; there is no second kernel for it.
 #include "pfmi_common.h"
+#include "pool_geometry.h"       // pool_weight, pool_counts, pf_pool_weights
 
 #include <stdlib.h>
 
@@ -98,8 +99,8 @@ __global__ __launch_bounds__(CROSS_THREADS) void pf_pool_cross_kernel(int d, int
             const int64_t n = n0 + cslot + NSL * u;
             const bool use = n < N_r;
             const int64_t nc = use ? n : n0;                        // (clamped: an in-range column)
-            w[u] = imp ? wk[nc] : 1.0;
-            on[u] = use && !(imp && w[u] == 0.0);                   // a zero weight skips the column whatever it holds
+            w[u] = pool_weight(imp, wk, nc);
+            on[u] = pool_counts(imp, use, w[u]);                     // a zero weight skips the column whatever it holds
             const double *col = run + (size_t)nc * d;
 #pragma unroll
             for (int v = 0; v < V; ++v) xa[u][v] = xb[u][v] = 0.0;
@@ -169,7 +170,7 @@ static void cross_launch(pfmi_ctx *c, const double *wts, const double *d_center,
 int32_t pf_launch_pool_cross(pfmi_ctx *c, int64_t col_offset, int importance, const double *d_center, const double *d_carry) {
     const int d = c->d;
     PF_TRY(c->cross.ensure(sizeof(double) * (size_t)d * d));
-    const double *wts = importance ? c->w.as<double>() + col_offset : nullptr;
+    const double *wts = pf_pool_weights(c, col_offset, importance);
     int tile = d >= CROSS_T128_MIN_D ? 128 : 64;
     if (const char *f = pf_debug_get("PFMI_POOL_CROSS_TILE")) { const int v = atoi(f); if (v == 64 || v == 128) tile = v; }   // A/B hook: same bits
     const int64_t nb = ((int64_t)d + tile - 1) / tile;

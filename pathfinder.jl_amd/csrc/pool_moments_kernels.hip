@@ -5,52 +5,28 @@
 // w = weights[col_offset + k N_r + n] (the ctx's PSIS weights of the GLOBAL pool), or 1 without importance weighting.  A column whose
 // weight is exactly 0 is skipped by a select (never 0 * NaN); without importance weighting nothing is skipped.
 //
-// One pass over the pool, bound by HBM.  A workgroup is 256 threads = 4 waves and owns a tile of rows and a chunk of L consecutive
-// columns of one run; grid = (row tiles, chunks, K).  Its threads are grouped into NS column SLOTS: slot s takes the columns
-// n0 + s, n0 + s + NS, ... of the chunk and keeps its sums in registers.
-//   d >= 64   lanes run along rows: a wave reads 64 V consecutive doubles of a column per load (V = 2, 16-byte loads, when d is even
-//             and >= 128 -- a column starts at byte 8 d s, so paired loads are aligned exactly when d is even; V = 1 otherwise).
-//             The 4 waves are RW row waves x CW column waves (RW = 4, 2, 1 as the rows need); NS = CW.
-//   d <  64   a wave holds G = 64 / d whole columns: lane = g d + i reads row i of column slot (wave G + g); NS = 4 G.  G d of the 64
-//             lanes work (more than half for every d), and the wave's loads are G d consecutive doubles.
-// Each thread issues MOM_BYTES_IN_FLIGHT / (8 V) independent loads before it consumes the first.  The slots' sums are combined through
-// LDS in slot order and written as the chunk's partial; pf_pool_moments_sum_kernel adds the chunks in chunk order.  No atomics.
+// One pass over the pool, bound by HBM, in the cut, thread layout and column walk of pool_geometry.h (stated there once).  The slots'
+// sums are combined through LDS in slot order and written as the chunk's partial; pf_pool_moments_sum_kernel adds the chunks in chunk
+// order.  No atomics.
 //
 // Ordering rule: the geometry (V, RW, NS, chunk length) is a function of (d, N_r) ALONE -- never of K, col_offset, the run's position or
 // the device -- so the sums of one run are formed in the same order, and have the same bits, on whichever context owns the run.
 #include "pfmi_common.h"
-
-#include "pool_geometry.h"       // mom_geometry: the one statement of the geometry, shared with pool_cdf_kernels.hip
+#include "pool_geometry.h"
 
 // partial sums of one (row tile, chunk, run): part[((k C + c) 3 + q) d + i], q = 0: s1, 1: s2, 2: s2w; pw[(k C + c) 2 + j]
 template <int V>
-__global__ __launch_bounds__(MOM_THREADS) void pf_pool_moments_kernel(int d, int64_t N_r, int64_t L, int RW, int G, int NS,
+__global__ __launch_bounds__(MOM_THREADS) void pf_pool_moments_kernel(int d, int64_t N_r, int64_t L, int G, int NS,
                                                                       const double *__restrict__ pool, const double *__restrict__ wts,
                                                                       const double *__restrict__ center, double *__restrict__ part,
                                                                       double *__restrict__ pw) {
-    constexpr int U = MOM_BYTES_IN_FLIGHT / (8 * V);
     __shared__ __attribute__((aligned(16))) double red[3 * MOM_THREADS * V];   // [q][slot][row of the tile]
     __shared__ double wred[2 * MOM_THREADS];                                   // [slot][2]: the slots' sums of w and w^2
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int k = blockIdx.z;
+    const int tid = threadIdx.x, k = blockIdx.z;
     const int64_t C = gridDim.y, n0 = (int64_t)blockIdx.y * L, n1 = (n0 + L < N_r) ? n0 + L : N_r;
-    int slot, rloc, rows_per_wg;
-    bool active;
-    if (G == 0) {                      // d >= 64: lanes along rows
-        const int rw = wave % RW;
-        slot = wave / RW;
-        rloc = (rw * 64 + lane) * V;
-        rows_per_wg = RW * 64 * V;
-        active = (int64_t)blockIdx.x * rows_per_wg + rloc < d;      // (V = 2: d is even, so the pair is inside too)
-    } else {                           // d < 64: G whole columns per wave
-        const int g = lane / d;
-        slot = wave * G + g;
-        rloc = lane - g * d;
-        rows_per_wg = d;
-        active = g < G;
-    }
-    const int row = blockIdx.x * rows_per_wg + rloc;
-    const bool imp = wts != nullptr;
+    const PoolLane p = pool_lane<V>(d, G, NS);
+    const int slot = p.slot, rloc = p.rloc, rows_per_wg = p.rows_per_wg, row = p.row;
+    const bool active = p.active;
     double s1[V], s2[V], s2w[V], sw = 0.0, sw2 = 0.0, cen[V];
 #pragma unroll
     for (int v = 0; v < V; ++v) s1[v] = s2[v] = s2w[v] = cen[v] = 0.0;
@@ -59,40 +35,20 @@ __global__ __launch_bounds__(MOM_THREADS) void pf_pool_moments_kernel(int d, int
 #pragma unroll
             for (int v = 0; v < V; ++v) cen[v] = center[row + v];
         }
-        const double *col = pool + (size_t)k * N_r * d + row;       // column n of the run: col + n d
-        const double *wk = imp ? wts + (size_t)k * N_r : nullptr;
-        for (int64_t n = n0 + slot; n < n1; n += (int64_t)U * NS) {
-            double x[U][V], w[U];
-            bool use[U];
+        pool_walk<V>(pool + (size_t)k * N_r * d + row, wts ? wts + (size_t)k * N_r : nullptr, d, n0 + slot, n1, NS,
+                     [&](const double (&x)[V], double w, bool on) {
+                         const double wu = on ? w : 0.0;
+                         sw += wu;
+                         sw2 += wu * wu;
 #pragma unroll
-            for (int u = 0; u < U; ++u) {                           // every load of the trip is issued before the first use
-                const int64_t nu = n + (int64_t)u * NS;
-                use[u] = nu < n1;
-                const int64_t nc = use[u] ? nu : n;                 // (clamped: an in-range column)
-                if constexpr (V == 2) {
-                    const double2 t = *reinterpret_cast<const double2 *>(col + (size_t)nc * d);
-                    x[u][0] = t.x; x[u][V - 1] = t.y;
-                } else {
-                    x[u][0] = col[(size_t)nc * d];
-                }
-                w[u] = imp ? wk[nc] : 1.0;
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const bool on = use[u] && !(imp && w[u] == 0.0);    // a zero weight skips the column whatever it holds
-                const double wu = on ? w[u] : 0.0;
-                sw += wu;
-                sw2 += wu * wu;
-#pragma unroll
-                for (int v = 0; v < V; ++v) {
-                    const double t = x[u][v] - cen[v];
-                    const double a = w[u] * t;
-                    s1[v] += on ? a : 0.0;
-                    s2[v] += on ? a * t : 0.0;
-                    s2w[v] += on ? a * a : 0.0;
-                }
-            }
-        }
+                         for (int v = 0; v < V; ++v) {
+                             const double t = x[v] - cen[v];
+                             const double a = w * t;
+                             s1[v] += on ? a : 0.0;
+                             s2[v] += on ? a * t : 0.0;
+                             s2w[v] += on ? a * a : 0.0;
+                         }
+                     });
         if (slot > 0) {
 #pragma unroll
             for (int v = 0; v < V; ++v) {
@@ -113,9 +69,9 @@ __global__ __launch_bounds__(MOM_THREADS) void pf_pool_moments_kernel(int d, int
                 s2w[v] += red[(2 * NS + s) * rows_per_wg + rloc + v];
             }
         }
-        double *p = part + ((size_t)k * C + blockIdx.y) * 3 * d + row;
+        double *o = part + ((size_t)k * C + blockIdx.y) * 3 * d + row;
 #pragma unroll
-        for (int v = 0; v < V; ++v) { p[v] = s1[v]; p[(size_t)d + v] = s2[v]; p[2 * (size_t)d + v] = s2w[v]; }
+        for (int v = 0; v < V; ++v) { o[v] = s1[v]; o[(size_t)d + v] = s2[v]; o[2 * (size_t)d + v] = s2w[v]; }
     }
     if (blockIdx.x == 0 && tid < 2) {  // the chunk's sums of w and w^2: row tile 0 only, slots in slot order
         double s = wred[tid];
@@ -151,18 +107,18 @@ int32_t pf_launch_pool_moments(pfmi_ctx *c, int64_t col_offset, int importance, 
     const int K = c->K, d = c->d;
     const int64_t N_r = c->N_r;
     const MomGeom g = mom_geometry(d, N_r);
-    PF_CHECK(K <= 65535 && g.C <= 65535, PFMI_ERR_ARG, "pool_moments: too many runs for one launch");
+    PF_CHECK(mom_grid_fits(K, g), PFMI_ERR_ARG, "pool_moments: too many runs for one launch");
     PF_TRY(c->mom.ensure(sizeof(double) * ((size_t)K * 2 + 3 * (size_t)K * d)));
     PF_TRY(c->mom_part.ensure(sizeof(double) * (size_t)K * g.C * (3 * (size_t)d + 2)));
     double *part = c->mom_part.as<double>(), *pw = part + (size_t)K * g.C * 3 * d;
-    const double *wts = importance ? c->w.as<double>() + col_offset : nullptr;
+    const double *wts = pf_pool_weights(c, col_offset, importance);
     const dim3 grid((unsigned)g.row_tiles, (unsigned)g.C, (unsigned)K);
     pf_kernel_begin(c);
     if (g.V == 2)
-        hipLaunchKernelGGL(pf_pool_moments_kernel<2>, grid, dim3(MOM_THREADS), 0, c->stream, d, N_r, g.L, g.RW, g.G, g.NS,
+        hipLaunchKernelGGL(pf_pool_moments_kernel<2>, grid, dim3(MOM_THREADS), 0, c->stream, d, N_r, g.L, g.G, g.NS,
                            c->pool.as<double>(), wts, d_center, part, pw);
     else
-        hipLaunchKernelGGL(pf_pool_moments_kernel<1>, grid, dim3(MOM_THREADS), 0, c->stream, d, N_r, g.L, g.RW, g.G, g.NS,
+        hipLaunchKernelGGL(pf_pool_moments_kernel<1>, grid, dim3(MOM_THREADS), 0, c->stream, d, N_r, g.L, g.G, g.NS,
                            c->pool.as<double>(), wts, d_center, part, pw);
     PF_HIP(hipGetLastError());
     pf_kernel_end(c, "pool_moments");

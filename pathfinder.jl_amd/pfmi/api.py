@@ -951,22 +951,37 @@ def _combine_moments(blocks):
 def _rebuild_pool(result, importance):
     """The preamble of the pooled summaries: every engine of `result` rebuilds its block of the pool from the runs' stored
     (fit, draw_seed, ndraws_per_run) and, with importance weighting, the pooled PSIS is re-run so that every engine holds the weights
-    of the global pool.  Returns (engines, run blocks, ndraws_per_run, weighted, pareto_shape)."""
+    of the global pool.  Returns (owners, weighted, pareto_shape); owners: one (engine, col_offset) per engine in global run order,
+    col_offset the global pool column of the engine's first draw."""
     engs = result.engines or [result.engine]
     runs = result.pathfinder_results
-    K = len(runs)
-    blocks = _blocks(K, len(engs))
     for r in runs:
         r.fit_distribution._live()                                  # the fits must still be the engine's current ones
     npr = runs[0].ndraws_per_run
     seeds = [r.draw_seed for r in runs]
-    for eng, (k0, k1) in zip(engs, blocks):
+    owners = []
+    for eng, (k0, k1) in zip(engs, _blocks(len(runs), len(engs))):
         eng.pool_build(npr, [r.fit_distribution.point for r in runs[k0:k1]], seeds[k0:k1])
+        owners.append((eng, k0 * npr))
     weighted = bool(importance) and result.psis_result is not None
     pareto_shape = float("nan")
     if weighted:                                                    # weights of the rebuilt pool, replicated on every engine
         pareto_shape = _comm_for(engs).pool_psis()["pareto_shape"]
-    return engs, blocks, npr, weighted, pareto_shape
+    return owners, weighted, pareto_shape
+
+
+def _moment_pass(owners, weighted, center):
+    """Engine.pool_moments of every owner about `center`: (wsum, s1, s2, s2w), each a list with one block of runs per engine"""
+    parts = [eng.pool_moments(off, weighted, center) for eng, off in owners]
+    return [[p[j] for p in parts] for j in range(4)]
+
+
+def _first_moments(owners, weighted, want_mean=True):
+    """The moment pass about the origin: (wsum blocks, wtot = (sum w, sum w^2) over all runs, W = sum w, mean = sum w x / W -- None
+    when it is not wanted)"""
+    wsum_b, s1_b, _, _ = _moment_pass(owners, weighted, None)
+    wtot = _combine_moments(wsum_b)
+    return wsum_b, wtot, wtot[0], (_combine_moments(s1_b) / wtot[0] if want_mean else None)
 
 
 def importance_summary(result, *, importance=True):
@@ -977,22 +992,14 @@ def importance_summary(result, *, importance=True):
     re-run, and two moment passes (Engine.pool_moments: about the origin, then about the mean) return 3 d numbers per run.  Across
     runs only the host adds, in run order, so the summary is bit-identical for any number of engines.  importance=False, or a
     result without psis_result: uniform weights.  Raises StaleHandleError when the engines hold newer fits."""
-    engs, blocks, npr, weighted, pareto_shape = _rebuild_pool(result, importance)
-    K = len(result.pathfinder_results)
-
-    def moment_pass(center):
-        parts = [eng.pool_moments(k0 * npr, weighted, center) for eng, (k0, _) in zip(engs, blocks)]
-        return [[p[j] for p in parts] for j in range(4)]            # wsum, s1, s2, s2w: one block per engine each
-
-    wsum_b, s1_b, _, _ = moment_pass(None)
-    wtot = _combine_moments(wsum_b)                                 # (sum w, sum w^2) over all runs
-    W = wtot[0]
-    mean = _combine_moments(s1_b) / W
-    _, c1_b, c2_b, c2w_b = moment_pass(mean)
+    owners, weighted, pareto_shape = _rebuild_pool(result, importance)
+    wsum_b, wtot, W, mean = _first_moments(owners, weighted)
+    _, c1_b, c2_b, c2w_b = _moment_pass(owners, weighted, mean)
     var = _combine_moments(c2_b) / W - (_combine_moments(c1_b) / W) ** 2
     mcse = np.sqrt(_combine_moments(c2w_b)) / W
     run_weights = np.concatenate([b[:, 0] for b in wsum_b]) / W
-    return ImportanceSummary(mean, var, np.sqrt(var), mcse, float(W * W / wtot[1]), run_weights, K * npr, pareto_shape)
+    S = len(result.pathfinder_results) * result.pathfinder_results[0].ndraws_per_run
+    return ImportanceSummary(mean, var, np.sqrt(var), mcse, float(W * W / wtot[1]), run_weights, S, pareto_shape)
 
 
 @dataclass
@@ -1036,16 +1043,13 @@ def importance_covariance(result, *, importance=True):
     order through the carry.  Across engines the host only forwards the carry, so the result is bit-identical for any number of
     engines; cov is symmetric bit for bit and its diagonal is importance_summary's var.  importance=False, or a result without
     psis_result: uniform weights (then np.cov(pool, ddof=0) to rounding).  Raises StaleHandleError when the engines hold newer fits."""
-    engs, blocks, npr, weighted, pareto_shape = _rebuild_pool(result, importance)
-    K = len(result.pathfinder_results)
-    parts = [eng.pool_moments(k0 * npr, weighted, None) for eng, (k0, _) in zip(engs, blocks)]
-    wtot = _combine_moments([p[0] for p in parts])
-    W = wtot[0]
-    mean = _combine_moments([p[1] for p in parts]) / W
-    c1 = _combine_moments([eng.pool_moments(k0 * npr, weighted, mean)[1] for eng, (k0, _) in zip(engs, blocks)])
-    passes = [(lambda cen, carry, eng=eng, k0=k0: eng.pool_cross(k0 * npr, weighted, cen, carry)) for eng, (k0, _) in zip(engs, blocks)]
+    owners, weighted, pareto_shape = _rebuild_pool(result, importance)
+    _, wtot, W, mean = _first_moments(owners, weighted)
+    c1 = _combine_moments(_moment_pass(owners, weighted, mean)[1])
+    passes = [(lambda cen, carry, eng=eng, off=off: eng.pool_cross(off, weighted, cen, carry)) for eng, off in owners]
     cov, corr = _covariance_from_sums(_cross_of_pool(passes, mean), c1, W)
-    return ImportanceCovariance(mean, cov, corr, float(W * W / wtot[1]), K * npr, pareto_shape)
+    S = len(result.pathfinder_results) * result.pathfinder_results[0].ndraws_per_run
+    return ImportanceCovariance(mean, cov, corr, float(W * W / wtot[1]), S, pareto_shape)
 
 
 def _f64_key(x):
@@ -1146,20 +1150,25 @@ def importance_quantiles(result, probs=(0.025, 0.25, 0.5, 0.75, 0.975), *, impor
     probs = np.atleast_1d(np.asarray(probs, dtype=np.float64))
     if probs.ndim != 1 or probs.size == 0 or not np.all((probs >= 0) & (probs <= 1)):
         raise ValueError("importance_quantiles: probs must be a non-empty sequence of numbers in [0, 1]")
-    engs, blocks, npr, weighted, _ = _rebuild_pool(result, importance)
-    q, passes = _quantiles_of_pool(engs, blocks, npr, weighted, probs)
+    owners, weighted, _ = _rebuild_pool(result, importance)
+    q, passes = _quantiles_of_owners(owners, weighted, probs)
     return (q, passes) if return_passes else q
 
 
 def _quantiles_of_pool(engs, blocks, npr, weighted, probs):
-    """importance_quantiles after its preamble: the quantiles of the pool the engines hold now, (q, passes)"""
-    d = engs[0].d
-    W = _combine_moments([eng.pool_moments(k0 * npr, weighted, None)[0] for eng, (k0, _) in zip(engs, blocks)])[0]
+    """_quantiles_of_owners for engines that hold the run blocks `blocks` (_blocks) of npr draws per run"""
+    return _quantiles_of_owners([(eng, k0 * npr) for eng, (k0, _) in zip(engs, blocks)], weighted, probs)
+
+
+def _quantiles_of_owners(owners, weighted, probs):
+    """importance_quantiles after its preamble: the quantiles of the pool the owners (_rebuild_pool) hold now, (q, passes)"""
+    d = owners[0][0].d
+    W = _first_moments(owners, weighted, want_mean=False)[2]
 
     def cdf_pass(T):
         wle, below, above, nan = None, None, None, None
-        for eng, (k0, _) in zip(engs, blocks):
-            w, b, a, f = eng.pool_cdf(k0 * npr, weighted, T, wle)
+        for eng, off in owners:
+            w, b, a, f = eng.pool_cdf(off, weighted, T, wle)
             wle = w                                                 # the carry of the next engine
             below = b if below is None else np.maximum(below, b)
             above = a if above is None else np.minimum(above, a)

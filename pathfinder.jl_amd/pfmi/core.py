@@ -20,6 +20,18 @@ def _d(a):
     return a.ctypes.data_as(_dp) if a is not None else None
 
 
+def _f64_of_shape(who, what, a, shape):
+    """the optional argument `what` of Engine method `who` as a contiguous float64 array of `shape` (a name in it: any extent), None
+    when it is None; ValueError otherwise"""
+    if a is None:
+        return None
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if a.ndim != len(shape) or any(not isinstance(s, str) and n != s for n, s in zip(a.shape, shape)):
+        want = ", ".join(str(s) for s in shape) + ("," if len(shape) == 1 else "")
+        raise ValueError(f"{who}: {what} must have shape ({want})")
+    return a
+
+
 def _is_torch(x):
     """x is a torch tensor (without importing torch when the caller never did)"""
     torch = sys.modules.get("torch")
@@ -514,10 +526,7 @@ class Engine:
         col_offset + k N_r + n (zero-weight columns are skipped); False: w = 1.  A run's rows have the same bits on whichever
         engine owns the run."""
         K, d = self.K, self.d
-        if center is not None:
-            center = np.ascontiguousarray(center, dtype=np.float64)
-            if center.shape != (d,):
-                raise ValueError(f"pool_moments: center must have shape ({d},)")
+        center = _f64_of_shape("pool_moments", "center", center, (d,))
         wsum = np.empty((K, 2))
         s1, s2, s2w = np.empty((K, d)), np.empty((K, d)), np.empty((K, d))
         check(self.L.pfmi_pool_moments(self.ctx, int(col_offset), int(bool(importance)), _d(center), _d(wsum), _d(s1), _d(s2), _d(s2w)))
@@ -529,14 +538,9 @@ class Engine:
         carry (nthr, d): the wle of the engines that own the earlier runs, added first; chaining engines in run order gives the bits
         of one engine that holds all the runs."""
         d = self.d
-        thresholds = np.ascontiguousarray(thresholds, dtype=np.float64)
-        if thresholds.ndim != 2 or thresholds.shape[1] != d:
-            raise ValueError(f"pool_cdf: thresholds must have shape (nthr, {d})")
+        thresholds = _f64_of_shape("pool_cdf", "thresholds", np.asarray(thresholds, dtype=np.float64), ("nthr", d))
         nthr = thresholds.shape[0]
-        if carry is not None:
-            carry = np.ascontiguousarray(carry, dtype=np.float64)
-            if carry.shape != (nthr, d):
-                raise ValueError(f"pool_cdf: carry must have shape ({nthr}, {d})")
+        carry = _f64_of_shape("pool_cdf", "carry", carry, (nthr, d))
         wle, below, above = np.empty((nthr, d)), np.empty((nthr, d)), np.empty((nthr, d))
         nanflag = np.empty(d, dtype=np.int32)
         check(self.L.pfmi_pool_cdf(self.ctx, int(col_offset), int(bool(importance)), nthr, _d(thresholds), _d(carry), _d(wle), _d(below),
@@ -550,14 +554,8 @@ class Engine:
         symmetric bit for bit.  carry (d, d): the C of the engines that own the earlier runs, added first; chaining engines in run
         order gives the bits of one engine that holds all the runs."""
         d = self.d
-        if center is not None:
-            center = np.ascontiguousarray(center, dtype=np.float64)
-            if center.shape != (d,):
-                raise ValueError(f"pool_cross: center must have shape ({d},)")
-        if carry is not None:
-            carry = np.ascontiguousarray(carry, dtype=np.float64)
-            if carry.shape != (d, d):
-                raise ValueError(f"pool_cross: carry must have shape ({d}, {d})")
+        center = _f64_of_shape("pool_cross", "center", center, (d,))
+        carry = _f64_of_shape("pool_cross", "carry", carry, (d, d))
         out = np.empty((d, d))
         check(self.L.pfmi_pool_cross(self.ctx, int(col_offset), int(bool(importance)), _d(center), _d(carry), _d(out)))
         return out

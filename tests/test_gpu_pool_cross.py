@@ -11,37 +11,19 @@ Shapes: d = 1 (one entry), 10 (under one 16-block), 17 (a block and a row), 63 /
 tiles with ragged rows and ragged columns), 257 (odd d), 1000 (many tiles, paired loads), 4100 (the 128 x 128 tile on a large grid,
 sampled); N_r = 1, 5, 37, 1000 (one column, N_r % 4 != 0, a ragged last chunk, many groups); K = 1, 3.  The 128 x 128 tile is also
 forced at d = 130 and 257 (both load widths) and must return the bits of the 64 x 64 tile."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 import margins as mg
-import test_gpu_pool_moments as tm
-from helpers import ROOT, STANDIN_LIB
+from pool_common import LD, U, J, _pool, check_pool_error_codes, ratio_to_bound, run_two_engines
 from pool_cross_reference import bound, covariance, pool_cross
 
 pytestmark = pytest.mark.gpu
 
-LD = np.longdouble
-U = LD(2.0) ** -53
-J = tm.J
-
-
-def _ratio(got, ref, A, M):
-    """max over entries of |got - ref| / bound (an entry with A = 0 must be exact)"""
-    err = np.abs(np.asarray(got, dtype=LD) - ref)
-    b = bound(M, A)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        r = np.where(b > 0, err / np.where(b > 0, b, 1), np.where(err == 0, 0.0, np.inf))
-    return float(np.max(r))
-
 
 def _check(tag, got, ref, A, M):
     assert got.shape == ref.shape, (tag, got.shape, ref.shape)
-    r = _ratio(got, ref, A, M)
+    r = ratio_to_bound(bound, got, ref, A, M)
     print(f"pool_cross {tag}: worst |gpu - ref| / bound = {r:.3g}")
     mg.check("pool_cross", "C", r, bound=1.0, contract=1.0, ctx=tag)
 
@@ -57,7 +39,7 @@ CASES = [("d1", 1, 1), ("d1", 5, 3), ("lr10", 5, 1), ("lr10", 1000, 3), ("d17", 
 
 @pytest.mark.parametrize("name,N_r,K", CASES, ids=[f"{n}-N{r}-K{k}" for n, r, k in CASES])
 def test_pool_cross_matches_the_longdouble_reference(pfmi_mod, eng, name, N_r, K):
-    P, lr = tm._pool(pfmi_mod, eng, name, K, N_r)
+    P, lr = _pool(pfmi_mod, eng, name, K, N_r)
     d = P.shape[0]
     w = eng.psis(lr)["weights"]
     center = np.random.default_rng(d + N_r).normal(size=d) * 0.7 + P[:, 0, 0]
@@ -75,7 +57,7 @@ def test_large_d_sampled(pfmi_mod, eng):
     """d = 4100: 33 x 33 tiles of 128 (561 workgroups), the last tile row 4 rows high; about 2 x 10^5 random entries and the whole last
     tile row against the reference, the symmetry on the full matrix"""
     N_r, K = 5, 1
-    P, lr = tm._pool(pfmi_mod, eng, "d4100", K, N_r)
+    P, lr = _pool(pfmi_mod, eng, "d4100", K, N_r)
     d = P.shape[0]
     assert d == 4100
     w = eng.psis(lr)["weights"]
@@ -96,7 +78,7 @@ def test_large_d_sampled(pfmi_mod, eng):
 @pytest.mark.parametrize("name", ["d130", "d257"])
 def test_the_tile_size_does_not_change_the_bits(pfmi_mod, eng, name):
     N_r, K = 37, 3
-    P, lr = tm._pool(pfmi_mod, eng, name, K, N_r)
+    P, lr = _pool(pfmi_mod, eng, name, K, N_r)
     eng.psis(lr)
     center = P[:, 2, 1] + 0.25
     L = pfmi_mod.lib()
@@ -115,7 +97,7 @@ def test_the_tile_size_does_not_change_the_bits(pfmi_mod, eng, name):
 def test_carry(pfmi_mod, eng, name, N_r):
     """a random symmetric carry stays within the bound with M + 1 terms; runs {0, 1, 2} in one call == run {0}, then runs {1, 2}
     with the first result as the carry (the engine rebuilt; it keeps the PSIS weights of the K = 3 pool): the same bits"""
-    P3, lr3 = tm._pool(pfmi_mod, eng, name, 3, N_r)
+    P3, lr3 = _pool(pfmi_mod, eng, name, 3, N_r)
     d = P3.shape[0]
     w = eng.psis(lr3)["weights"]
     center = P3[:, 0, 2] * 0.5 + 0.1
@@ -126,9 +108,9 @@ def test_carry(pfmi_mod, eng, name, N_r):
     ref, A = pool_cross(P3, w, center, X)
     _check(f"{name} carry", got, ref, A, 3 * N_r + 1)
     whole = {imp: eng.pool_cross(0, imp, center) for imp in (True, False)}
-    tm._pool(pfmi_mod, eng, name, 1, N_r, runs=[0])
+    _pool(pfmi_mod, eng, name, 1, N_r, runs=[0])
     first = {imp: eng.pool_cross(0, imp, center) for imp in (True, False)}
-    P12, _ = tm._pool(pfmi_mod, eng, name, 2, N_r, runs=[1, 2])
+    P12, _ = _pool(pfmi_mod, eng, name, 2, N_r, runs=[1, 2])
     np.testing.assert_array_equal(P12, P3[:, :, 1:])              # (precondition: the same draws)
     for imp in (True, False):
         np.testing.assert_array_equal(eng.pool_cross(N_r, imp, center, carry=first[imp]), whole[imp], err_msg=f"imp={imp}")
@@ -137,7 +119,7 @@ def test_carry(pfmi_mod, eng, name, N_r):
 
 def test_col_offset_into_a_longer_psis_vector(pfmi_mod, eng):
     N_r, K = 37, 3
-    P, lr = tm._pool(pfmi_mod, eng, "lr65", K, N_r)
+    P, lr = _pool(pfmi_mod, eng, "lr65", K, N_r)
     rng = np.random.default_rng(8)
     off = 2 * N_r + 5
     glob = np.concatenate([rng.normal(size=off) + lr.mean(), lr, rng.normal(size=50) + lr.mean()])
@@ -150,7 +132,7 @@ def test_col_offset_into_a_longer_psis_vector(pfmi_mod, eng):
 
 def test_zero_weights_are_skipped(pfmi_mod, eng):
     N_r, K = 37, 3
-    P, lr = tm._pool(pfmi_mod, eng, "diag30", K, N_r)
+    P, lr = _pool(pfmi_mod, eng, "diag30", K, N_r)
     d = P.shape[0]
     lr = lr.copy()
     lr[N_r + 3:2 * N_r + 9] = -np.inf                            # a block across two runs
@@ -162,7 +144,7 @@ def test_zero_weights_are_skipped(pfmi_mod, eng):
         ref, A = pool_cross(P, w, c)
         _check("zero weights", eng.pool_cross(0, True, c), ref, A, K * N_r)
     # a run whose columns all have weight 0 changes nothing: the output is the carry
-    tm._pool(pfmi_mod, eng, "diag30", 1, N_r, runs=[1])
+    _pool(pfmi_mod, eng, "diag30", 1, N_r, runs=[1])
     lr[N_r:2 * N_r] = -np.inf
     w = eng.psis(lr)["weights"]
     assert np.all(w[N_r:2 * N_r] == 0.0)
@@ -175,7 +157,7 @@ def test_zero_weights_are_skipped(pfmi_mod, eng):
 @pytest.mark.parametrize("name", ["lr10", "lr65", "d130", "d1000"])
 def test_nan_under_a_zero_weight_is_invisible_and_under_a_weight_poisons_its_row_and_column(pfmi_mod, eng, name):
     N_r, K = 37, 3
-    P, lr = tm._pool(pfmi_mod, eng, name, K, N_r)
+    P, lr = _pool(pfmi_mod, eng, name, K, N_r)
     d = P.shape[0]
     z, c = N_r + 20, 2 * N_r + 36                                  # columns of runs 1 and 2 (the ragged last chunk of run 2)
     r0, r1 = d // 2, d - 1
@@ -208,39 +190,15 @@ def test_nan_under_a_zero_weight_is_invisible_and_under_a_weight_poisons_its_row
 
 
 def test_error_codes(pfmi_mod):
-    e = pfmi_mod.Engine(0)
-    try:
-        tg, traces = tm._traces(pfmi_mod, "lr10")
-        e.set_target(tg)
-        e.set_traces([t.points for t in traces[:2]], [t.gradients for t in traces[:2]])
-        e.fit_batch(J)
-        with pytest.raises(pfmi_mod.PfmiError) as ex:            # no pool
-            e.pool_cross(0, False)
-        assert ex.value.code == -3
-        pts = [int(e.offsets[k + 1]) - 1 for k in range(2)]
-        e.pool_build(5, pts, np.array([1, 2], dtype=np.uint64))
-        with pytest.raises(pfmi_mod.PfmiError) as ex:            # importance without a PSIS result
-            e.pool_cross(0, True)
-        assert ex.value.code == -3
-        e.pool_cross(0, False)                                   # uniform weights need none
-        _, lr = e.pool_get(draws=False)
-        e.psis(lr)
-        e.pool_cross(0, True)
-        with pytest.raises(pfmi_mod.PfmiError) as ex:            # the PSIS result does not cover [1, 1 + K N_r)
-            e.pool_cross(1, True)
-        assert ex.value.code == -3
-        for imp in (True, False):
-            with pytest.raises(pfmi_mod.PfmiError) as ex:
-                e.pool_cross(-1, imp)
-            assert ex.value.code == -1
+    def then(e):
         assert e.L.pfmi_pool_cross(e.ctx, 0, 0, None, None, None) == -1       # c_out NULL
         with pytest.raises(ValueError):
             e.pool_cross(0, False, np.zeros(3))
         for bad in (np.zeros((10, 9)), np.zeros(100)):
             with pytest.raises(ValueError):
                 e.pool_cross(0, False, None, carry=bad)
-    finally:
-        e.close()
+
+    check_pool_error_codes(pfmi_mod, lambda e, off, imp: e.pool_cross(off, imp), then)
 
 
 @pytest.mark.parametrize("d,r", [(10, 3), (65, 8)])
@@ -327,10 +285,4 @@ print("covariance engines ok")
 def test_covariance_over_two_engines_is_bit_identical():
     """engines=[Engine(0), Engine(0)] through the RCCL stand-in: the covariance and the chained primitive have the bits of the
     one-engine result"""
-    assert os.path.exists(STANDIN_LIB), "tests/rccl_standin/librccl_standin.so missing: run __graft_entry__.build()"
-    env = dict(os.environ, PFMI_RCCL_LIB=STANDIN_LIB, PFMI_COMM_ALLOW_SHARED_GPU="1", PFMI_STANDIN_TIMEOUT_S="60")
-    env.pop("PFMI_COMM_FORCE_RCCL", None)
-    r = subprocess.run([sys.executable, "-c", _MULTI, ROOT], env=env, capture_output=True, text=True, timeout=550)
-    print(r.stdout[-2000:])
-    assert r.returncode == 0, r.stdout[-2000:] + "\n" + r.stderr[-4000:]
-    assert "covariance engines ok" in r.stdout
+    run_two_engines(_MULTI, "covariance engines ok")

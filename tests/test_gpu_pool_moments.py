@@ -6,67 +6,15 @@ the formulas (tests/pool_moments_reference.py) on the DOWNLOADED pool and weight
 |gpu - ref| <= (N_r + 4) 2^-53 A, A the sum of the absolute values of the entry's terms (pool_moments_reference.bound).  The worst
 observed ratio to the bound is recorded through tests/margins.py (config "pool_moments") and printed.
 
-Shapes: d = 1 (a single row), 10 / 12 / 30 / 50 / 63 (several columns per wave, one column per wave), 64 and 65 (lanes along rows, one
-load per lane, odd d), 130 (paired loads, two row waves), 257 (odd d over two row tiles), 1000 and 10 000 (paired loads, several row
-tiles, many chunks); N_r = 1, 5, 37, 1000 (one column, fewer columns than slots, a ragged last chunk, many chunks); K = 1, 3."""
-import os
-import subprocess
-import sys
-
+Shapes: tests/pool_common.py (CASES), every size at which the column walk takes another path; K = 1, 3."""
 import numpy as np
 import pytest
 
 import margins as mg
-from gpu_common import _targets
-from helpers import ROOT, STANDIN_LIB, make_traces
+from pool_common import CASES, LD, U, J, _pool, check_pool_error_codes, ratio_to_bound, run_two_engines
 from pool_moments_reference import bound, pool_moments, summary
 
 pytestmark = pytest.mark.gpu
-
-LD = np.longdouble
-U = LD(2.0) ** -53
-J = 6
-_TRACES = {}
-
-
-def _traces(pfmi, name):
-    """(target, three traces) of a named case, built once per session"""
-    if name not in _TRACES:
-        small = _targets(pfmi)
-        if name in small:
-            tg, maxit = small[name], (25 if name.startswith("funnel") else 1000)
-        elif name == "d1":
-            tg, maxit = pfmi.t_diag(1), 1000
-        elif name == "lr65":
-            tg, maxit = pfmi.t_lowrank(65, r=3), 1000
-        else:                                                  # "d<dim>": diagonal target, three iterations
-            tg, maxit = pfmi.t_diag(int(name[1:])), 3
-        _TRACES[name] = (tg, make_traces(tg, 3, 11, history_length=J, maxiters=maxit))
-    return _TRACES[name]
-
-
-def _pool(pfmi, eng, name, K, N_r, runs=None):
-    """fit the first K (or the given) traces of the case, pool N_r draws of every path's last fit; returns the pool and its PSIS"""
-    tg, traces = _traces(pfmi, name)
-    traces = [traces[k] for k in (runs if runs is not None else range(K))]
-    eng.set_target(tg)
-    eng.set_traces([t.points for t in traces], [t.gradients for t in traces])
-    eng.fit_batch(J)
-    pts = [int(eng.offsets[k + 1]) - 1 for k in range(len(traces))]
-    seeds = np.array([1000 + 7 * k for k in (runs if runs is not None else range(K))], dtype=np.uint64)
-    eng.pool_build(N_r, pts, seeds)
-    P, lr = eng.pool_get()
-    assert np.all(np.isfinite(P))
-    return np.array(P), lr
-
-
-def _ratio(got, ref, A, N_r):
-    """max over entries of |got - ref| / bound (an entry with A = 0 must be exact)"""
-    err = np.abs(np.asarray(got, dtype=LD) - ref)
-    b = bound(N_r, A)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        r = np.where(b > 0, err / np.where(b > 0, b, 1), np.where(err == 0, 0.0, np.inf))
-    return float(np.max(r))
 
 
 def _check(tag, got, ref, N_r):
@@ -75,15 +23,10 @@ def _check(tag, got, ref, N_r):
     for q, g, r, a in (("wsum", wsum, ref["wsum"], ref["Aw"]), ("s1", s1, ref["s1"], ref["A1"]), ("s2", s2, ref["s2"], ref["A2"]),
                        ("s2w", s2w, ref["s2w"], ref["A2w"])):
         assert g.shape == r.shape, (tag, q, g.shape, r.shape)
-        worst[q] = _ratio(g, r, a, N_r)
+        worst[q] = ratio_to_bound(bound, g, r, a, N_r)
     print(f"pool_moments {tag}: worst |gpu - ref| / bound = " + ", ".join(f"{q} {v:.3g}" for q, v in worst.items()))
     for q, v in worst.items():                                 # (printed for every quantity before the first assertion)
         mg.check("pool_moments", q, v, bound=1.0, contract=1.0, ctx=tag)
-
-
-CASES = [("d1", 1, 1), ("d1", 5, 3), ("d1", 1000, 3), ("lr10", 5, 1), ("lr10", 1000, 3), ("funnel12", 37, 3), ("diag30", 37, 3),
-         ("diag30", 1000, 1), ("lr50", 1, 3), ("lr50", 1000, 1), ("d63", 37, 1), ("d64", 37, 3), ("lr65", 37, 3), ("lr65", 1000, 1),
-         ("d130", 37, 3), ("d257", 37, 3), ("d1000", 1000, 3), ("d1000", 5, 1), ("d10000", 37, 3), ("d10000", 5, 1)]
 
 
 @pytest.mark.parametrize("name,N_r,K", CASES, ids=[f"{n}-N{r}-K{k}" for n, r, k in CASES])
@@ -158,35 +101,11 @@ def test_rows_do_not_depend_on_where_the_run_sits(pfmi_mod, eng, name, N_r):
 
 
 def test_error_codes(pfmi_mod):
-    e = pfmi_mod.Engine(0)
-    try:
-        tg, traces = _traces(pfmi_mod, "lr10")
-        e.set_target(tg)
-        e.set_traces([t.points for t in traces[:2]], [t.gradients for t in traces[:2]])
-        e.fit_batch(J)
-        with pytest.raises(pfmi_mod.PfmiError) as ex:            # no pool
-            e.pool_moments(0, False, None)
-        assert ex.value.code == -3
-        pts = [int(e.offsets[k + 1]) - 1 for k in range(2)]
-        e.pool_build(5, pts, np.array([1, 2], dtype=np.uint64))
-        with pytest.raises(pfmi_mod.PfmiError) as ex:            # importance without a PSIS result
-            e.pool_moments(0, True, None)
-        assert ex.value.code == -3
-        e.pool_moments(0, False, None)                           # uniform weights need none
-        _, lr = e.pool_get(draws=False)
-        e.psis(lr)
-        e.pool_moments(0, True, None)
-        with pytest.raises(pfmi_mod.PfmiError) as ex:            # the PSIS result does not cover [1, 1 + K N_r)
-            e.pool_moments(1, True, None)
-        assert ex.value.code == -3
-        for imp in (True, False):
-            with pytest.raises(pfmi_mod.PfmiError) as ex:
-                e.pool_moments(-1, imp, None)
-            assert ex.value.code == -1
+    def then(e):
         with pytest.raises(ValueError):
             e.pool_moments(0, False, np.zeros(3))
-    finally:
-        e.close()
+
+    check_pool_error_codes(pfmi_mod, lambda e, off, imp: e.pool_moments(off, imp, None), then)
 
 
 def _summary_bounds(P, w):
@@ -277,10 +196,4 @@ print("summary engines ok", a.ess)
 @pytest.mark.timeout(600)
 def test_summary_over_two_engines_is_bit_identical():
     """engines=[Engine(0), Engine(0)] through the RCCL stand-in: every field of summary() has the bits of the one-engine result"""
-    assert os.path.exists(STANDIN_LIB), "tests/rccl_standin/librccl_standin.so missing: run __graft_entry__.build()"
-    env = dict(os.environ, PFMI_RCCL_LIB=STANDIN_LIB, PFMI_COMM_ALLOW_SHARED_GPU="1", PFMI_STANDIN_TIMEOUT_S="60")
-    env.pop("PFMI_COMM_FORCE_RCCL", None)
-    r = subprocess.run([sys.executable, "-c", _MULTI, ROOT], env=env, capture_output=True, text=True, timeout=550)
-    print(r.stdout[-2000:])
-    assert r.returncode == 0, r.stdout[-2000:] + "\n" + r.stderr[-4000:]
-    assert "summary engines ok" in r.stdout
+    run_two_engines(_MULTI, "summary engines ok")

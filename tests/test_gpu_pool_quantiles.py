@@ -5,28 +5,20 @@ Primitive: pool_build, pool_get + psis, pool_cdf; compared with the longdouble r
 DOWNLOADED pool and weights.  below / above / nanflag must be equal exactly; |wle - ref| <= (K N_r + 5) 2^-53 * (sum of the counted
 weights): any order of adding K N_r non-negative terms is within (K N_r - 1) u of the exact sum relative to the sum of all terms,
 the same form as the moments' bound.  The worst ratio is recorded through tests/margins.py (config "pool_quantiles").  Shapes are those
-of tests/test_gpu_pool_moments.py, at which the kernels' paths switch; threshold counts 3, 8, 13 and 32 take every instantiation
+of tests/pool_common.py (CASES), at which the kernels' paths switch; threshold counts 3, 8, 13 and 32 take every instantiation
 (4, 8, 16 thresholds per thread, two rows per lane up to 8, the doubled workgroup above 16).
 
 NaN rules: a NaN is written into the pool on the device through pfmi_pool_draws_dev + pfmi_memcpy_h2d, under a zero and under a
 non-zero weight, at shapes with several slots per workgroup (d < 64, d = 65), with one (d = 1000) and at every instantiation."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 import margins as mg
-import test_gpu_pool_moments as tm
-from helpers import ROOT, STANDIN_LIB
+from pool_common import CASES, LD, U, J, _pool, check_pool_error_codes, run_two_engines
 from pool_quantiles_reference import cdf, quantiles
 
 pytestmark = pytest.mark.gpu
 
-LD = np.longdouble
-U = LD(2.0) ** -53
-J = tm.J
 NTHR = (3, 8, 13, 32)
 PROBS = (0.025, 0.25, 0.5, 0.75, 0.975)
 
@@ -57,9 +49,9 @@ def _check_cdf(tag, got, ref, n_terms, total):
     mg.check("pool_quantiles", "wle", ratio, bound=1.0, contract=1.0, ctx=tag)
 
 
-@pytest.mark.parametrize("name,N_r,K", tm.CASES, ids=[f"{n}-N{r}-K{k}" for n, r, k in tm.CASES])
+@pytest.mark.parametrize("name,N_r,K", CASES, ids=[f"{n}-N{r}-K{k}" for n, r, k in CASES])
 def test_pool_cdf_matches_the_longdouble_reference(pfmi_mod, eng, name, N_r, K):
-    P, lr = tm._pool(pfmi_mod, eng, name, K, N_r)
+    P, lr = _pool(pfmi_mod, eng, name, K, N_r)
     d = P.shape[0]
     P2 = P.reshape(d, K * N_r, order="F")
     w = eng.psis(lr)["weights"]
@@ -80,7 +72,7 @@ def test_pool_cdf_matches_the_longdouble_reference(pfmi_mod, eng, name, N_r, K):
 def test_carry_chains_contexts_in_run_order(pfmi_mod, eng, name, N_r):
     """runs {0, 1, 2} on one engine == runs {0, 1}, then run {2} with the first result as the carry (the engine rebuilt; it keeps the
     PSIS weights of the K = 3 pool): the same bits, for every instantiation"""
-    P3, lr3 = tm._pool(pfmi_mod, eng, name, 3, N_r)
+    P3, lr3 = _pool(pfmi_mod, eng, name, 3, N_r)
     d = P3.shape[0]
     P2 = P3.reshape(d, 3 * N_r, order="F")
     w = eng.psis(lr3)["weights"]
@@ -89,9 +81,9 @@ def test_carry_chains_contexts_in_run_order(pfmi_mod, eng, name, N_r):
     again = eng.pool_cdf(0, True, T)
     for x, y in zip(whole[(True, 32)], again):
         np.testing.assert_array_equal(x, y)
-    tm._pool(pfmi_mod, eng, name, 2, N_r, runs=[0, 1])
+    _pool(pfmi_mod, eng, name, 2, N_r, runs=[0, 1])
     first = {key: eng.pool_cdf(0, key[0], T[:key[1]]) for key in whole}
-    tm._pool(pfmi_mod, eng, name, 1, N_r, runs=[2])
+    _pool(pfmi_mod, eng, name, 1, N_r, runs=[2])
     for (imp, n), a in whole.items():
         f = first[(imp, n)]
         s = eng.pool_cdf(2 * N_r, imp, T[:n], carry=f[0])
@@ -104,7 +96,7 @@ def test_carry_chains_contexts_in_run_order(pfmi_mod, eng, name, N_r):
 
 def test_col_offset_into_a_longer_psis_vector(pfmi_mod, eng):
     N_r, K = 37, 3
-    P, lr = tm._pool(pfmi_mod, eng, "lr65", K, N_r)
+    P, lr = _pool(pfmi_mod, eng, "lr65", K, N_r)
     P2 = P.reshape(P.shape[0], K * N_r, order="F")
     rng = np.random.default_rng(8)
     off = 2 * N_r + 5
@@ -120,7 +112,7 @@ def test_col_offset_into_a_longer_psis_vector(pfmi_mod, eng):
 def test_zero_weights_are_skipped(pfmi_mod, eng):
     """a zero-weight column enters neither the sums nor below / above: the run of the row's extreme values gets weight 0"""
     N_r, K = 37, 3
-    P, lr = tm._pool(pfmi_mod, eng, "diag30", K, N_r)
+    P, lr = _pool(pfmi_mod, eng, "diag30", K, N_r)
     P2 = P.reshape(P.shape[0], K * N_r, order="F")
     lr = lr.copy()
     lr[np.argmax(P2[0])] = -np.inf
@@ -138,7 +130,7 @@ def test_zero_weights_are_skipped(pfmi_mod, eng):
 def test_nan_under_a_zero_weight_is_invisible_and_under_a_weight_sets_the_flag(pfmi_mod, eng, name):
     from pfmi.api import _quantiles_of_pool
     N_r, K = 37, 3
-    P, lr = tm._pool(pfmi_mod, eng, name, K, N_r)
+    P, lr = _pool(pfmi_mod, eng, name, K, N_r)
     d = P.shape[0]
     P2 = P.reshape(d, K * N_r, order="F")
     z, c = N_r + 20, 2 * N_r + 36                                  # columns of runs 1 and 2 (second chunks where a run has two)
@@ -187,42 +179,20 @@ def test_nan_under_a_zero_weight_is_invisible_and_under_a_weight_sets_the_flag(p
 
 
 def test_error_codes(pfmi_mod):
-    e = pfmi_mod.Engine(0)
-    try:
-        tg, traces = tm._traces(pfmi_mod, "lr10")
-        e.set_target(tg)
-        e.set_traces([t.points for t in traces[:2]], [t.gradients for t in traces[:2]])
-        e.fit_batch(J)
-        T = np.zeros((4, 10))
-        with pytest.raises(pfmi_mod.PfmiError) as ex:            # no pool
-            e.pool_cdf(0, False, T)
-        assert ex.value.code == -3
-        pts = [int(e.offsets[k + 1]) - 1 for k in range(2)]
-        e.pool_build(5, pts, np.array([1, 2], dtype=np.uint64))
-        with pytest.raises(pfmi_mod.PfmiError) as ex:            # importance without a PSIS result
-            e.pool_cdf(0, True, T)
-        assert ex.value.code == -3
-        e.pool_cdf(0, False, T)
-        _, lr = e.pool_get(draws=False)
-        e.psis(lr)
-        e.pool_cdf(0, True, T)
-        with pytest.raises(pfmi_mod.PfmiError) as ex:            # the PSIS result does not cover [1, 1 + K N_r)
-            e.pool_cdf(1, True, T)
-        assert ex.value.code == -3
+    T = np.zeros((4, 10))
+
+    def then(e):
         for bad in (np.zeros((0, 10)), np.zeros((33, 10))):      # nthr outside [1, 32]
             with pytest.raises(pfmi_mod.PfmiError) as ex:
                 e.pool_cdf(0, False, bad)
             assert ex.value.code == -1
-        with pytest.raises(pfmi_mod.PfmiError) as ex:
-            e.pool_cdf(-1, False, T)
-        assert ex.value.code == -1
         for bad in (np.zeros((4, 9)), np.zeros(40)):             # a wrong thresholds length
             with pytest.raises(ValueError):
                 e.pool_cdf(0, False, bad)
         with pytest.raises(ValueError):
             e.pool_cdf(0, False, T, carry=np.zeros((3, 10)))
-    finally:
-        e.close()
+
+    check_pool_error_codes(pfmi_mod, lambda e, off, imp: e.pool_cdf(off, imp, T), then)
 
 
 def _check_quantiles(tag, q, P2, w, W, probs):
@@ -303,10 +273,4 @@ print("quantiles engines ok", pa)
 def test_quantiles_over_two_engines_are_bit_identical():
     """engines=[Engine(0), Engine(0)] through the RCCL stand-in: quantiles, pass count and the chained primitive have the bits of the
     one-engine result"""
-    assert os.path.exists(STANDIN_LIB), "tests/rccl_standin/librccl_standin.so missing: run __graft_entry__.build()"
-    env = dict(os.environ, PFMI_RCCL_LIB=STANDIN_LIB, PFMI_COMM_ALLOW_SHARED_GPU="1", PFMI_STANDIN_TIMEOUT_S="60")
-    env.pop("PFMI_COMM_FORCE_RCCL", None)
-    r = subprocess.run([sys.executable, "-c", _MULTI, ROOT], env=env, capture_output=True, text=True, timeout=550)
-    print(r.stdout[-2000:])
-    assert r.returncode == 0, r.stdout[-2000:] + "\n" + r.stderr[-4000:]
-    assert "quantiles engines ok" in r.stdout
+    run_two_engines(_MULTI, "quantiles engines ok")

@@ -30,6 +30,20 @@ PINS = {
     "pf_history_kernel<4, 256>(": (256, 0, "history walk at d <= 1024: four register sets of rows, nothing spilled"),
     "pf_lbfgs_kernel<4, 256, 8, true>(": (512, 0, "device L-BFGS at config 3 (rank-8 target, ring in LDS): VGPRs + AGPRs at one wave per SIMD, no scratch"),
     "pf_lbfgs_kernel<4, 256, 0, true>(": (512, 0, "device L-BFGS, diagonal / funnel target"),
+    # the passes over the pool, as built before their column walk moved into csrc/pool_geometry.h (count at that build in brackets): + 8
+    # registers, or the top of the occupancy tier (512 / waves per SIMD, in steps of 8) where that is nearer
+    "pf_pool_moments_kernel<2>(": (72, 0, "pool moments, paired loads: 7 waves per SIMD [66]"),
+    "pf_pool_moments_kernel<1>(": (64, 0, "pool moments: 8 waves per SIMD [62]"),
+    "pf_pool_cdf_kernel<2, 4, 1>(": (118, 0, "pool CDF, two rows x 4 thresholds per lane: 4 waves per SIMD [110]"),
+    "pf_pool_cdf_kernel<1, 4, 1>(": (94, 0, "pool CDF, 4 thresholds per lane: 5 waves per SIMD [86]"),
+    "pf_pool_cdf_kernel<2, 8, 1>(": (234, 0, "pool CDF, two rows x 8 thresholds per lane: 2 waves per SIMD [226]"),
+    "pf_pool_cdf_kernel<1, 8, 1>(": (128, 0, "pool CDF, 8 thresholds per lane: 4 waves per SIMD [126]"),
+    "pf_pool_cdf_kernel<1, 16, 1>(": (214, 0, "pool CDF, 16 thresholds per lane: 2 waves per SIMD [206]; the build with the shared walk sits AT 214 (no SGPR spills into lanes any more): no slack left, on purpose -- a further rise is to be looked at, 256 is the tier"),
+    "pf_pool_cdf_kernel<1, 16, 2>(": (249, 0, "pool CDF, doubled workgroup (8 waves): 2 waves per SIMD or it does not launch [241]"),
+    "pf_pool_cross_kernel<64, 2>(": (144, 0, "pool cross moments, 64 x 64 tile, paired loads: 3 waves per SIMD [136]"),
+    "pf_pool_cross_kernel<64, 1>(": (152, 0, "pool cross moments, 64 x 64 tile: 3 waves per SIMD [144]"),
+    "pf_pool_cross_kernel<128, 2>(": (348, 0, "pool cross moments, 128 x 128 tile, paired loads: 64 accumulator doubles per lane, 1 wave per SIMD [340]"),
+    "pf_pool_cross_kernel<128, 1>(": (356, 0, "pool cross moments, 128 x 128 tile: 1 wave per SIMD [348]"),
 }
 
 
