@@ -376,6 +376,31 @@ int32_t pfmi_pool_cdf(pfmi_ctx *ctx, int64_t col_offset, int32_t importance, int
  * No pool: PFMI_ERR_STATE; importance != 0 without a PSIS result covering [col_offset, col_offset + K*N_r): PFMI_ERR_STATE;
  * col_offset < 0 or c_out NULL: PFMI_ERR_ARG. */
 int32_t pfmi_pool_cross(pfmi_ctx *ctx, int64_t col_offset, int32_t importance, const double *center, const double *c_in, double *c_out);
+/* The weighted second moment of the pool applied to a thin block of r vectors on the device, without forming the d x d matrix
+ * (1 <= r <= PFMI_POOL_APPLY_MAX_R): what a subspace iteration for the top eigenpairs of the pooled covariance needs, at 4 d r flops per
+ * draw instead of d^2.  Directions v[j*d + i], j < r.  With t_i(n) = fl(x_i(n) - center[i]) (center NULL: 0), over the N_r draws n of the
+ * ctx's runs k:
+ *   scores[(k*N_r + n)*r + j] = z_j(n) = sum_i t_i(n) * v[j*d + i]                      (0 for every j when the column is skipped)
+ *   y_out[j*d + i]            = y_in[j*d + i] + sum_k (in run order) sum_n fl(w t_i(n)) * z_j(n)          (y_in NULL: zeros)
+ * so that row j of y_out is (sum_n (w t) t') v_j.  Both contractions run on the f64 matrix cores, every product accumulated by a fused
+ * multiply-add.  y_out is required; scores is a host buffer of K*N_r*r doubles, or NULL for no download.  Columns and weights w are
+ * those of pfmi_pool_moments: importance != 0 takes the ctx's PSIS weight of global pool column col_offset + k*N_r + n and skips a column
+ * whose weight is exactly 0 whatever it holds: it is not read, its scores are exact zeros and it adds nothing to y_out (a NaN anywhere in
+ * it is invisible); importance == 0 takes w = 1 and skips nothing.  A NaN in a counted column makes that column's r scores NaN, and
+ * with them every entry of y_out.
+ * Independence of the block: z_j(n) and row j of y_out have the same bits whatever r is and whatever the other directions hold
+ * (direction 3 of an r = 32 call equals direction 0 of an r = 1 call given that one vector).
+ * Ordering of scores: a score depends on its column, its direction, center and d only -- not on K, N_r, col_offset, the run's position
+ * or the device.
+ * Ordering of apply (the guarantee of pfmi_pool_cross): no atomics; the terms of one run are added in an order that depends on (d, N_r)
+ * only -- not on K, col_offset, the run's position or the device; the runs' sums are added in run order on top of y_in, which is added
+ * first.  So contexts chained in run order, each passing its y_out to the next as y_in, return the bits of one context that holds all
+ * the runs.
+ * No pool: PFMI_ERR_STATE; importance != 0 without a PSIS result covering [col_offset, col_offset + K*N_r): PFMI_ERR_STATE;
+ * col_offset < 0, r outside [1, PFMI_POOL_APPLY_MAX_R], v or y_out NULL: PFMI_ERR_ARG. */
+#define PFMI_POOL_APPLY_MAX_R 32
+int32_t pfmi_pool_apply(pfmi_ctx *ctx, int64_t col_offset, int32_t importance, const double *center, int32_t r, const double *v,
+                        const double *y_in, double *y_out, double *scores);
 /* device pointer to the local pool's draws (d x K_local*N_r doubles, column-major, a column per draw; count = their number), for hosts
  * that keep the pool on the GPU.  The stream is idle on return.  Valid until the next pfmi_pool_build* on this ctx. */
 int32_t pfmi_pool_draws_dev(pfmi_ctx *ctx, void **dev_ptr, int64_t *count);

@@ -33,7 +33,7 @@ static int32_t pool_fill(pfmi_ctx *c) {
     return PFMI_OK;
 }
 
-// what the passes over the pool (pfmi_pool_moments / _cdf / _cross) check first: a pool, the entry point's own arguments (arg_error:
+// what the passes over the pool (pfmi_pool_moments / _cdf / _cross / _apply) check first: a pool, the entry point's own arguments (arg_error:
 // its complaint, or NULL), a col_offset >= 0 and, with importance weighting, PSIS weights on this ctx that cover the pool's columns
 // [col_offset, col_offset + K N_r) of the global pool.  arg_error exists to keep each entry point's message and the place of its
 // check between the pool's and the weights'; pfmi_pool_cross words the offset and its NULL output as ONE complaint, so for it the
@@ -163,6 +163,22 @@ int32_t pfmi_pool_cross(pfmi_ctx *c, int64_t col_offset, int32_t importance, con
     PF_TRY(upload_optional(c, c->cross, c_in, d * d, &d_carry));                   // accumulated in place
     PF_TRY(pf_launch_pool_cross(c, col_offset, importance, d_center, d_carry));
     PF_TRY(pf_download(c, c_out, c->cross.p, sizeof(double) * d * d));
+    return pf_stream_sync(c);
+}
+
+int32_t pfmi_pool_apply(pfmi_ctx *c, int64_t col_offset, int32_t importance, const double *center, int32_t r, const double *v,
+                        const double *y_in, double *y_out, double *scores) {
+    PF_CTX_MUT(c);
+    PF_TRY(pool_pass_check(c, "pool_apply", col_offset, importance,
+                           r >= 1 && r <= PFMI_POOL_APPLY_MAX_R && v && y_out ? nullptr : "r must be in [1, 32] and v, y_out non-NULL"));
+    const size_t plane = (size_t)r * (size_t)c->d;
+    const double *d_center, *d_v, *d_carry;
+    PF_TRY(upload_optional(c, c->pool_center, center, (size_t)c->d, &d_center));
+    PF_TRY(upload_optional(c, c->apply_v, v, plane, &d_v));
+    PF_TRY(upload_optional(c, c->apply_y, y_in, plane, &d_carry));                 // accumulated in place
+    PF_TRY(pf_launch_pool_apply(c, col_offset, importance, d_center, r, d_v, d_carry));
+    PF_TRY(pf_download(c, y_out, c->apply_y.p, sizeof(double) * plane));
+    if (scores) PF_TRY(pf_download(c, scores, c->apply_z.p, sizeof(double) * (size_t)c->K * (size_t)c->N_r * (size_t)r));
     return pf_stream_sync(c);
 }
 

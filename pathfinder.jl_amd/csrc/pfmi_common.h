@@ -275,6 +275,10 @@ struct pfmi_ctx {
     DevBuf pcdf_carry;             // its carry-in vector [nthr d]
     DevBuf cross;                  // pfmi_pool_cross: C [d d], both triangles (a carry-in is uploaded here and accumulated in place)
     DevBuf pool_center;            // the centre vector [d] of pfmi_pool_moments / pfmi_pool_cross (the calls are serialised on the ctx stream)
+    DevBuf apply_z;                // pfmi_pool_apply: the scores [K N_r][r]
+    DevBuf apply_part;             // its per-run sums [K][r d] (pool_apply_kernels.hip)
+    DevBuf apply_y;                // its result Y [r d] (a carry-in is uploaded here and accumulated in place)
+    DevBuf apply_v;                // its directions [r d]
 };
 
 // small host -> device upload on the ctx stream WITHOUT synchronising it (pinned arena); large blocks take the synchronous path
@@ -311,6 +315,10 @@ int32_t pf_launch_pool_cdf(pfmi_ctx *c, int64_t col_offset, int importance, int 
 // weighted cross moments of the ctx's pool into c->cross (d_center: device, d doubles or NULL; d_carry: device, d d doubles -- it may be
 // c->cross itself -- or NULL for zeros)
 int32_t pf_launch_pool_cross(pfmi_ctx *c, int64_t col_offset, int importance, const double *d_center, const double *d_carry);
+// scores of the ctx's pool against r directions into c->apply_z and the pooled second moment applied to them into c->apply_y (d_center:
+// device, d doubles or NULL; d_v: device, r d doubles; d_carry: device, r d doubles -- it may be c->apply_y itself -- or NULL for zeros)
+int32_t pf_launch_pool_apply(pfmi_ctx *c, int64_t col_offset, int importance, const double *d_center, int r, const double *d_v,
+                             const double *d_carry);
 // Test / tuning hooks (kernel selection, the RCCL stand-in, ...): a value set with pfmi_debug_set(), or -- ONLY when the process was
 // started with PFMI_DEBUG_HOOKS=1 -- the environment variable of that name.  A production process therefore never has its numerics or
 // its dlopen path changed by a stray environment variable.  NULL when unset.

@@ -1055,6 +1055,32 @@ function pool_cross(b::Batch; col_offset::Integer=0, importance::Bool=true, cent
 end
 
 """
+    pool_apply(b::Batch, V; col_offset=0, importance=true, center=nothing, carry=nothing, want_scores=false, ncolumns=0) -> Y (d x r) [, scores (r x ncolumns), ncolumns = K N_r]
+
+The weighted second moment of the engine's pool applied to the r <= 32 columns of `V` (d x r) on the device, the d x d matrix never
+formed: Y[:, j] = carry[:, j] + Σ (w t) (t' V[:, j]) with t = x - center, the runs added in run order on top of `carry` (the Y of the
+engines that own the earlier runs).  A column of Y does not depend on r or on the other columns of V.  (The column-major d x r matrices
+are the C ABI's v[j*d + i] and y[j*d + i]; the r x K N_r scores are its scores[(k*N_r + n)*r + j].)
+"""
+function pool_apply(b::Batch, V::Matrix{Float64}; col_offset::Integer=0, importance::Bool=true,
+                    center::Union{Nothing,Vector{Float64}}=nothing, carry::Union{Nothing,Matrix{Float64}}=nothing, want_scores::Bool=false,
+                    ncolumns::Integer=0)
+    _live(b.eng, b.gen)
+    r = size(V, 2)
+    size(V, 1) == b.dim && 1 <= r <= 32 || throw(ArgumentError("pool_apply: V must be d x r with 1 <= r <= 32"))
+    center === nothing || length(center) == b.dim || throw(ArgumentError("pool_apply: center must have length d"))
+    carry === nothing || size(carry) == (b.dim, r) || throw(ArgumentError("pool_apply: carry must be d x r"))
+    !want_scores || ncolumns > 0 || throw(ArgumentError("pool_apply: want_scores needs ncolumns = K N_r of this engine's pool"))
+    Y = Matrix{Float64}(undef, b.dim, r)
+    Z = want_scores ? Matrix{Float64}(undef, r, ncolumns) : nothing
+    check(ccall((:pfmi_pool_apply, libpfmi), Int32,
+                (Ptr{Cvoid}, Int64, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                b.eng.ptr, col_offset, importance, center === nothing ? Ptr{Float64}(C_NULL) : pointer(center), r, V,
+                carry === nothing ? Ptr{Float64}(C_NULL) : pointer(carry), Y, Z === nothing ? Ptr{Float64}(C_NULL) : pointer(Z)))
+    return want_scores ? (Y, Z) : Y
+end
+
+"""
     importance_covariance(result::Pathfinder.MultiPathfinderResult; importance=true)
 
 Posterior `mean`, `cov`, `corr`, `ess`, `ncandidates` and `pareto_shape` from ALL pooled candidates under their PSIS weights (uniform

@@ -386,6 +386,11 @@ class MultiPathfinderResult:        # src/multipath.jl:31-44
         """the (d, d) correlation matrix of covariance(): importance_covariance(self).corr"""
         return importance_covariance(self, importance=importance).corr
 
+    def lowrank_covariance(self, rank, **kw):
+        """the top `rank` eigenpairs of the importance-weighted posterior covariance plus its residual diagonal, the (d, d) matrix
+        never formed: importance_lowrank_covariance(self, rank, **kw)"""
+        return importance_lowrank_covariance(self, rank, **kw)
+
     def __str__(self):                  # Base.show, src/multipath.jl:46-65
         lines = ["Multi-path Pathfinder result", f"  runs: {len(self.pathfinder_results)}", f"  draws: {self.draws.shape[1]}"]
         if self.psis_result is not None:
@@ -1050,6 +1055,128 @@ def importance_covariance(result, *, importance=True):
     cov, corr = _covariance_from_sums(_cross_of_pool(passes, mean), c1, W)
     S = len(result.pathfinder_results) * result.pathfinder_results[0].ndraws_per_run
     return ImportanceCovariance(mean, cov, corr, float(W * W / wtot[1]), S, pareto_shape)
+
+
+@dataclass
+class LowRankCovariance:
+    """Diagonal plus low rank from the pooled candidates under their PSIS weights (importance_lowrank_covariance): the top eigenpairs
+    of the posterior covariance and what they leave on the diagonal, diag(diag) + U diag(eigenvalues) U'."""
+    mean: np.ndarray                # (d,) sum w x / W
+    var: np.ndarray                 # (d,) the diagonal of the pooled covariance: ImportanceSummary.var
+    eigenvalues: np.ndarray         # (rank,) Ritz values, descending
+    eigenvectors: np.ndarray        # (d, rank) Ritz vectors U, orthonormal columns
+    diag: np.ndarray                # (d,) max(var - sum_j eigenvalues_j U_ij^2, 0)
+    residuals: np.ndarray           # (rank,) |cov U_j - eigenvalues_j U_j|_2: an eigenvalue of cov lies within residuals_j of eigenvalues_j
+    passes: int                     # applications of the covariance to the block
+    converged: bool                 # max residuals <= tol * eigenvalues[0] within max_passes
+    ess: float                      # W^2 / sum w^2
+    ncandidates: int                # S
+    pareto_shape: float             # k-hat of the pooled PSIS (NaN for uniform weights)
+
+    def dense(self):
+        """(d, d): diag(diag) + U diag(eigenvalues) U'"""
+        U = self.eigenvectors
+        return np.diag(self.diag) + (U * self.eigenvalues) @ U.T
+
+    def mul(self, x):
+        """dense() @ x in O(d rank) per column; x (d,) or (d, N)"""
+        x = np.asarray(x, dtype=np.float64)
+        U = self.eigenvectors
+        return (self.diag * x.T).T + U @ (self.eigenvalues * (U.T @ x).T).T
+
+    def _capacitance(self):
+        """(D^-1 U, the Cholesky factor of Lambda^-1 + U' D^-1 U) of the Woodbury identity; PosDefException unless diag > 0 and
+        eigenvalues > 0"""
+        if not np.all(self.diag > 0):
+            raise PosDefException(f"LowRankCovariance: diag[{int(np.flatnonzero(~(self.diag > 0))[0])}] is not positive")
+        if not np.all(self.eigenvalues > 0):
+            raise PosDefException("LowRankCovariance: an eigenvalue is not positive")
+        DU = (self.eigenvectors.T / self.diag).T
+        return DU, np.linalg.cholesky(np.diag(1.0 / self.eigenvalues) + self.eigenvectors.T @ DU)
+
+    def solve(self, x):
+        """dense()^-1 x by the Woodbury identity on the host, O(d rank) per column; x (d,) or (d, N).  PosDefException when a diag
+        entry is not positive."""
+        x = np.asarray(x, dtype=np.float64)
+        DU, L = self._capacitance()
+        Dx = (x.T / self.diag).T
+        y = np.linalg.solve(L.T, np.linalg.solve(L, DU.T @ x))
+        return Dx - DU @ y
+
+    @property
+    def logdet(self):
+        """log det dense() = sum log diag + sum log eigenvalues + log det(Lambda^-1 + U' D^-1 U)"""
+        _, L = self._capacitance()
+        return float(np.sum(np.log(self.diag)) + np.sum(np.log(self.eigenvalues)) + 2.0 * np.sum(np.log(np.diagonal(L))))
+
+
+def _apply_of_pool(apply_passes, center, V):
+    """the engines' apply passes chained in run order through the carry: apply_passes[e](center, V, carry) -> (r, d)"""
+    Y = None
+    for apply_pass in apply_passes:
+        Y = apply_pass(center, V, Y)                                # the carry of the next engine
+    return Y
+
+
+def _lowrank_from_apply(apply, d, rank, *, oversample=8, tol=1e-6, max_passes=30, seed=0):
+    """Block subspace iteration for the top `rank` eigenpairs of a symmetric positive semi-definite d x d operator given only as
+    apply(Q (d, b)) -> operator @ Q (d, b).  b = min(d, 32, rank + oversample) columns; start: the thin QR of
+    default_rng(seed).standard_normal((d, b)).  Per pass Y = apply(Q), B = (Q'Y + (Q'Y)') / 2, eigh(B) sorted descending gives the
+    Ritz values lam and vectors U = Q E, and the same Y the residuals rho_j = |Y E_j - lam_j U_j|_2; stop when
+    max_{j < rank} rho_j <= tol lam_1 or after max_passes, else Q = qr(Y).  Returns (lam (rank,), U (d, rank), rho (rank,), passes,
+    converged).  ValueError when Y is not finite or rank is outside [1, min(d, 32)]."""
+    if not 1 <= rank <= min(d, 32):
+        raise ValueError(f"lowrank_covariance: rank must be in [1, min(d, 32)] = [1, {min(d, 32)}], got {rank}")
+    if oversample < 0 or max_passes < 1:
+        raise ValueError("lowrank_covariance: oversample must be >= 0 and max_passes >= 1")
+    b = min(d, 32, rank + int(oversample))
+    Q = np.linalg.qr(np.random.default_rng(seed).standard_normal((d, b)))[0]
+    passes, converged = 0, False
+    while True:
+        Y = np.asarray(apply(Q), dtype=np.float64)
+        passes += 1
+        if not np.all(np.isfinite(Y)):
+            raise ValueError("lowrank_covariance: the covariance applied to the block is not finite (a non-finite draw under a non-zero weight)")
+        B = Q.T @ Y
+        lam, E = np.linalg.eigh((B + B.T) / 2)
+        lam, E = lam[::-1], E[:, ::-1]
+        Uv = Q @ E
+        rho = np.linalg.norm(Y @ E - Uv * lam, axis=0)
+        converged = bool(np.max(rho[:rank]) <= tol * lam[0])
+        if converged or passes >= max_passes:
+            return lam[:rank].copy(), np.ascontiguousarray(Uv[:, :rank]), rho[:rank].copy(), passes, converged
+        Q = np.linalg.qr(Y)[0]
+
+
+def importance_lowrank_covariance(result, rank, *, importance=True, oversample=8, tol=1e-6, max_passes=30, seed=0):
+    """The top `rank` <= min(d, 32) eigenpairs of the importance-weighted posterior covariance of ALL candidates of a multipathfinder
+    result, and the diagonal they leave: diagonal plus low rank, the metric Pathfinder itself uses at large d, for the mixture of fits.
+    The (d, d) covariance of importance_covariance is never formed: a block subspace iteration (_lowrank_from_apply) applies it to
+    b = min(d, 32, rank + oversample) vectors per pass through Engine.pool_apply -- two tall-skinny contractions over the pool on the
+    matrix cores, 4 d b flops per draw instead of d^2 -- as cov V = (pool apply about the mean) / W - delta (delta' V), delta the centred
+    first moment over W.  The pool is rebuilt and weighted as in importance_summary; mean and var have the bits of its mean and var.  The
+    engines are chained in run order through the carry and the host algebra sees the same bits from one engine or several, so the
+    whole result is bit-identical for any number of engines.  importance=False, or a result without psis_result: uniform weights.
+    ValueError for a rank outside [1, min(d, 32)], for W == 0 and for a non-finite draw under a non-zero weight; StaleHandleError when
+    the engines hold newer fits."""
+    owners, weighted, pareto_shape = _rebuild_pool(result, importance)
+    _, wtot, W, mean = _first_moments(owners, weighted)
+    if not W > 0:
+        raise ValueError("lowrank_covariance: the total weight W is 0")
+    _, c1_b, c2_b, _ = _moment_pass(owners, weighted, mean)
+    delta = _combine_moments(c1_b) / W
+    var = _combine_moments(c2_b) / W - delta ** 2
+    d = mean.shape[0]
+    passes = [(lambda cen, V, carry, eng=eng, off=off: eng.pool_apply(off, weighted, cen, V, carry)) for eng, off in owners]
+
+    def apply(Q):
+        Y = _apply_of_pool(passes, mean, np.ascontiguousarray(Q.T)).T
+        return Y / W - delta[:, None] * (delta @ Q)[None, :]
+
+    lam, Uv, rho, npass, converged = _lowrank_from_apply(apply, d, rank, oversample=oversample, tol=tol, max_passes=max_passes, seed=seed)
+    diag = np.maximum(var - (Uv * Uv) @ lam, 0.0)
+    S = len(result.pathfinder_results) * result.pathfinder_results[0].ndraws_per_run
+    return LowRankCovariance(mean, var, lam, Uv, diag, rho, npass, converged, float(W * W / wtot[1]), S, pareto_shape)
 
 
 def _f64_key(x):

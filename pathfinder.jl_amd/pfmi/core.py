@@ -560,6 +560,25 @@ class Engine:
         check(self.L.pfmi_pool_cross(self.ctx, int(col_offset), int(bool(importance)), _d(center), _d(carry), _d(out)))
         return out
 
+    def pool_apply(self, col_offset=0, importance=True, center=None, V=None, carry=None, want_scores=False):
+        """The weighted second moment of this engine's pool applied to the r <= 32 directions V (r, d) on the device, the (d, d) matrix
+        never formed (include/pfmi.h pfmi_pool_apply): Y[j] = carry[j] + sum over the local runs, in run order, of sum_n (w t) z_j(n)
+        with t = x - center and the scores z_j(n) = t(n) . V[j]; weights and the zero-weight rule as in pool_moments.  Returns Y (r, d),
+        or (Y, scores (K N_r, r)) with want_scores.  A row of Y and a column of scores do not depend on r or on the other directions.
+        carry (r, d): the Y of the engines that own the earlier runs, added first; chaining engines in run order gives the bits of one
+        engine that holds all the runs."""
+        d = self.d
+        center = _f64_of_shape("pool_apply", "center", center, (d,))
+        V = _f64_of_shape("pool_apply", "V", V, ("r", d))
+        if V is None:
+            raise ValueError("pool_apply: V must have shape (r, d)")
+        r = V.shape[0]
+        carry = _f64_of_shape("pool_apply", "carry", carry, (r, d))
+        out = np.empty((r, d))
+        scores = np.empty((self.K * self.N_r, r)) if want_scores else None
+        check(self.L.pfmi_pool_apply(self.ctx, int(col_offset), int(bool(importance)), _d(center), r, _d(V), _d(carry), _d(out), _d(scores)))
+        return (out, scores) if want_scores else out
+
     def pool_draws_dev(self):
         """(device pointer, count) of this engine's pool draws: d x K N_r doubles, column-major (pfmi_pool_draws_dev)"""
         p, n = C.c_void_p(), C.c_int64()
