@@ -290,7 +290,8 @@ int32_t pf_launch_mixture_logpdf(pfmi_ctx *c, int K, const int32_t *d_points, in
         int64_t ng = (8 * (int64_t)ncu + ntiles - 1) / ntiles;
         if (ng < 1) ng = 1;
         if (ng > K) ng = K;
-        const int cpb = (int)((K + ng - 1) / ng);
+        int cpb = (int)((K + ng - 1) / ng);
+        if (const char *f = pf_debug_get("PFMI_MIXTURE_CPB")) { const int v = atoi(f); cpb = v < 1 ? 1 : (v > K ? K : v); }   // test hook: the group size
         const int ngroups = (K + cpb - 1) / cpb;
         dim3 grid((unsigned)ntiles, (unsigned)ngroups);
         int32_t rc = PFMI_OK;

@@ -16,81 +16,9 @@ from scipy.special import logsumexp
 import margins as mg
 from gpu_common import CASES, _targets
 from helpers import ROOT, STANDIN_LIB, fit_seeds, make_traces
+from mixture_reference import _chol_ld, _solve_ld, _top_eig, ref_logpdf  # noqa: F401  (the extended-precision reference)
 
 pytestmark = pytest.mark.gpu
-
-LD = np.longdouble
-
-
-# ---- extended-precision reference ----------------------------------------------------------------------------------------------------
-def _solve_ld(M, R):
-    """M^{-1} R by Gaussian elimination with partial pivoting in long double; also log|det M|"""
-    M = M.astype(LD).copy()
-    R = R.astype(LD).copy()
-    m = M.shape[0]
-    logdet = LD(0)
-    for c in range(m):
-        piv = c + int(np.argmax(np.abs(M[c:, c])))
-        if piv != c:
-            M[[c, piv]] = M[[piv, c]]
-            R[[c, piv]] = R[[piv, c]]
-        logdet += np.log(np.abs(M[c, c]))
-        f = M[c + 1:, c] / M[c, c]
-        M[c + 1:, c:] -= np.outer(f, M[c, c:])
-        R[c + 1:] -= np.outer(f, R[c])
-    for c in range(m - 1, -1, -1):
-        R[c] = (R[c] - M[c, c + 1:] @ R[c + 1:]) / M[c, c]
-    return R, logdet
-
-
-def _chol_ld(S):
-    n = S.shape[0]
-    L = np.zeros_like(S)
-    for j in range(n):
-        v = S[j, j] - L[j, :j] @ L[j, :j]
-        L[j, j] = np.sqrt(v)
-        L[j + 1:, j] = (S[j + 1:, j] - L[j + 1:, :j] @ L[j, :j]) / L[j, j]
-    return L
-
-
-def ref_logpdf(f, X):
-    """logpdf(MvNormal(mu, diag(alpha) + B D B'), X) in long double: dense Sigma and a Cholesky for d <= 64, the Woodbury identity
-    (A + B D B')^{-1} = A^{-1} - A^{-1} B (I + D G)^{-1} D B' A^{-1}, G = B' A^{-1} B, det = det A det(I + D G) above"""
-    a, B, D, mu = (f[k].astype(LD) for k in ("alpha", "B", "D", "mu"))
-    d, m = B.shape
-    Z = np.asarray(X, dtype=LD) - mu[:, None]
-    if d <= 64:
-        L = _chol_ld(np.diag(a) + B @ D @ B.T)
-        Y = Z.copy()
-        for i in range(d):                                # forward substitution L y = z
-            Y[i] = (Y[i] - L[i, :i] @ Y[:i]) / L[i, i]
-        quad = np.sum(Y * Y, axis=0)
-        logdet = 2 * np.sum(np.log(np.diag(L)))
-    else:
-        AiB = B / a[:, None]
-        quad = np.sum(Z * Z / a[:, None], axis=0)
-        logdet = np.sum(np.log(a))
-        if m:
-            M = np.eye(m, dtype=LD) + D @ (B.T @ AiB)
-            U = AiB.T @ Z                                 # B' A^{-1} z
-            S, ld = _solve_ld(M, D @ U)
-            quad = quad - np.sum(U * S, axis=0)
-            logdet = logdet + ld
-    return (-(d * np.log(2 * LD(np.pi)) + logdet) / 2 - quad / 2).astype(np.float64)
-
-
-def _top_eig(f):
-    """(lambda_max, v_max) of Sigma = diag(alpha) + B D B'"""
-    a, B, D = f["alpha"], f["B"], f["D"]
-    d = len(a)
-    if d <= 512:
-        lam, V = np.linalg.eigh(np.diag(a) + B @ D @ B.T)
-        return lam[-1], V[:, -1]
-    v = np.random.default_rng(0).normal(size=d)
-    for _ in range(500):                                  # power iteration on the low-rank-plus-diagonal operator
-        w = a * v + B @ (D @ (B.T @ v))
-        v = w / np.linalg.norm(w)
-    return float(v @ (a * v + B @ (D @ (B.T @ v)))), v
 
 
 # ---- fits and points -----------------------------------------------------------------------------------------------------------------

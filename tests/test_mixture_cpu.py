@@ -124,9 +124,7 @@ def test_stale_component_raises():
 
 
 # ---- the main mixture kernel stays in registers --------------------------------------------------------------------------------------
-@pytest.mark.parametrize("kpad", [12, 20])
-@pytest.mark.parametrize("stage", ["true", "false"])
-def test_mixture_mfma_kernel_has_no_scratch(kpad, stage):
+def _mfma_kernel_resources(kpad, stage):
     sys.path.insert(0, os.path.join(ROOT, "pathfinder.jl_amd", "tools"))
     import kernel_resources as kr
     import pfmi
@@ -137,3 +135,17 @@ def test_mixture_mfma_kernel_has_no_scratch(kpad, stage):
     r = t[hits[0]]
     assert r["private_segment_fixed_size"] == 0 and r["vgpr_spill_count"] == 0, r
     assert r["vgpr_count"] <= 256, r                           # two waves per SIMD (512-thread workgroups)
+    return r
+
+
+@pytest.mark.parametrize("kpad", [12, 20])
+@pytest.mark.parametrize("stage", ["true", "false"])
+def test_mixture_mfma_kernel_has_no_scratch(kpad, stage):
+    _mfma_kernel_resources(kpad, stage)
+
+
+# with the rows above: every instantiation the launcher can reach, (4,T) (8,T) (12,T) (16,T) (16,F) (20,T) (20,F) (32,T) (32,F)
+# (kpad <= 12 always stages at d <= 1024: <4|8|12, false> are compiled but never launched)
+@pytest.mark.parametrize("kpad,stage", [(4, "true"), (8, "true"), (16, "true"), (16, "false"), (32, "true"), (32, "false")])
+def test_mixture_mfma_kernel_reachable_instantiations_have_no_scratch(kpad, stage):
+    _mfma_kernel_resources(kpad, stage)
