@@ -20,6 +20,9 @@
  *   StatsBase.sample (0.33.17-0.34; replaced by this repo's own deterministic fixed-point
  *   inverse-CDF sampler -- see pfo_sample_weighted).  The reference's own tests only check
  *   sum(weights) ~ 1 and membership for those (test/resample.jl:91-109, 8-60).
+ * The PSIS tail selection follows the call `PSIS.psis(log_ratios)` at src/resample.jl:78: PSIS.jl orders the log ratios with
+ *   Julia's default sort, i.e. by isless (-0.0 < +0.0, every NaN last), and the sort is stable; cmp_idx_by_val is that order
+ *   followed by the index, a total order for every input (tests/test_oracle_elbo_psis.py pins the signed-zero and NaN cases).
  *
  * Layout convention: every matrix is column-major Float64 (Julia default); A[i + ld*j].
  */
@@ -582,11 +585,21 @@ uint64_t pfo_rand_u64(uint64_t seed, uint64_t t, uint32_t stream) {
 /* shape prior-adjusted (k M + 5)/(M + 10)) and identically by ArviZ/loo.  reff = 1.            */
 /* logw (S) in: log ratios; out: smoothed + normalised log weights.  weights = exp(logw).      */
 /* ------------------------------------------------------------------------------------------ */
+/* Total order of the sort: Julia's isless on the value (PSIS.psis at src/resample.jl:78 sorts the log ratios with the default   */
+/* order, i.e. isless: -0.0 before +0.0, every NaN after +Inf and all NaNs equal), then the index (a stable sort).               */
+/* rank 0: not a NaN, 1: NaN.  Among non-NaN values `<` decides, and a +-0.0 pair is split by the sign bit.                      */
+static int isless_cmp(double x, double y) {
+    int nx = (x != x), ny = (y != y);
+    if (nx || ny) return nx - ny;
+    if (x < y) return -1;
+    if (x > y) return 1;
+    return (signbit(y) != 0) - (signbit(x) != 0);          /* equal values: only -0.0 / +0.0 differ in sign */
+}
 static int cmp_idx_by_val(const void *a, const void *b, void *ctx) {
     const double *v = (const double *)ctx;
     long ia = *(const long *)a, ib = *(const long *)b;
-    if (v[ia] < v[ib]) return -1;
-    if (v[ia] > v[ib]) return 1;
+    int c = isless_cmp(v[ia], v[ib]);
+    if (c) return c;
     return (ia > ib) - (ia < ib);   /* stable tie-break by index */
 }
 long pfo_psis_tail_length(long S) {

@@ -26,9 +26,14 @@
 #endif
 #define TAILCAP 4096
 
-__device__ __forceinline__ uint64_t pf_key_of(double x) {   // order-preserving map double -> u64
+// order-preserving map double -> u64 in the order of Julia's isless (what PSIS.jl's sort uses): -0.0 below +0.0, and every NaN,
+// whatever its sign bit and payload, keyed as ONE value above +Inf (the key of the positive quiet NaN: pf_val_of gives a NaN back).
+// It stays below the padding sentinel ~0ull of the sorts.
+#define PF_KEY_NAN 0xFFF8000000000000ull
+__device__ __forceinline__ uint64_t pf_key_of(double x) {
     uint64_t b = (uint64_t)__double_as_longlong(x);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+    const uint64_t k = (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+    return (x != x) ? PF_KEY_NAN : k;
 }
 __device__ __forceinline__ double pf_val_of(uint64_t k) {
     uint64_t b = (k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k;

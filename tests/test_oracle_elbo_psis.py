@@ -325,3 +325,42 @@ def test_oracle_single_path_recovers_the_reference_literal_covariance():
         B, D = po.lbfgs_inverse_hessian(alpha_all[l], S, Y)
         Sfit = np.diag(alpha_all[l]) + B @ D @ B.T
         assert np.linalg.norm(Sfit - Sigma) <= 0.1 * max(np.linalg.norm(Sfit), np.linalg.norm(Sigma))
+
+
+def test_psis_sort_is_isless_then_index_on_signed_zeros():
+    """PSIS.psis (src/resample.jl:78) sorts with isless, and isless(-0.0, 0.0) is true: of forty log ratios alternating +0.0 / -0.0
+    across the cutoff, ten of them in the tail, the ten +0.0 with the largest indices are smoothed -- not the ten largest indices of
+    all forty, which is what a comparator built on `<` and `>` alone selects."""
+    import psis_reference as pr
+    lr = pr.case_lr("signed_zeros_1000")
+    S, M = len(lr), pr.tail_length(len(lr))
+    assert (S, M) == (1000, 95)
+    zeros = np.flatnonzero(lr == 0.0)
+    assert len(zeros) == 40 and np.sum(lr > 0.0) == M - 10
+    plus = zeros[~np.signbit(lr[zeros])]
+    expect = set(plus[-10:].tolist())                                   # (key, index) order
+    by_index_alone = set(zeros[-10:].tolist())
+    assert expect != by_index_alone
+    tail, cut = pr.tail_indices(lr)
+    assert set(tail.tolist()) & set(zeros.tolist()) == expect and cut == plus[-11]
+    lw, w, k, M2 = po.psis(lr)
+    assert M2 == M and np.isfinite(k)
+    raw = lw[zeros].min()                                               # an unsmoothed zero keeps 0 - logsumexp; smoothing only raises
+    assert np.sum(lw[zeros] == raw) == 30
+    assert set(zeros[lw[zeros] > raw].tolist()) == expect
+
+
+@pytest.mark.parametrize("negative", [False, True])
+@pytest.mark.parametrize("S", [30, 1000, 64000])
+def test_psis_nan_input_returns_all_nan(S, negative):
+    """isless puts every NaN last, whatever its sign bit: the NaN is in the tail, nothing is fitted, and the logsumexp spreads it.
+    The comparator stays a total order, so the sort is defined (the call returns) wherever the NaN sits."""
+    import psis_reference as pr
+    rng = np.random.default_rng(S)
+    for where in (0, S // 2, S - 1):
+        lr = rng.normal(size=S) * 1.5
+        lr[where] = pr._nan(negative)
+        assert np.signbit(lr[where]) == negative
+        lw, w, k, M = po.psis(lr)
+        assert M == pr.tail_length(S) and np.isnan(k)
+        assert np.all(np.isnan(lw)) and np.all(np.isnan(w))
