@@ -42,6 +42,9 @@
 #ifndef QF_ABLATE
 #define QF_ABLATE 0
 #endif
+#ifndef QF_PHILOX_HOIST
+#define QF_PHILOX_HOIST 1              // 0: every generator call of the block loop runs all of its rounds (A/B builds)
+#endif
 #ifndef QF_NG2_MAXKC
 #define QF_NG2_MAXKC 20                // two groups per wave up to this KC (round 2: 12; KC = 16, 20 take the register-lean block body)
 #endif
@@ -78,6 +81,12 @@ __device__ __forceinline__ double qf_mfma4(double a, double b, double c) { retur
 
 // per-fit constant block in LDS (doubles): [0] C0  [1] mu_0  [2] s_0  [3] -   then v[KC], M[KC][KC], t0[RPAD], Nn[RPAD][KC], vh0[KC]
 __host__ __device__ constexpr int qf_nconst(int KC, int RPAD) { return 4 + KC + KC * KC + RPAD + RPAD * KC + KC; }
+
+// Doubles of LDS for the head transform's A operands.  Two groups per wave at KC <= 12 have no registers to spare in the block loop
+// (256 VGPRs, two waves per SIMD) and use the four operands of a lane only in block 0 of each batch: the prologue parks them in LDS, one
+// 16 x 16 tile in lane order, and the peeled first block reads them back (conflict-free ds_read_b64).  Every other instantiation keeps
+// them in registers (KC <= 12, one group) or fetches them from L2 when a special block comes up (KC >= 16, two groups).
+__host__ __device__ constexpr int qf_head_lds(int KC, int NG) { return (NG == 2 && KC < 16) ? 256 : 0; }
 
 // a_i (target diagonal weight), c_i = mu_i - m_i for row i
 template <int TGT>
@@ -118,6 +127,8 @@ __global__ __launch_bounds__(QF_THREADS) void pf_elbo_qf_kernel(ElboArgs A, int 
     // register-lean body (two groups, KC >= 16): there the fused operand needs both row scalars at once, and the extra LDS waits and
     // wait states cost more than the saved f64 adds (tools/qf_issue_count.py at <20, 2, 0, 2>)
     constexpr bool FOLD = !(NG == 2 && KC >= 16);
+    // the block loop's generator calls start from the per-draw share of Philox rounds 1 - 3 (pf_philox4x32_hoisted: the same words)
+    constexpr bool PHX = QF_PHILOX_HOIST != 0;
     constexpr int PRE = (QF_CHB * 16 * KC + QF_THREADS - 1) / QF_THREADS;      // prefetch registers per thread (streaming)
     const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63, q = lane >> 4, c = lane & 15, l3 = lane & 3;
     const int d = A.d, nblk = (d + 15) >> 4;
@@ -167,7 +178,8 @@ __global__ __launch_bounds__(QF_THREADS) void pf_elbo_qf_kernel(ElboArgs A, int 
     double *t_s = lds + fix_off;                   // [KC][KC]
     double *cn_s = t_s + KC * KC;                  // [NC]
     double *g_s = cn_s + NC;                       // [RPAD][RPAD]
-    double2 *icdf = reinterpret_cast<double2 *>(g_s + RPAD * RPAD + ((KC * KC + NC + RPAD * RPAD) & 1));   // [2 * 608] inverse-CDF table + guard
+    double *h_s = g_s + RPAD * RPAD;               // [4][64] head-transform operands, lane order (two groups per wave at KC <= 12 only)
+    double2 *icdf = reinterpret_cast<double2 *>(h_s + qf_head_lds(KC, NG) + ((KC * KC + NC + RPAD * RPAD) & 1));   // [2 * 608] inverse-CDF table + guard
 
     const double *Vh = A.vh + (size_t)p * d * KC, *mu = A.mu + (size_t)p * d, *sqa = A.sqrt_alpha + (size_t)p * d;
     auto stage_direct = [&](int ck, int buf) {
@@ -230,7 +242,8 @@ __global__ __launch_bounds__(QF_THREADS) void pf_elbo_qf_kernel(ElboArgs A, int 
     const int rho = 4 * (c & 3) + (c >> 2);
     // (two groups per wave at KC >= 16 need the registers: there the operands are fetched when a special block comes up -- L2, twice per
     // 16-draw group -- instead of living in 48 VGPRs for the whole kernel)
-    constexpr bool HREG = !(NG == 2 && KC >= 16);
+    constexpr bool HLDS = qf_head_lds(KC, NG) > 0;
+    constexpr bool HREG = !(NG == 2 && KC >= 16) && !HLDS;
     const double *Vc = A.vchol + (size_t)p * KC * KC;
     auto head_op = [&](const int which, const int r) -> double {          // which: 0 = H00, 1 = H10, 2 = H11
         const int b = 4 * q + r;
@@ -250,7 +263,12 @@ __global__ __launch_bounds__(QF_THREADS) void pf_elbo_qf_kernel(ElboArgs A, int 
             a_h11[HREG ? r : 0] = (KC > 16) ? head_op(2, r) : 0.0;
         }
     }
+    if (HLDS && wv == 0) {                                              // (KC < 16: H00 only; the same values in every wave)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) h_s[r * 64 + lane] = head_op(0, r);
+    }
     auto hop = [&](const int which, const int r) -> double {
+        if (HLDS) return h_s[r * 64 + lane];
         if (HREG) return which == 0 ? a_h00[HREG ? r : 0] : (which == 1 ? a_h10[HREG ? r : 0] : a_h11[HREG ? r : 0]);
         return head_op(which, r);
     };
@@ -275,8 +293,11 @@ __global__ __launch_bounds__(QF_THREADS) void pf_elbo_qf_kernel(ElboArgs A, int 
     for (int lb = 0; lb < nlb; ++lb) {
         bool pseudo[NG], active[NG];
         int sl[NG];
-        int64_t nl[NG];
-        uint32_t n[NG];
+        int grp[NG];                                                // wave-uniform; the draw of lane column c is 16 grp + c
+        pf_philox_inv pinv[NG];                                     // the draw's share of Philox rounds 1 - 3 (pfmi_common.h)
+        // Philox counter word 0 of lane column c of group g.  Formed where it is used: the block loop needs it only on the refinement
+        // path (probability 2^-19 per normal), its generator calls start from pinv[g]
+        auto draw_of = [&](const int g) -> uint32_t { return (uint32_t)(A.n0 + ((int64_t)grp[g] * 16 + c)); };
         double accw[NG][NT], acc3[NG][NT], acc4[NG][TR > 0 ? TR : 1];
         double usq[NG], q12[NG], z00[NG], u0[NG][4];
         bool any_active = false, any_pseudo = false, any_real = false;
@@ -284,10 +305,14 @@ __global__ __launch_bounds__(QF_THREADS) void pf_elbo_qf_kernel(ElboArgs A, int 
         for (int g = 0; g < NG; ++g) {
             sl[g] = (lb * QF_WAVES + wv) * NG + g;                  // wave-uniform slot
             pseudo[g] = sl[g] < npg;
-            const int grp = g_begin + sl[g] - npg;
-            active[g] = pseudo[g] || grp < g_end;
-            nl[g] = (int64_t)grp * 16 + c;
-            n[g] = (uint32_t)(A.n0 + nl[g]);
+            grp[g] = g_begin + sl[g] - npg;
+            active[g] = pseudo[g] || grp[g] < g_end;
+            if (PHX) {
+                pinv[g] = pf_philox_draw_invariants(draw_of(g), k0, k1);
+                // (register-lean body: the words pinned in registers, or part of them is formed again in every block -- one more VALU per
+                //  block and 8 B more scratch at <20, 2, 0, 2>; the other bodies keep them live without it and measure 0.2 % faster so)
+                if constexpr (NG == 2 && KC >= 16) asm volatile("" : "+v"(pinv[g].C), "+v"(pinv[g].D), "+v"(pinv[g].E), "+v"(pinv[g].F));
+            }
             any_active |= active[g]; any_pseudo |= pseudo[g]; any_real |= active[g] && !pseudo[g];
 #pragma unroll
             for (int T = 0; T < NT; ++T) { accw[g][T] = 0.0; acc3[g][T] = 0.0; }
@@ -304,16 +329,20 @@ __global__ __launch_bounds__(QF_THREADS) void pf_elbo_qf_kernel(ElboArgs A, int 
         // one group at d = 10^4; with no MFMA / VALU co-issue on gfx950 there is nothing to hide the look-ups behind.)
         struct Pend { uint32_t x[4]; double dp[4]; double2 c01[4], c23[4]; };
         const uint32_t icdf_adj = pf_icdf_adj_bfe<PF_ICDF_NB_LDS>(icdf);
-        auto gen_issue = [&](const int g, const int blk, Pend &P) {
+        auto gen_issue = [&](const int g, const int blk, const uint64_t t, Pend &P) {
+            auto words = [&](uint32_t (&x)[4]) {
+                if (PHX) pf_philox4x32_hoisted<PF_NORMAL_ROUNDS>(pinv[g], t, k0, k1, x);
+                else pf_philox_normals(draw_of(g), (uint32_t)(blk * 4 + q), 0u, 0u, k0, k1, x);
+            };
 #if QF_ABLATE == 1                     // ablation (timing experiments only): no generator at all
 #pragma unroll
-            for (int r = 0; r < 4; ++r) { P.x[r] = 0x40000000u | (n[g] + blk); P.dp[r] = 1e-3 * (blk + r); P.c01[r] = make_double2(0.1, 0.2); P.c23[r] = make_double2(0.3, 0.4); }
+            for (int r = 0; r < 4; ++r) { P.x[r] = 0x40000000u | (draw_of(g) + blk); P.dp[r] = 1e-3 * (blk + r); P.c01[r] = make_double2(0.1, 0.2); P.c23[r] = make_double2(0.3, 0.4); }
 #elif QF_ABLATE == 2                   // ablation: Philox only, no table look-up
-            pf_philox_normals(n[g], (uint32_t)(blk * 4 + q), 0u, 0u, k0, k1, P.x);
+            words(P.x);
 #pragma unroll
             for (int r = 0; r < 4; ++r) { P.dp[r] = (double)P.x[r] * 0x1p-32; P.c01[r] = make_double2(0.1, 0.2); P.c23[r] = make_double2(0.3, 0.4); }
 #else
-            pf_philox_normals(n[g], (uint32_t)(blk * 4 + q), 0u, 0u, k0, k1, P.x);
+            words(P.x);
 #pragma unroll
             for (int r = 0; r < 4; ++r) pf_icdf_issue_bfe<PF_ICDF_NB_LDS>(P.x[r], icdf_adj, P.dp[r], P.c01[r], P.c23[r]);
 #endif
@@ -397,8 +426,8 @@ __global__ __launch_bounds__(QF_THREADS) void pf_elbo_qf_kernel(ElboArgs A, int 
                 // normals of rows 16 blk + 4q + {0..3} of draw n[g], head transform included
                 auto normals = [&](const int g, const int blk, double (&z)[4]) {
                     uint32_t x[4];
-                    pf_philox_normals(n[g], (uint32_t)(blk * 4 + q), 0u, 0u, k0, k1, x);
-                    pf_icdf4(x, n[g], (uint32_t)(blk * 4 + q), 0u, k0, k1, icdf, z);
+                    pf_philox_normals(draw_of(g), (uint32_t)(blk * 4 + q), 0u, 0u, k0, k1, x);
+                    pf_icdf4(x, draw_of(g), (uint32_t)(blk * 4 + q), 0u, k0, k1, icdf, z);
                     if (blk == nblk - 1) {
 #pragma unroll
                         for (int r = 0; r < 4; ++r) z[r] = (blk * 16 + 4 * q + r < d) ? z[r] : 0.0;
@@ -428,7 +457,7 @@ __global__ __launch_bounds__(QF_THREADS) void pf_elbo_qf_kernel(ElboArgs A, int 
 #pragma unroll
                     for (int r = 0; r < 4; ++r) z[r] = pf_icdf_finish(P.x[r], P.dp[r], P.c01[r], P.c23[r]);
                     if (__builtin_expect(__any(pf_icdf_miss4(P.x)), 0))          // probability 2^-19 per normal
-                        pf_icdf4_fix(P.x, n[g], (uint32_t)(blk * 4 + q), 0u, k0, k1, z);
+                        pf_icdf4_fix(P.x, draw_of(g), (uint32_t)(blk * 4 + q), 0u, k0, k1, z);
                     if (SPECIAL) {
                         if (blk == nblk - 1) {                                   // rows >= d do not exist
 #pragma unroll
@@ -494,10 +523,11 @@ __global__ __launch_bounds__(QF_THREADS) void pf_elbo_qf_kernel(ElboArgs A, int 
                     auto block_body_seq = [&](const int bl, auto special_tag) {
                         const int blk = blk0 + bl;
                         double z[NG][4];
+                        const uint64_t t = pf_philox_block_product((uint32_t)(blk * 4 + q), k0);   // shared by the groups
 #pragma unroll
                         for (int g = 0; g < NG; ++g) {
                             Pend pp;
-                            gen_issue(g, blk, pp);
+                            gen_issue(g, blk, t, pp);
                             finish(g, blk, pp, z[g], special_tag);
                         }
                         const double *rp = rs + bl * 48 + 4 * q;
@@ -545,8 +575,9 @@ __global__ __launch_bounds__(QF_THREADS) void pf_elbo_qf_kernel(ElboArgs A, int 
                         __builtin_amdgcn_sched_barrier(0);
                         Pend pp[NG];
                         double z[NG][4];
+                        const uint64_t t = pf_philox_block_product((uint32_t)(blk * 4 + q), k0);   // shared by the groups
 #pragma unroll
-                        for (int g = 0; g < NG; ++g) gen_issue(g, blk, pp[g]);
+                        for (int g = 0; g < NG; ++g) gen_issue(g, blk, t, pp[g]);
 #pragma unroll
                         for (int g = 0; g < NG; ++g) {           // the MFMA burst of group g hides the look-up latency of group g + 1
                             finish(g, blk, pp[g], z[g], special_tag);
@@ -675,17 +706,19 @@ __global__ __launch_bounds__(QF_THREADS) void pf_elbo_qf_kernel(ElboArgs A, int 
                 }
                 __syncthreads();
                 const bool lost = cn_s[3] != 0.0;
+                int tid_s = tid;                                   // opaque: the per-thread offsets of this copy are formed here, not in the prologue
+                asm volatile("" : "+v"(tid_s));
                 const double *src = cshare + (size_t)tail_f * NC;
                 double cv[(NC + QF_THREADS - 1) / QF_THREADS];
 #pragma unroll
                 for (int u = 0; u < (NC + QF_THREADS - 1) / QF_THREADS; ++u) {
-                    const int i = tid + u * QF_THREADS;
+                    const int i = tid_s + u * QF_THREADS;
                     cv[u] = __hip_atomic_load(src + (i < NC ? i : NC - 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
                 __syncthreads();                                   // everybody has read cn_s[3]
 #pragma unroll
                 for (int u = 0; u < (NC + QF_THREADS - 1) / QF_THREADS; ++u) {
-                    const int i = tid + u * QF_THREADS;
+                    const int i = tid_s + u * QF_THREADS;
                     if (i < NC) cn_s[i] = lost ? NAN : cv[u];
                 }
             }
@@ -706,6 +739,12 @@ __global__ __launch_bounds__(QF_THREADS) void pf_elbo_qf_kernel(ElboArgs A, int 
         int lane_e = lane;
         asm volatile("" : "+v"(lane_e));
         const int qe = lane_e >> 4, ce = lane_e & 15;
+        // (the same for the draw index: formed here from an opaque wave index, it is not carried -- and spilled -- across the block loop)
+        int wv_e = tid;
+        asm volatile("" : "+v"(wv_e));
+        wv_e >>= 6;
+        int d_e = d;                                                // (and for the two constants (double) d feeds: one v_cvt here, not 8 B of scratch each)
+        asm volatile("" : "+s"(d_e));
         // ---- finish the 16 draws of each group in registers: lane (q, c) holds entries 4T + q of w, A3, A4 of draw c
 #pragma unroll
         for (int g = 0; g < NG; ++g) {
@@ -771,12 +810,13 @@ __global__ __launch_bounds__(QF_THREADS) void pf_elbo_qf_kernel(ElboArgs A, int 
                     for (int T = 0; T < NT; ++T) pr = fma(vh0[4 * T + qe], tvd[T], pr);
                     pr = pf_sum_q(pr);
                     const double ta = cn_s[1] + cn_s[2] * (zh - pr), t3 = ta / 3.0;
-                    lp = (t3 * t3 + (double)(d - 1) * ta + q1 * exp(-ta)) / -2.0;
+                    lp = (t3 * t3 + (double)(d_e - 1) * ta + q1 * exp(-ta)) / -2.0;
                 }
             }
-            if (qe == 0 && nl[g] < A.N) {
-                out_lq[nl[g]] = ((double)d * PF_LOG2PI + logdet + us) / -2.0;        // src/mvnormal.jl:36
-                out_lp[nl[g]] = lp;
+            const int64_t nl = (int64_t)(g_begin + (lb * QF_WAVES + wv_e) * NG + g - npg) * 16 + ce;
+            if (qe == 0 && nl < A.N) {
+                out_lq[nl] = ((double)d_e * PF_LOG2PI + logdet + us) / -2.0;        // src/mvnormal.jl:36
+                out_lp[nl] = lp;
             }
         }
 #if QF_PROF
@@ -791,11 +831,11 @@ __global__ __launch_bounds__(QF_THREADS) void pf_elbo_qf_kernel(ElboArgs A, int 
 }
 
 // ---------------------------------------------------------------------------------------------------
-static size_t qf_lds_bytes(int ch_blocks, int nchunks, int kc, int rpad) {
+static size_t qf_lds_bytes(int ch_blocks, int nchunks, int kc, int rpad, int ng) {
     const size_t per = (size_t)ch_blocks * 16 * kc + (size_t)ch_blocks * 48;
     size_t stage = per * (nchunks > 1 ? 2 : 1);
     if (stage < QF_MIN_FRONT) stage = QF_MIN_FRONT;
-    return sizeof(double) * (stage + (size_t)kc * kc + qf_nconst(kc, rpad) + (size_t)rpad * rpad + 1 + 4 * PF_ICDF_LDS_ENTRIES + 2 * PF_ICDF_BFE_BEHIND);
+    return sizeof(double) * (stage + (size_t)kc * kc + qf_nconst(kc, rpad) + (size_t)rpad * rpad + qf_head_lds(kc, ng) + 1 + 4 * PF_ICDF_LDS_ENTRIES + 2 * PF_ICDF_BFE_BEHIND);
 }
 
 // the plan of one scan call, counted per ctx for pfmi_kernel_time (include/pfmi.h): instantiation, resident / streamed factor block, and the
@@ -812,8 +852,8 @@ static int32_t launch_qf_ng(pfmi_ctx *c, const ElboArgs &a, int64_t nfits) {
     const int nblk = (a.d + 15) / 16;
     int ch_blocks = nblk, nchunks = 1;
     constexpr int QF_CHB = qf_chb<KC>::v;
-    if (qf_lds_bytes(nblk, 1, KC, RPAD) > 156 * 1024) { ch_blocks = QF_CHB; nchunks = (nblk + QF_CHB - 1) / QF_CHB; }
-    const size_t lds_bytes = qf_lds_bytes(ch_blocks, nchunks, KC, RPAD);
+    if (qf_lds_bytes(nblk, 1, KC, RPAD, NG) > 156 * 1024) { ch_blocks = QF_CHB; nchunks = (nblk + QF_CHB - 1) / QF_CHB; }
+    const size_t lds_bytes = qf_lds_bytes(ch_blocks, nchunks, KC, RPAD, NG);
     PF_CHECK(lds_bytes <= 160 * 1024, PFMI_ERR_UNSUPPORTED, "qf kernel LDS %zu too large", lds_bytes);
     auto kern = pf_elbo_qf_kernel<KC, TGT, RPAD, NG>;
     PF_TRY(pf_raise_lds_limit(c, reinterpret_cast<const void *>(kern), 160 * 1024));

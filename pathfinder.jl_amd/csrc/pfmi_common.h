@@ -369,22 +369,71 @@ void pf_kernel_end(pfmi_ctx *c, const char *name);
 // Philox4x32-10 (Salmon et al. 2011); identical bit stream to oracle/pf_oracle.c:pfo_philox4x32_10
 // a ^ b ^ k with the (wave-uniform) round key as the one scalar operand VOP3 allows: LLVM splits this into two v_xor_b32 when k
 // lives in an SGPR, which costs 20 extra instructions per Philox call
-__device__ __forceinline__ uint32_t pf_xor3_key(uint32_t a, uint32_t b, uint32_t k) {
+__host__ __device__ __forceinline__ uint32_t pf_xor3_key(uint32_t a, uint32_t b, uint32_t k) {
+#if defined(__HIP_DEVICE_COMPILE__)
     if (__builtin_constant_p(k)) return a ^ b ^ k;
     uint32_t r;
     asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x96" : "=v"(r) : "v"(a), "v"(b), "s"(k));   // gfx950: three-input bit op, truth table 0x96 = a ^ b ^ c
     return r;
+#else
+    return a ^ b ^ k;
+#endif
 }
 // Rounds of the NORMAL-generation stream.  Philox4x32 is crush-resistant from 7 rounds (Salmon et al. 2011, table 2: 7 is the
 // minimum that passes BigCrush, 10 the default with a safety margin); the 1.1e10 normals of a step are the kernel's second
 // largest issue stream and each round costs 24 SIMD cycles (two 64-bit multiplies), so the normals use 7.  Seeds, resampling
 // uniforms and everything a host sees keep the 10-round function with its published known answers.
+// In the ELBO scan the counter is (draw, 4 blk + q, 0, 0): its first three rounds are largely per-draw constants, and the block loop
+// starts from them (pf_philox_draw_invariants / pf_philox4x32_hoisted below) -- 9 products per call + 1 per block instead of 14.
 #define PF_NORMAL_ROUNDS 7
 template <int ROUNDS>
-__device__ __forceinline__ void pf_philox4x32(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
+__host__ __device__ __forceinline__ void pf_philox4x32(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
                                               uint32_t k0, uint32_t k1, uint32_t (&out)[4]) {
 #pragma unroll
     for (int r = 0; r < ROUNDS; ++r) {
+        uint64_t p0 = (uint64_t)0xD2511F53u * c0;
+        uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
+        uint32_t n0 = pf_xor3_key((uint32_t)(p1 >> 32), c1, k0);
+        uint32_t n1 = (uint32_t)p1;
+        uint32_t n2 = pf_xor3_key((uint32_t)(p0 >> 32), c3, k1);
+        uint32_t n3 = (uint32_t)p0;
+        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+// Philox4x32 with counter (n, g, 0, 0) split by what each product depends on (M0 = 0xD2511F53, M1 = 0xCD9E8D57, W = the key
+// increments; hi / lo = the halves of a 64-bit product).  Words 2 and 3 are zero, so round 1 has ONE product, p = M0 n, and after it
+// word 0 = g ^ k0 is the only word that knows g.  Round 2 multiplies it (t = M0 (g ^ k0): no n in it, the same for every draw of a
+// fit) and r = M1 (hi(p) ^ k1) (no g in it); round 3 multiplies A = hi(r) ^ (k0 + W0) (no g: s = M0 A) and the first word that
+// depends on both, hi(t) ^ lo(p) ^ (k1 + W1).  Per (n, key) that leaves four words, the xors with the round keys folded in:
+//   C = lo(p) ^ (k1 + W1)   D = lo(r) ^ (k0 + 2 W0)   E = hi(s) ^ (k1 + 2 W1)   F = lo(s)
+// and a call is finished from them and t with u = M1 (hi(t) ^ C): the words after round 3 are (hi(u) ^ D, lo(u), lo(t) ^ E, F).
+// Integer arithmetic only: the same words as pf_philox4x32<ROUNDS>(n, g, 0, 0, k0, k1), bit for bit.
+struct pf_philox_inv { uint32_t C, D, E, F; };
+__host__ __device__ __forceinline__ pf_philox_inv pf_philox_draw_invariants(uint32_t n, uint32_t k0, uint32_t k1) {
+    const uint64_t p = (uint64_t)0xD2511F53u * n;
+    const uint64_t r = (uint64_t)0xCD9E8D57u * ((uint32_t)(p >> 32) ^ k1);
+    const uint32_t A = (uint32_t)(r >> 32) ^ (k0 + 0x9E3779B9u);
+    const uint64_t s = (uint64_t)0xD2511F53u * A;
+    pf_philox_inv v;
+    v.C = (uint32_t)p ^ (k1 + 0xBB67AE85u);
+    v.D = (uint32_t)r ^ (k0 + 2u * 0x9E3779B9u);
+    v.E = (uint32_t)(s >> 32) ^ (k1 + 2u * 0xBB67AE85u);
+    v.F = (uint32_t)s;
+    return v;
+}
+// the product of a call that does not depend on the draw
+__host__ __device__ __forceinline__ uint64_t pf_philox_block_product(uint32_t g, uint32_t k0) { return (uint64_t)0xD2511F53u * (g ^ k0); }
+template <int ROUNDS>
+__host__ __device__ __forceinline__ void pf_philox4x32_hoisted(const pf_philox_inv &v, uint64_t t, uint32_t k0, uint32_t k1, uint32_t (&out)[4]) {
+    static_assert(ROUNDS >= 3, "the hoisted form starts from the words after round 3");
+    const uint32_t t_lo = (uint32_t)t;
+    const uint64_t u = (uint64_t)0xCD9E8D57u * ((uint32_t)(t >> 32) ^ v.C);
+    uint32_t c0 = (uint32_t)(u >> 32) ^ v.D, c1 = (uint32_t)u, c2 = t_lo ^ v.E, c3 = v.F;
+    k0 += 3u * 0x9E3779B9u; k1 += 3u * 0xBB67AE85u;
+#pragma unroll
+    for (int r = 3; r < ROUNDS; ++r) {
         uint64_t p0 = (uint64_t)0xD2511F53u * c0;
         uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
         uint32_t n0 = pf_xor3_key((uint32_t)(p1 >> 32), c1, k0);
