@@ -407,6 +407,23 @@ int32_t pfmi_pool_draws_dev(pfmi_ctx *ctx, void **dev_ptr, int64_t *count);
 /* device pointer to the local log-ratio shard (K_local * N_r doubles) for the RCCL all-gather */
 int32_t pfmi_pool_log_ratios_dev(pfmi_ctx *ctx, void **dev_ptr, int64_t *count);
 
+/* Mixture-proposal log ratios of the pool on the device.  The pool is a stratified sample of the uniform mixture qbar = (1/K) sum_k q_k of
+ * the K fits it was drawn from (the points of pfmi_pool_build / _build_best, in run order); for every pool column g = k*N_r + n:
+ *   log_mix[g]    = log sum_k exp(logpdf(fit k, x_g)) - log K     components in run order; NaN if any component is NaN (a failed fit),
+ *                                                                 -inf if all are -inf (the rules of pfmi_mixture_logpdf)
+ *   log_ratios[g] = logp[g] - log_mix[g]                          logp: the target values pfmi_pool_build stored with the pool
+ * -- the deterministic-mixture (balance-heuristic) weights of multiple importance sampling, in place of logp - logq of the run that drew
+ * the column (pfmi_pool_get, which this call leaves untouched).  Host outputs of K*N_r doubles each, either may be NULL; blocks.
+ * At d <= 1024 log_mix has the bits of pfmi_mixture_logpdf_dev on pfmi_pool_draws_dev minus log K (the double log(K) of the host's libm);
+ * at d > 1024 with history_length <= 16 the components come from a row-tiled matrix-core kernel and agree with it to rounding.
+ * Ordering guarantee: a column's value depends on the column, the K fits and d only -- not on its position in the pool, on N_r, or on how
+ * the call cuts the pool into chunks.
+ * No pool: PFMI_ERR_STATE; a column padding the kernels do not cover: PFMI_ERR_UNSUPPORTED. */
+int32_t pfmi_pool_mixture_ratios(pfmi_ctx *ctx, double *log_mix, double *log_ratios);
+/* device pointer to the log ratios of the last pfmi_pool_mixture_ratios (K_local * N_r doubles), for pfmi_psis_dev.  The stream is idle on
+ * return.  Valid until the next pfmi_pool_build* on this ctx; no pfmi_pool_mixture_ratios on the current pool: PFMI_ERR_STATE. */
+int32_t pfmi_pool_mixture_ratios_dev(pfmi_ctx *ctx, void **dev_ptr, int64_t *count);
+
 /* PSIS.psis(log_ratios) (src/resample.jl:78): log_ratios_dev is a DEVICE buffer of S doubles (the
  * all-gathered pool), weights are kept device-resident; host outputs may be NULL. */
 int32_t pfmi_psis_dev(pfmi_ctx *ctx, const void *log_ratios_dev, int64_t S, double *weights,

@@ -14,6 +14,7 @@ static int32_t pool_alloc(pfmi_ctx *c, int64_t N_r) {
     PF_TRY(c->pool_lq.ensure(sizeof(double) * S));
     PF_TRY(c->pool_points.ensure(sizeof(int32_t) * K));
     PF_TRY(c->pool_seeds.ensure(sizeof(uint64_t) * K));
+    c->pool_mix_done = false;              // the mixture-proposal ratios belong to the pool they were formed on
     return PFMI_OK;
 }
 
@@ -196,6 +197,27 @@ int32_t pfmi_pool_log_ratios_dev(pfmi_ctx *c, void **dev_ptr, int64_t *count) {
     PF_CHECK(c->pooled, PFMI_ERR_STATE, "pool_log_ratios_dev: call pfmi_pool_build first");
     PF_HIP(hipStreamSynchronize(c->stream));
     if (dev_ptr) *dev_ptr = c->pool_lr.p;
+    if (count) *count = (int64_t)c->K * c->N_r;
+    return PFMI_OK;
+}
+
+int32_t pfmi_pool_mixture_ratios(pfmi_ctx *c, double *log_mix, double *log_ratios) {
+    PF_CTX_MUT(c);
+    PF_CHECK(c->pooled, PFMI_ERR_STATE, "pool_mixture_ratios: call pfmi_pool_build first");
+    c->pool_mix_done = false;
+    PF_TRY(pf_launch_pool_mixture_ratios(c));
+    c->pool_mix_done = true;
+    const size_t S = (size_t)c->K * c->N_r;
+    if (log_mix) PF_TRY(pf_download(c, log_mix, c->pool_lmix.p, sizeof(double) * S));
+    if (log_ratios) PF_TRY(pf_download(c, log_ratios, c->pool_lr_mix.p, sizeof(double) * S));
+    return pf_stream_sync(c);
+}
+
+int32_t pfmi_pool_mixture_ratios_dev(pfmi_ctx *c, void **dev_ptr, int64_t *count) {
+    PF_CTX(c);
+    PF_CHECK(c->pooled && c->pool_mix_done, PFMI_ERR_STATE, "pool_mixture_ratios_dev: call pfmi_pool_mixture_ratios on the current pool first");
+    PF_HIP(hipStreamSynchronize(c->stream));
+    if (dev_ptr) *dev_ptr = c->pool_lr_mix.p;
     if (count) *count = (int64_t)c->K * c->N_r;
     return PFMI_OK;
 }

@@ -266,13 +266,11 @@ __global__ void pf_mixture_lse_kernel(int64_t N, int K, const double *__restrict
     lse[n] = out;
 }
 
-// comp [K][N] and lse [N] from X (d, N) for the K fit points d_points (device, int32, validated by the caller)
-int32_t pf_launch_mixture_logpdf(pfmi_ctx *c, int K, const int32_t *d_points, int64_t N, const double *d_x, double *d_lse,
-                                 double *d_comp) {
+// comp [K][N] from X (d, N) for the K fit points d_points (device, int32, validated by the caller): the launch alone, no timing pair
+int32_t pf_launch_mixture_comp(pfmi_ctx *c, int K, const int32_t *d_points, int64_t N, const double *d_x, double *d_comp) {
     const int d = c->d, kp = c->kpad;
     const char *force = pf_debug_get("PFMI_MIXTURE_KERNEL");
     const bool lane = (force && strcmp(force, "lane") == 0) || d > MX_DMAX || kp > 32;
-    pf_kernel_begin(c);
     if (lane) {
         PF_CHECK((N + MX_LANE_THREADS - 1) / MX_LANE_THREADS <= INT32_MAX, PFMI_ERR_ARG, "mixture_logpdf: N too large");
         dim3 grid((unsigned)((N + MX_LANE_THREADS - 1) / MX_LANE_THREADS), (unsigned)K);
@@ -315,6 +313,14 @@ int32_t pf_launch_mixture_logpdf(pfmi_ctx *c, int K, const int32_t *d_points, in
         PF_TRY(rc);
     }
     PF_HIP(hipGetLastError());
+    return PFMI_OK;
+}
+
+// comp [K][N] and lse [N] from X (d, N) for the K fit points d_points (device, int32, validated by the caller)
+int32_t pf_launch_mixture_logpdf(pfmi_ctx *c, int K, const int32_t *d_points, int64_t N, const double *d_x, double *d_lse,
+                                 double *d_comp) {
+    pf_kernel_begin(c);
+    PF_TRY(pf_launch_mixture_comp(c, K, d_points, N, d_x, d_comp));
     pf_kernel_end(c, "mixture_logpdf");
     pf_kernel_begin(c);
     hipLaunchKernelGGL(pf_mixture_lse_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, N, K, d_comp, d_lse);

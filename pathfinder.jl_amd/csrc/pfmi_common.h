@@ -279,6 +279,9 @@ struct pfmi_ctx {
     DevBuf apply_part;             // its per-run sums [K][r d] (pool_apply_kernels.hip)
     DevBuf apply_y;                // its result Y [r d] (a carry-in is uploaded here and accumulated in place)
     DevBuf apply_v;                // its directions [r d]
+    bool pool_mix_done = false;    // pfmi_pool_mixture_ratios has run on the current pool (cleared by pfmi_pool_build*)
+    DevBuf pool_lmix, pool_lr_mix; // its results [K*N_r]: log of the uniform mixture of the pool's own fits, pool_lp minus it
+    DevBuf pool_mix_comp;          // its scratch comp [K][chunk] (at most 64 MB: the pool is walked in chunks of columns)
 };
 
 // small host -> device upload on the ctx stream WITHOUT synchronising it (pinned arena); large blocks take the synchronous path
@@ -307,6 +310,10 @@ int32_t pf_launch_elbo_reduce(pfmi_ctx *c);
 int32_t pf_launch_logpdf(pfmi_ctx *c, int64_t point, int64_t N, const double *d_x, double *d_out);
 int32_t pf_launch_mixture_logpdf(pfmi_ctx *c, int K, const int32_t *d_points, int64_t N, const double *d_x, double *d_lse,
                                  double *d_comp);
+// its component kernels alone (comp [K][N]; the route and the bits of pf_launch_mixture_logpdf), for callers that time and reduce themselves
+int32_t pf_launch_mixture_comp(pfmi_ctx *c, int K, const int32_t *d_points, int64_t N, const double *d_x, double *d_comp);
+// mixture-proposal log ratios of the ctx's pool into c->pool_lmix (log qbar) and c->pool_lr_mix (pool_lp - log qbar), pool_mixture_kernels.hip
+int32_t pf_launch_pool_mixture_ratios(pfmi_ctx *c);
 int32_t pf_launch_psis(pfmi_ctx *c, const double *d_lr, int64_t S);
 // weighted moments of the ctx's pool into c->mom (weights c->w + col_offset when importance != 0; d_center: device, d doubles or NULL)
 int32_t pf_launch_pool_moments(pfmi_ctx *c, int64_t col_offset, int importance, const double *d_center);

@@ -1081,6 +1081,30 @@ function pool_apply(b::Batch, V::Matrix{Float64}; col_offset::Integer=0, importa
 end
 
 """
+    pool_mixture_ratios(b::Batch, ncolumns) -> (log_mix, log_ratios), ncolumns = K N_r of this engine's pool
+
+Mixture-proposal log ratios of the engine's pool, formed on the device: `log_mix` is the log density of the uniform mixture of the pool's
+own K fits at every pool column (run-major, the order of the pool), `log_ratios = logp .- log_mix` -- the balance-heuristic weights of
+multiple importance sampling in place of the per-run `logp - logq`, which stay as they are.  `pool_mixture_ratios_dev` gives the device
+pointer of the ratios for `pfmi_psis_dev`.
+"""
+function pool_mixture_ratios(b::Batch, ncolumns::Integer)
+    _live(b.eng, b.gen)
+    lm = Vector{Float64}(undef, ncolumns)
+    lr = Vector{Float64}(undef, ncolumns)
+    check(ccall((:pfmi_pool_mixture_ratios, libpfmi), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), b.eng.ptr, lm, lr))
+    return lm, lr
+end
+
+function pool_mixture_ratios_dev(b::Batch)
+    _live(b.eng, b.gen)
+    dev = Ref{Ptr{Cvoid}}(C_NULL)
+    cnt = Ref{Int64}(0)
+    check(ccall((:pfmi_pool_mixture_ratios_dev, libpfmi), Int32, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}, Ref{Int64}), b.eng.ptr, dev, cnt))
+    return dev[], cnt[]
+end
+
+"""
     importance_covariance(result::Pathfinder.MultiPathfinderResult; importance=true)
 
 Posterior `mean`, `cov`, `corr`, `ess`, `ncandidates` and `pareto_shape` from ALL pooled candidates under their PSIS weights (uniform

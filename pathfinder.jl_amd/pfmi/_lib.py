@@ -49,6 +49,7 @@ SYMBOLS = [
     "pfmi_stream_enqueue", "pfmi_stream_seeds", "pfmi_stream_pump", "pfmi_stream_wait", "pfmi_stream_cancel",
     "pfmi_fit_batch_ex", "pfmi_set_hinit", "pfmi_set_callback_threads",
     "pfmi_set_target_gradient", "pfmi_optimize_batch_pump", "pfmi_optimize_batch_cancel", "pfmi_optimize_stats",
+    "pfmi_pool_mixture_ratios", "pfmi_pool_mixture_ratios_dev",
 ]
 
 # declared argument types (entry points not listed here take what the caller wraps by hand)
@@ -58,6 +59,7 @@ ARGTYPES = {
     "pfmi_pool_cdf": [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int32)],
     "pfmi_pool_cross": [C.c_void_p, C.c_int64, C.c_int32, _dp, _dp, _dp],
     "pfmi_pool_apply": [C.c_void_p, C.c_int64, C.c_int32, _dp, C.c_int32, _dp, _dp, _dp, _dp],
+    "pfmi_pool_mixture_ratios": [C.c_void_p, _dp, _dp],
 }
 
 

@@ -362,6 +362,7 @@ class MultiPathfinderResult:        # src/multipath.jl:31-44
     engine: Any = field(repr=False, default=None)
     ndraws_per_run: int = 0
     engines: Any = field(repr=False, default=None)      # the engines the runs are sharded over (contiguous blocks)
+    proposal: str = "component"                         # what the PSIS weights divide logp by: the run's own fit, or the "mixture" of all
 
     @property
     def fit_distribution_transformed(self): return self.fit_distribution
@@ -855,14 +856,55 @@ def pathfinder(target, *, rng=None, init=None, dim=-1, init_scale=2, init_sample
                             a["dists"], a["ests"], st["nrej"], st["success"], a["draw_seed"], ndraws)
 
 
+PROPOSALS = ("component", "mixture")
+
+
+def _check_proposal(proposal, importance, engs):
+    """The `proposal` keyword of multipathfinder / resample.  "component": every candidate is weighted by p / q_k of the run that drew
+    it (the reference, src/resample.jl:81-95).  "mixture": by p / qbar with qbar the uniform mixture of all runs' fits, which needs
+    every run's factor on the GPU that holds the candidate -- one engine, no communicator across processes."""
+    if proposal not in PROPOSALS:
+        raise ValueError(f"proposal must be one of {PROPOSALS}, got {proposal!r}")
+    if proposal == "mixture":
+        if not importance:
+            raise ValueError('proposal="mixture" chooses the importance weights: it needs importance=True')
+        if len(engs) > 1:
+            raise ValueError('proposal="mixture" is limited to one engine: the mixture needs every run\'s fit on the GPU that holds '
+                             "the candidate")
+        from .core import _LIVE_COMMS
+        for comm in list(_LIVE_COMMS):
+            if comm.h is not None and engs[0] in comm.engines and comm.info()["world"] > 1:
+                raise ValueError('proposal="mixture" is limited to one engine: this engine belongs to a communicator of several ranks')
+    return proposal
+
+
+def _mixture_pool_psis(eng, npr, points, seeds, want_weights=True):
+    """pool of the runs' fits `points` drawn with `seeds`, its mixture-proposal log ratios and their PSIS, all on the device of `eng`
+    (the weights stay there for the index selection and the pool passes); returns the PSIS result"""
+    eng.pool_build(npr, points, seeds)
+    eng.pool_mixture_ratios(want=False)
+    ptr, S = eng.pool_mixture_ratios_dev()
+    return eng.psis_dev(ptr, S, want_weights=want_weights)
+
+
+def _mixture_pooled_stage(eng, npr, points, seeds, ndraws, seed, replace=True):
+    """the pooled stage under the mixture proposal: (PSIS result, indices, draws)"""
+    res = _mixture_pool_psis(eng, npr, points, seeds)
+    idx = eng.resample_indices(len(points) * npr, ndraws, importance=True, replace=replace, seed=seed)
+    return res, idx, eng.pool_gather(idx)
+
+
 def multipathfinder(target, ndraws, *, init=None, nruns=-1, ndraws_elbo=DEFAULT_NDRAWS_ELBO, ndraws_per_run=None,
                     rng=None, history_length=DEFAULT_HISTORY_LENGTH, importance=True, dim=-1, init_scale=2,
                     init_sampler=None, ntries=1000, ntasks=1, ntasks_per_run=1, input=None, engine=None, engines=None,
-                    materialise=False, optimizer="auto", strict=True, **optimizer_kwargs):
+                    materialise=False, optimizer="auto", strict=True, proposal="component", **optimizer_kwargs):
     """Multi-path Pathfinder (reference src/multipath.jl:118-245).  optimizer, strict: see pathfinder().
+    proposal="mixture": the pooled candidates are weighted by p / qbar, qbar the uniform mixture of the runs' fits (fit_distribution),
+    instead of p / q_k of the run that drew them -- the deterministic-mixture weights of multiple importance sampling; one engine only.
     engines=[Engine(0), Engine(1), ...]: the runs are sharded in contiguous blocks over several GPUs driven by this one host thread
     (the reference fans them out over tasks, src/multipath.jl:190-208); the pooled stage (:215-225) goes through the RCCL group of
     the engines.  The result does not depend on the number of engines (test/multipath.jl:107-140 extended to GPUs)."""
+    _check_proposal(proposal, importance, list(engines) if engines else [engine])
     if init is None:
         if nruns <= 0:
             raise ValueError("A positive `nruns` must be set or `init` must be provided.")     # :148-150
@@ -920,13 +962,17 @@ def multipathfinder(target, ndraws, *, init=None, nruns=-1, ndraws_elbo=DEFAULT_
             results[-1].draws
     S = nruns * ndraws_per_run
     psis_result = None
+    if proposal == "mixture":       # the runs are final: the pooled stage again, every candidate weighted against the mixture of the winners
+        res, idx, draws = _mixture_pooled_stage(engs[0], ndraws_per_run, [r.fit_distribution.point for r in results],
+                                                [r.draw_seed for r in results], ndraws, resample_seed)
+        pooled = dict(psis=res, idx=idx, draws=draws, weights=(res["weights"], res["log_weights"]))
     if importance:                                                                               # :220-224
         w, lw = pooled["weights"] if pooled.get("weights") is not None else engs[0].psis_weights(S)
         psis_result = PSISResult(w, lw, pooled["psis"]["pareto_shape"], pooled["psis"]["tail_length"])
     ids = pooled["idx"] // ndraws_per_run + 1                                                   # cld.(inds, N) with 1-based inds
     return MultiPathfinderResult(input if input is not None else target, rng, target.logp,
                                  MixtureModel([r.fit_distribution for r in results]), pooled["draws"], ids, results, psis_result, engs[0],
-                                 ndraws_per_run, engs)
+                                 ndraws_per_run, engs, proposal)
 
 
 @dataclass
@@ -964,6 +1010,10 @@ def _rebuild_pool(result, importance):
         r.fit_distribution._live()                                  # the fits must still be the engine's current ones
     npr = runs[0].ndraws_per_run
     seeds = [r.draw_seed for r in runs]
+    if getattr(result, "proposal", "component") == "mixture" and bool(importance) and result.psis_result is not None:
+        _check_proposal("mixture", True, engs)                      # the weights of the mixture route, as multipathfinder formed them
+        res = _mixture_pool_psis(engs[0], npr, [r.fit_distribution.point for r in runs], seeds, want_weights=False)
+        return [(engs[0], 0)], True, res["pareto_shape"]
     owners = []
     for eng, (k0, k1) in zip(engs, _blocks(len(runs), len(engs))):
         eng.pool_build(npr, [r.fit_distribution.point for r in runs[k0:k1]], seeds[k0:k1])
@@ -1321,10 +1371,14 @@ def _resample(rng, comm, psis, ndraws_per_component, ndraws, replace=True):
     return res, draws, ids
 
 
-def resample(result, ndraws, *, rng=None, replace=True, importance=True, ndraws_per_run=None, ntasks=1):
-    """resample(result::MultiPathfinderResult, ndraws; ...)  (reference src/resample.jl:20-46)"""
+def resample(result, ndraws, *, rng=None, replace=True, importance=True, ndraws_per_run=None, ntasks=1, proposal=None):
+    """resample(result::MultiPathfinderResult, ndraws; ...)  (reference src/resample.jl:20-46).  proposal: "component" or "mixture" as in
+    multipathfinder; None takes the result's."""
     rng = rng if rng is not None else result.rng
     engs = result.engines or [result.engine]
+    if proposal is None:
+        proposal = getattr(result, "proposal", "component")
+    _check_proposal(proposal, importance, engs)
     runs = result.pathfinder_results
     K = len(runs)
     blocks = _blocks(K, len(engs))
@@ -1336,15 +1390,22 @@ def resample(result, ndraws, *, rng=None, replace=True, importance=True, ndraws_
     else:                                                           # reuse stored draws (:97-101): the candidates are
         npr = runs[0].ndraws_per_run                                # pathfinder_results[k].draws, whatever an earlier
         seeds = [r.draw_seed for r in runs]                         # resample() drew fresh
-    for eng, (k0, k1) in zip(engs, blocks):
-        eng.set_callback_threads(ntasks)                            # src/resample.jl:85-92: logp over `ntasks` tasks
-        eng.pool_build(npr, [r.fit_distribution.point for r in runs[k0:k1]], seeds[k0:k1])
     S = K * npr
-    # PSIS of the (re)built pool: for stored draws this reproduces result.psis_result bit for bit
-    res, draws, ids = _resample(rng, _comm_for(engs), importance, npr, ndraws, replace=replace)
+    if proposal == "mixture":
+        engs[0].set_callback_threads(ntasks)
+        res, idx, draws = _mixture_pooled_stage(engs[0], npr, [r.fit_distribution.point for r in runs], seeds, ndraws,
+                                                int(rng.rand_u64(1)[0]), replace=replace)
+        ids = idx // npr + 1
+    else:
+        for eng, (k0, k1) in zip(engs, blocks):
+            eng.set_callback_threads(ntasks)                        # src/resample.jl:85-92: logp over `ntasks` tasks
+            eng.pool_build(npr, [r.fit_distribution.point for r in runs[k0:k1]], seeds[k0:k1])
+        # PSIS of the (re)built pool: for stored draws this reproduces result.psis_result bit for bit
+        res, draws, ids = _resample(rng, _comm_for(engs), importance, npr, ndraws, replace=replace)
     psis_result = None
     if importance:
-        if ndraws_per_run is None and result.psis_result is not None and len(result.psis_result.weights) == S:
+        if (ndraws_per_run is None and result.psis_result is not None and len(result.psis_result.weights) == S
+                and proposal == getattr(result, "proposal", "component")):
             # stored draws + stored PSIS: the reference hands the SAME object on (:31-41).  (A result of a fresh-candidate resample
             # stores weights of ITS candidates, not of pathfinder_results[k].draws: the reference would pair them with the wrong pool
             # and fail on the length; here the stored pool's PSIS is recomputed instead.)
@@ -1353,4 +1414,4 @@ def resample(result, ndraws, *, rng=None, replace=True, importance=True, ndraws_
             w, lw = engs[0].psis_weights(S)
             psis_result = PSISResult(w, lw, res["pareto_shape"], res["tail_length"])
     return MultiPathfinderResult(result.input, result.rng, result.logp, result.fit_distribution, draws, ids,
-                                 runs, psis_result, engs[0], npr, engs)
+                                 runs, psis_result, engs[0], npr, engs, proposal)

@@ -590,6 +590,23 @@ class Engine:
         check(self.L.pfmi_pool_log_ratios_dev(self.ctx, C.byref(p), C.byref(n)))
         return p.value, n.value
 
+    def pool_mixture_ratios(self, want=True):
+        """Mixture-proposal log ratios of this engine's pool, formed on the device (include/pfmi.h pfmi_pool_mixture_ratios): returns
+        (log_mix, log_ratios), K N_r doubles each, log_mix = the log density of the uniform mixture of the pool's own K fits at every
+        pool column and log_ratios = logp - log_mix.  pool_get()'s per-run ratios are left as they are.  want=False: nothing is
+        downloaded (returns None); pool_mixture_ratios_dev() then gives the device pointer for psis_dev."""
+        S = self.K * getattr(self, "N_r", 0)                # (no pool yet: the library says so)
+        lm = np.empty(S) if want and S else None
+        lr = np.empty(S) if want and S else None
+        check(self.L.pfmi_pool_mixture_ratios(self.ctx, _d(lm), _d(lr)))
+        return (lm, lr) if want else None
+
+    def pool_mixture_ratios_dev(self):
+        """(device pointer, count) of the log ratios of the last pool_mixture_ratios on the current pool"""
+        p, n = C.c_void_p(), C.c_int64()
+        check(self.L.pfmi_pool_mixture_ratios_dev(self.ctx, C.byref(p), C.byref(n)))
+        return p.value, n.value
+
     def psis(self, log_ratios, want_weights=True):
         lr = np.ascontiguousarray(log_ratios, dtype=np.float64)
         S = len(lr)
