@@ -103,7 +103,7 @@ int32_t pfmi_debug_set(const char *key, const char *value);
 /* device-time instrumentation (hipEvents on the ctx stream).  pfmi_timer_* bracket any sequence of
  * calls; pfmi_kernel_time returns accumulated time and launch count of one named kernel family
  * ("history", "fit", "elbo_draws" = ELBO scan, "elbo_draws_x" = draw launches that also write x, "elbo_reduce",
- * "psis", "resample") since pfmi_profile(ctx, mode).  mode 1: the host waits after every stage (each stage starts on an idle
+ * "psis", "psis_runs", "resample") since pfmi_profile(ctx, mode).  mode 1: the host waits after every stage (each stage starts on an idle
  * GPU: its figure includes the host's launch latency); mode 2: the event pairs stay in the stream and are read by
  * pfmi_kernel_time (which waits for them) -- the pipeline runs as it does unprofiled and a stage's figure is its kernels'
  * time; mode 0: off.
@@ -423,6 +423,28 @@ int32_t pfmi_pool_mixture_ratios(pfmi_ctx *ctx, double *log_mix, double *log_rat
 /* device pointer to the log ratios of the last pfmi_pool_mixture_ratios (K_local * N_r doubles), for pfmi_psis_dev.  The stream is idle on
  * return.  Valid until the next pfmi_pool_build* on this ctx; no pfmi_pool_mixture_ratios on the current pool: PFMI_ERR_STATE. */
 int32_t pfmi_pool_mixture_ratios_dev(pfmi_ctx *ctx, void **dev_ptr, int64_t *count);
+
+/* Per-run Pareto diagnostics of the pool: PSIS.psis of every run's own N_r log ratios, all K runs in one launch (one workgroup per
+ * run).  source selects the ratios: */
+#define PFMI_RATIOS_COMPONENT 0   /* logp - logq of the run that drew the column (pfmi_pool_get) */
+#define PFMI_RATIOS_MIXTURE   1   /* logp - log qbar (the last pfmi_pool_mixture_ratios on this pool) */
+/* For run k, over lr[k*N_r .. (k+1)*N_r):
+ *   pareto_k[k]   k-hat of the run; NaN where PSIS does not smooth (a tail of fewer than 5, a non-finite value in the tail, ...)
+ *   tail_len[k]   M = min(cld(N_r, 5), ceil(3 sqrt(N_r)))
+ *   lse[k]        logsumexp of the run's smoothed log ratios: lse[k] - log(N_r) estimates the log evidence from this run alone
+ *   sumsq[k]      sum_n w_n^2 of the run's normalised weights (1 / sumsq is the run's effective sample size); NaN if any w_n is NaN
+ *   log_weights, weights   K*N_r each, every run normalised on its own (each run's weights sum to 1)
+ * Host outputs of K, K, K, K, K*N_r, K*N_r entries; any may be NULL (all NULL: the pass still runs); blocks.
+ * Guarantees: pareto_k, tail_len, log_weights and weights of a run have the bits of pfmi_psis on the run's slice taken through the
+ * one-workgroup route (both call one device function), and lse is the constant that route subtracted; sumsq is added in an order that
+ * depends on N_r only.  A run's outputs depend on its N_r ratios alone -- not on K, on the run's position in the pool, or on the device --
+ * so the diagnostics of a pool sharded over several contexts are the per-context results concatenated, and no communicator is involved.
+ * The context's current PSIS result (pfmi_psis / pfmi_psis_dev / pfmi_comm_pool_psis: what pfmi_psis_weights, pfmi_resample_indices and
+ * the importance-weighted pool passes read) is neither read nor written: the call has buffers of its own.
+ * No pool: PFMI_ERR_STATE; PFMI_RATIOS_MIXTURE without pfmi_pool_mixture_ratios on the current pool: PFMI_ERR_STATE; any other source:
+ * PFMI_ERR_ARG; N_r whose tail M + 1 exceeds 4096 (N_r > 1 863 225): PFMI_ERR_UNSUPPORTED.  Stage name under pfmi_profile: "psis_runs". */
+int32_t pfmi_pool_psis_runs(pfmi_ctx *ctx, int32_t source, double *pareto_k, int64_t *tail_len, double *lse, double *sumsq,
+                            double *log_weights, double *weights);   /* K, K, K, K, K*N_r, K*N_r; any may be NULL; blocks */
 
 /* PSIS.psis(log_ratios) (src/resample.jl:78): log_ratios_dev is a DEVICE buffer of S doubles (the
  * all-gathered pool), weights are kept device-resident; host outputs may be NULL. */

@@ -222,6 +222,31 @@ int32_t pfmi_pool_mixture_ratios_dev(pfmi_ctx *c, void **dev_ptr, int64_t *count
     return PFMI_OK;
 }
 
+int32_t pfmi_pool_psis_runs(pfmi_ctx *c, int32_t source, double *pareto_k, int64_t *tail_len, double *lse, double *sumsq, double *log_weights,
+                            double *weights) {
+    PF_CTX_MUT(c);
+    PF_CHECK(c->pooled, PFMI_ERR_STATE, "pool_psis_runs: call pfmi_pool_build first");
+    PF_CHECK(source == PFMI_RATIOS_COMPONENT || source == PFMI_RATIOS_MIXTURE, PFMI_ERR_ARG, "pool_psis_runs: unknown source %d", (int)source);
+    PF_CHECK(source != PFMI_RATIOS_MIXTURE || c->pool_mix_done, PFMI_ERR_STATE,
+             "pool_psis_runs: call pfmi_pool_mixture_ratios on the current pool first");
+    const int K = c->K;
+    const size_t S = (size_t)K * (size_t)c->N_r;
+    PF_TRY(pf_launch_psis_runs(c, source == PFMI_RATIOS_MIXTURE ? c->pool_lr_mix.as<double>() : c->pool_lr.as<double>(), K, c->N_r));
+    std::vector<double> out((size_t)K * PF_PSIS_RUN_OUT);
+    PF_TRY(pf_download(c, out.data(), c->runs_out.p, sizeof(double) * out.size()));
+    if (log_weights) PF_TRY(pf_download(c, log_weights, c->runs_lw.p, sizeof(double) * S));
+    if (weights) PF_TRY(pf_download(c, weights, c->runs_w.p, sizeof(double) * S));
+    PF_TRY(pf_stream_sync(c));
+    for (int k = 0; k < K; ++k) {
+        const double *o = out.data() + (size_t)k * PF_PSIS_RUN_OUT;
+        if (pareto_k) pareto_k[k] = o[0];
+        if (tail_len) tail_len[k] = (int64_t)o[1];
+        if (lse) lse[k] = o[3];
+        if (sumsq) sumsq[k] = o[4];
+    }
+    return PFMI_OK;
+}
+
 int32_t pfmi_psis_dev(pfmi_ctx *c, const void *lr_dev, int64_t S, double *weights, double *log_weights,
                       double *pareto_k, int64_t *tail_len) {
     PF_CTX_MUT(c);

@@ -282,6 +282,8 @@ struct pfmi_ctx {
     bool pool_mix_done = false;    // pfmi_pool_mixture_ratios has run on the current pool (cleared by pfmi_pool_build*)
     DevBuf pool_lmix, pool_lr_mix; // its results [K*N_r]: log of the uniform mixture of the pool's own fits, pool_lp minus it
     DevBuf pool_mix_comp;          // its scratch comp [K][chunk] (at most 64 MB: the pool is walked in chunks of columns)
+    DevBuf runs_lw, runs_w;        // pfmi_pool_psis_runs: log weights and weights [K*N_r], every run normalised on its own (never c->lw / c->w)
+    DevBuf runs_out;               // its per-run results [K][PF_PSIS_RUN_OUT]: pareto_k, tail length, sigma, logsumexp, sum of squared weights
 };
 
 // small host -> device upload on the ctx stream WITHOUT synchronising it (pinned arena); large blocks take the synchronous path
@@ -315,6 +317,9 @@ int32_t pf_launch_mixture_comp(pfmi_ctx *c, int K, const int32_t *d_points, int6
 // mixture-proposal log ratios of the ctx's pool into c->pool_lmix (log qbar) and c->pool_lr_mix (pool_lp - log qbar), pool_mixture_kernels.hip
 int32_t pf_launch_pool_mixture_ratios(pfmi_ctx *c);
 int32_t pf_launch_psis(pfmi_ctx *c, const double *d_lr, int64_t S);
+#define PF_PSIS_RUN_OUT 5
+// PSIS of each of the K runs' N_r log ratios on its own (d_lr: device, run-major) into c->runs_lw, c->runs_w, c->runs_out; psis_kernels.hip
+int32_t pf_launch_psis_runs(pfmi_ctx *c, const double *d_lr, int K, int64_t N_r);
 // weighted moments of the ctx's pool into c->mom (weights c->w + col_offset when importance != 0; d_center: device, d doubles or NULL)
 int32_t pf_launch_pool_moments(pfmi_ctx *c, int64_t col_offset, int importance, const double *d_center);
 // weighted CDF of the ctx's pool at nthr thresholds per row into c->pcdf (d_thr, d_carry: device, nthr d doubles; d_carry may be NULL)

@@ -6,6 +6,8 @@
 //                        ((value, index) composite order -> deterministic under ties), LDS bitonic
 //                        sort of the tail, GPD profile-likelihood grid (one wave per theta), tail
 //                        replacement by GPD quantiles, logsumexp normalisation.
+//   pf_psis_runs_kernel: the same arithmetic (one device function, pf_psis_segment) on every run's slice of the pool, one workgroup
+//                        per run, all runs in one launch (pfmi_pool_psis_runs).
 //   pf_cdf_kernel      : exact fixed-point CDF (u64 prefix sums of floor(w 2^62)); integer arithmetic
 //                        makes the table independent of summation order, launch geometry and GPU count.
 //   pf_sample_kernel   : inverse-CDF index draw (stands in for StatsBase.sample, src/resample.jl:61-66).
@@ -313,10 +315,11 @@ __global__ __launch_bounds__(PSIS_MT) void pf_psis_norm_kernel(long long S, cons
 // out[0] = pareto_k, out[1] = tail length M, out[2] = sigma (scaled), out[3] = logsumexp
 // MULTI: the passes over S run in the multi-workgroup kernels above; this workgroup sorts the candidates (or selects by itself when
 // the candidate list overflowed), fits the tail and leaves the smoothed tail + normalisation constants in `aux`.
+// The one statement of the arithmetic: PSIS of the segment lr[0..S) by the calling 1024-thread workgroup (indices, ties and outputs are
+// relative to the segment).  pf_psis_kernel runs it on the whole vector, pf_psis_runs_kernel on one run's slice of the pool.
 template <bool MULTI>
-__global__ __launch_bounds__(PSIS_THREADS) void pf_psis_kernel(long long S, const double *__restrict__ lr,
-                                                               double *__restrict__ lw, double *__restrict__ wout,
-                                                               double *__restrict__ out, int M, PsisAux *aux) {
+__device__ __forceinline__ void pf_psis_segment(long long S, const double *__restrict__ lr, double *__restrict__ lw,
+                                                double *__restrict__ wout, double *__restrict__ out, int M, PsisAux *aux) {
     const int tid = threadIdx.x, nt = blockDim.x, lane = tid & 63, wave = tid >> 6, nw = nt >> 6;
     __shared__ uint64_t tkeys[TAILCAP];   // reused as double w[] after the sort
     __shared__ uint32_t tidx[TAILCAP];
@@ -513,6 +516,32 @@ __global__ __launch_bounds__(PSIS_THREADS) void pf_psis_kernel(long long S, cons
     PS_STAMP(5);
     if (tid == 0) printf("PSIS_PROF single S %lld M %d (10 ns): select+sort %lld vals %lld grid %lld mean+k %lld smooth %lld normalise %lld\n", S, M, ps_t[0], ps_t[1], ps_t[2], ps_t[3], ps_t[4], ps_t[5]);
 #endif
+}
+template <bool MULTI>
+__global__ __launch_bounds__(PSIS_THREADS) void pf_psis_kernel(long long S, const double *__restrict__ lr,
+                                                               double *__restrict__ lw, double *__restrict__ wout,
+                                                               double *__restrict__ out, int M, PsisAux *aux) {
+    pf_psis_segment<MULTI>(S, lr, lw, wout, out, M, aux);
+}
+
+// ---- per-run PSIS of the pool: one workgroup per run, all runs in one launch ---------------------------------------------------------
+// Workgroup k = blockIdx.x runs pf_psis_segment<false> on lr[k N_r .. (k + 1) N_r): the bits of pf_psis_kernel<false> on that slice,
+// whatever K, the run's position and the device.  out5[k] = {pareto_k, M, sigma, logsumexp, sum_n w_n^2}; lw, w [K N_r]: every run
+// normalised on its own.  The sum of squares re-reads the run's weights once they are all written: thread t adds w[t], w[t + 1024], ...
+// in that order and pf_block_sum1 adds the threads -- an order that depends on N_r only; a NaN weight makes it NaN.  No atomics on
+// global memory; nothing outside the run's slices of lw / w / out5 is written.
+__global__ __launch_bounds__(PSIS_THREADS) void pf_psis_runs_kernel(long long N_r, const double *__restrict__ lr, double *__restrict__ lw,
+                                                                    double *__restrict__ wout, double *__restrict__ out5, int M) {
+    __shared__ double red[PSIS_THREADS / 64];
+    const size_t base = (size_t)blockIdx.x * (size_t)N_r;
+    double *o = out5 + (size_t)blockIdx.x * PF_PSIS_RUN_OUT;
+    pf_psis_segment<false>(N_r, lr + base, lw + base, wout + base, o, M, nullptr);
+    __syncthreads();                                               // the run's weights are in memory for every thread of the workgroup
+    const double *w = wout + base;
+    double ss = 0.0;
+    for (long long i = threadIdx.x; i < N_r; i += PSIS_THREADS) { const double x = w[i]; ss += x * x; }
+    ss = pf_block_sum1(ss, red);
+    if (threadIdx.x == 0) o[4] = ss;
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -890,6 +919,25 @@ int32_t pf_launch_psis(pfmi_ctx *c, const double *d_lr, int64_t S) {
     pf_kernel_end(c, "psis");
     PF_HIP(hipGetLastError());
     c->S_w = S;
+    return PFMI_OK;
+}
+
+// per-run PSIS of K N_r log ratios (d_lr: device, run-major) into c->runs_lw / c->runs_w [K N_r] and c->runs_out [K][PF_PSIS_RUN_OUT]; the
+// pooled result (c->lw, c->w, c->psis_out, c->S_w) is neither read nor written
+int32_t pf_launch_psis_runs(pfmi_ctx *c, const double *d_lr, int K, int64_t N_r) {
+    PF_CHECK(K >= 1 && N_r >= 1, PFMI_ERR_ARG, "psis_runs: empty pool");
+    const long long M = psis_tail_length(N_r);
+    PF_CHECK(M + 1 <= TAILCAP, PFMI_ERR_UNSUPPORTED, "psis_runs: %lld draws per run need a tail of %lld, beyond the one-workgroup route (%d)",
+             (long long)N_r, M, TAILCAP - 1);
+    const size_t S = (size_t)K * (size_t)N_r;
+    PF_TRY(c->runs_lw.ensure(sizeof(double) * S));
+    PF_TRY(c->runs_w.ensure(sizeof(double) * S));
+    PF_TRY(c->runs_out.ensure(sizeof(double) * PF_PSIS_RUN_OUT * (size_t)K));
+    pf_kernel_begin(c);
+    hipLaunchKernelGGL(pf_psis_runs_kernel, dim3((unsigned)K), dim3(PSIS_THREADS), 0, c->stream, (long long)N_r, d_lr, c->runs_lw.as<double>(),
+                       c->runs_w.as<double>(), c->runs_out.as<double>(), (int)M);
+    pf_kernel_end(c, "psis_runs");
+    PF_HIP(hipGetLastError());
     return PFMI_OK;
 }
 

@@ -1105,6 +1105,32 @@ function pool_mixture_ratios_dev(b::Batch)
 end
 
 """
+    pool_psis_runs(b::Batch, nruns, ndraws_per_run; source=:component, want_weights=false)
+        -> (; pareto_shape, tail_length, lse, sumsq, log_weights, weights)
+
+PSIS of every run of the engine's pool on the run's own `ndraws_per_run` log ratios, all runs in one launch (one workgroup per run):
+per run the Pareto k-hat, the tail length, the logsumexp of the smoothed log ratios (`lse .- log(ndraws_per_run)` is the run's own
+evidence estimate) and the sum of its squared normalised weights (`1 ./ sumsq` is its effective sample size); with `want_weights`
+also the `(ndraws_per_run, nruns)` log weights and weights, every run normalised on its own.  `source=:mixture` takes the ratios of the
+last `pool_mixture_ratios` on this pool.  A run's numbers have the bits of `PSIS.psis` of the library on that run's slice and the
+engine's current PSIS weights are left untouched.
+"""
+function pool_psis_runs(b::Batch, nruns::Integer, ndraws_per_run::Integer; source::Symbol=:component, want_weights::Bool=false)
+    _live(b.eng, b.gen)
+    src = source === :component ? Int32(0) : source === :mixture ? Int32(1) : throw(ArgumentError("source must be :component or :mixture"))
+    k = Vector{Float64}(undef, nruns)
+    M = Vector{Int64}(undef, nruns)
+    lse = Vector{Float64}(undef, nruns)
+    ss = Vector{Float64}(undef, nruns)
+    lw = want_weights ? Matrix{Float64}(undef, ndraws_per_run, nruns) : nothing
+    w = want_weights ? Matrix{Float64}(undef, ndraws_per_run, nruns) : nothing
+    check(ccall((:pfmi_pool_psis_runs, libpfmi), Int32,
+                (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                b.eng.ptr, src, k, M, lse, ss, want_weights ? lw : C_NULL, want_weights ? w : C_NULL))
+    return (; pareto_shape=k, tail_length=M, lse=lse, sumsq=ss, log_weights=lw, weights=w)
+end
+
+"""
     importance_covariance(result::Pathfinder.MultiPathfinderResult; importance=true)
 
 Posterior `mean`, `cov`, `corr`, `ess`, `ncandidates` and `pareto_shape` from ALL pooled candidates under their PSIS weights (uniform

@@ -392,6 +392,11 @@ class MultiPathfinderResult:        # src/multipath.jl:31-44
         never formed: importance_lowrank_covariance(self, rank, **kw)"""
         return importance_lowrank_covariance(self, rank, **kw)
 
+    def run_diagnostics(self, source="component"):
+        """every run's own Pareto k-hat, effective sample size and evidence estimate -- which runs a bad pooled k-hat comes from --
+        from one pass on the device over the pool: importance_run_diagnostics(self, source=source)"""
+        return importance_run_diagnostics(self, source=source)
+
     def __str__(self):                  # Base.show, src/multipath.jl:46-65
         lines = ["Multi-path Pathfinder result", f"  runs: {len(self.pathfinder_results)}", f"  draws: {self.draws.shape[1]}"]
         if self.psis_result is not None:
@@ -1055,6 +1060,62 @@ def importance_summary(result, *, importance=True):
     run_weights = np.concatenate([b[:, 0] for b in wsum_b]) / W
     S = len(result.pathfinder_results) * result.pathfinder_results[0].ndraws_per_run
     return ImportanceSummary(mean, var, np.sqrt(var), mcse, float(W * W / wtot[1]), run_weights, S, pareto_shape)
+
+
+@dataclass
+class RunDiagnostics:
+    """PSIS of every run of a multipathfinder result on the run's own ndraws_per_run candidates (importance_run_diagnostics); every
+    field has one entry per run, in run order."""
+    pareto_shape: np.ndarray        # k-hat of the run's own log ratios; NaN where PSIS does not smooth (fewer than 25 candidates, a non-finite tail)
+    tail_length: np.ndarray         # M = min(cld(N_r, 5), ceil(3 sqrt(N_r)))
+    ess: np.ndarray                 # 1 / sum w^2 of the run's own normalised, smoothed weights
+    log_evidence: np.ndarray        # logsumexp of the run's smoothed log ratios - log N_r: log Z estimated from this run alone
+    elbo: np.ndarray                # the ELBO estimate of the run's chosen fit; NaN when fit_iteration == 0
+    success: np.ndarray             # the run's success flag (bool)
+    ndraws_per_run: int             # N_r
+
+    def ok(self, threshold=0.7):
+        """mask of the runs whose k-hat is at most `threshold` (False where k-hat is NaN)"""
+        return _run_ok(self.pareto_shape, threshold)
+
+
+def _run_ok(pareto_shape, threshold=0.7):
+    with np.errstate(invalid="ignore"):
+        return np.asarray(pareto_shape, dtype=np.float64) <= threshold       # (NaN <= x is False)
+
+
+def _run_diagnostics_host(pareto_shape, tail_length, lse, sumsq, ndraws_per_run, elbo, success):
+    """The host arithmetic of importance_run_diagnostics, a pure function of the arrays Engine.pool_psis_runs downloads (concatenated
+    in run order): ess = 1 / sumsq, log_evidence = lse - log(ndraws_per_run) with the log taken once."""
+    sumsq = np.asarray(sumsq, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ess = 1.0 / sumsq
+    log_evidence = np.asarray(lse, dtype=np.float64) - np.log(np.float64(ndraws_per_run))
+    return RunDiagnostics(np.asarray(pareto_shape, dtype=np.float64), np.asarray(tail_length, dtype=np.int64), ess, log_evidence,
+                          np.asarray(elbo, dtype=np.float64), np.asarray(success, dtype=bool), int(ndraws_per_run))
+
+
+def importance_run_diagnostics(result, *, source="component"):
+    """Per-run Pareto diagnostics of a multipathfinder result: PSIS of each run's own ndraws_per_run candidates -- k-hat, tail length,
+    effective sample size, the run's own evidence estimate -- next to the run's ELBO and success flag, so that a bad pooled k-hat can
+    be traced to the runs behind it.  Every engine of `result.engines` rebuilds its block of the pool as importance_summary does and
+    makes ONE pass over it (Engine.pool_psis_runs: one workgroup per run); no pooled PSIS is run and no communicator is used, and the
+    engines' current PSIS weights stay as they are.  A run's numbers depend on its own candidates alone, so the result is
+    bit-identical for any number of engines.  source="mixture": the candidates are weighted against the uniform mixture of all runs'
+    fits (one engine, as proposal="mixture").  Raises StaleHandleError when the engines hold newer fits."""
+    if source not in PROPOSALS:
+        raise ValueError(f"source must be one of {PROPOSALS}, got {source!r}")
+    if source == "mixture":
+        _check_proposal("mixture", True, result.engines or [result.engine])
+    owners, _, _ = _rebuild_pool(result, False)
+    if source == "mixture":
+        owners[0][0].pool_mixture_ratios(want=False)
+    parts = [eng.pool_psis_runs(source) for eng, _ in owners]
+    runs = result.pathfinder_results
+    elbo = [r.elbo_estimates[r.fit_iteration - 1].value if r.fit_iteration >= 1 else float("nan") for r in runs]
+    cat = {name: np.concatenate([p[name] for p in parts]) for name in ("pareto_shape", "tail_length", "lse", "sumsq")}
+    return _run_diagnostics_host(cat["pareto_shape"], cat["tail_length"], cat["lse"], cat["sumsq"], runs[0].ndraws_per_run, elbo,
+                                 [r.success for r in runs])
 
 
 @dataclass

@@ -14,6 +14,7 @@ _dp = C.POINTER(C.c_double)
 _i32p = C.POINTER(C.c_int32)
 _i64p = C.POINTER(C.c_int64)
 _u64p = C.POINTER(C.c_uint64)
+RATIO_SOURCES = {"component": 0, "mixture": 1}     # include/pfmi.h PFMI_RATIOS_COMPONENT / PFMI_RATIOS_MIXTURE
 
 
 def _d(a):
@@ -606,6 +607,26 @@ class Engine:
         p, n = C.c_void_p(), C.c_int64()
         check(self.L.pfmi_pool_mixture_ratios_dev(self.ctx, C.byref(p), C.byref(n)))
         return p.value, n.value
+
+    def pool_psis_runs(self, source="component", want_weights=False):
+        """PSIS of every run of this engine's pool on its own N_r log ratios, all runs in one launch (include/pfmi.h
+        pfmi_pool_psis_runs): a dict of pareto_shape, tail_length, lse (logsumexp of the run's smoothed log ratios) and sumsq (sum of
+        the run's squared normalised weights), each of length K, plus log_weights and weights (K, N_r), every run normalised on its
+        own, with want_weights (None without).  source: "component" (pool_get()'s logp - logq) or "mixture" (the ratios of the last
+        pool_mixture_ratios on this pool).  A run's numbers have the bits of psis() on the run's slice through the one-workgroup
+        route and depend on nothing else; the engine's current PSIS result (psis_weights, resample_indices, the weighted pool
+        passes) is left untouched."""
+        if isinstance(source, str):
+            if source not in RATIO_SOURCES:
+                raise ValueError(f"source must be one of {tuple(RATIO_SOURCES)}, got {source!r}")
+            source = RATIO_SOURCES[source]
+        K, N_r = self.K, getattr(self, "N_r", 0)            # (no pool yet: the library says so)
+        k, M = np.empty(K), np.empty(K, dtype=np.int64)
+        lse, sumsq = np.empty(K), np.empty(K)
+        lw = np.empty((K, N_r)) if want_weights and N_r else None
+        w = np.empty((K, N_r)) if want_weights and N_r else None
+        check(self.L.pfmi_pool_psis_runs(self.ctx, int(source), _d(k), M.ctypes.data_as(_i64p), _d(lse), _d(sumsq), _d(lw), _d(w)))
+        return dict(pareto_shape=k, tail_length=M, lse=lse, sumsq=sumsq, log_weights=lw, weights=w)
 
     def psis(self, log_ratios, want_weights=True):
         lr = np.ascontiguousarray(log_ratios, dtype=np.float64)
