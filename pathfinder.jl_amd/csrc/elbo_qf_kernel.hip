@@ -45,6 +45,9 @@
 #ifndef QF_PHILOX_HOIST
 #define QF_PHILOX_HOIST 1              // 0: every generator call of the block loop runs all of its rounds (A/B builds)
 #endif
+#ifndef QF_PSEUDO_FLIGHT
+#define QF_PSEUDO_FLIGHT 1             // 0: the c/s column of the pseudo group loads its inputs row by row, behind guards (A/B builds)
+#endif
 #ifndef QF_NG2_MAXKC
 #define QF_NG2_MAXKC 20                // two groups per wave up to this KC (round 2: 12; KC = 16, 20 take the register-lean block body)
 #endif
@@ -489,17 +492,41 @@ __global__ __launch_bounds__(QF_THREADS) void pf_elbo_qf_kernel(ElboArgs A, int 
                 // pseudo group: column j of this lane is Vh[:, j] (j < KC) or c/s (j == KC); no RNG, no head transform
                 auto pseudo_cols = [&](const int g, const int blk, const int bl, double (&z)[4]) {
                     const int j = 16 * sl[g] + c;
+                    if constexpr (QF_PSEUDO_FLIGHT != 0 && TGT == 1) {
+                        // Gaussian targets: the inputs of the c/s column's four rows in one flight, from clamped addresses, then the
+                        // subtractions and divisions.  As guarded loads they were one round trip per row (the loads, s_waitcnt vmcnt(0), the
+                        // division), each of them waiting for the block's Wd loads as well, in the wave every other wave of the workgroup
+                        // waits for before the constants are published.  (The funnel's column is two loads per row; in one flight it costs
+                        // the register-lean body 16 B of scratch.)
+                        double pm[4], ptm[4], ps[4];
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int row = blk * 16 + 4 * q + r;
-                        double v = 0.0;
-                        if (j < KC) v = vs[qf_vh_pos<KC>(bl * 16 + 4 * q + r, j)];
-                        else if (j == KC && row < d) {
-                            double aa, cc;
-                            qf_row_ac<TGT>(A, mu, row, aa, cc);
-                            v = cc / sqa[row];
+                        for (int r = 0; r < 4; ++r) {
+                            const int row = blk * 16 + 4 * q + r, rc = row < d ? row : d - 1;
+                            pm[r] = mu[rc]; ptm[r] = A.t_mean[rc]; ps[r] = sqa[rc];
                         }
-                        z[r] = v;
+                        asm volatile("" ::: "memory");               // the loads stay above: none sinks into the guarded block of its row
+                        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const int row = blk * 16 + 4 * q + r;
+                            double v = 0.0;
+                            if (j < KC) v = vs[qf_vh_pos<KC>(bl * 16 + 4 * q + r, j)];
+                            else if (j == KC && row < d) v = (pm[r] - ptm[r]) / ps[r];       // c = mu - m as in qf_row_ac
+                            z[r] = v;
+                        }
+                    } else {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const int row = blk * 16 + 4 * q + r;
+                            double v = 0.0;
+                            if (j < KC) v = vs[qf_vh_pos<KC>(bl * 16 + 4 * q + r, j)];
+                            else if (j == KC && row < d) {
+                                double aa, cc;
+                                qf_row_ac<TGT>(A, mu, row, aa, cc);
+                                v = cc / sqa[row];
+                            }
+                            z[r] = v;
+                        }
                     }
                 };
                 if (any_pseudo) {                            // first batch only: mixed pseudo / real wave, no need to be fast

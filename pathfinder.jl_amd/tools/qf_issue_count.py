@@ -215,6 +215,28 @@ def steady_counts(asm, kc=12, tgt=1, rpad=8, ng=2):
     return per
 
 
+def prologue_load_trips(asm, kc=12, tgt=1, rpad=8, ng=2):
+    """(dependent global round trips, global loads) of the kernel's prologue: its text in layout order from the entry to the first
+    `s_barrier`.  A trip is an `s_waitcnt` with a vmcnt field whose next vector-memory event is a further `global_load`: the kernel
+    waited for what was in flight and then sent more.  One flight of loads, however many waits drain it, counts 0; a loop counts once."""
+    trips = loads = 0
+    waited = False
+    for l in kernel_lines(asm, mangled(kc, tgt, rpad, ng))[1:]:
+        s = l.strip().split(";")[0].strip()
+        if not s or s.startswith("."):
+            continue
+        op = s.split()[0]
+        if op == "s_barrier":
+            return trips, loads
+        if op == "s_waitcnt" and "vmcnt" in s:
+            waited = True
+        elif op.startswith("global_load"):
+            loads += 1
+            trips += waited
+            waited = False
+    raise RuntimeError("no s_barrier in the kernel")
+
+
 def main(argv):
     asm_file = None
     if argv[:1] == ["--asm"]:
@@ -228,6 +250,8 @@ def main(argv):
         for k in CLASSES:
             print(f"  {k:12s} {r[k]:7.1f}")
         print(f"  {'~cycles':12s} MFMA {r['mfma_cycles']:.0f} + other {r['non_mfma_cycles']:.0f}")
+        t, n = prologue_load_trips(asm, *inst)
+        print(f"  prologue: {n} global loads, {t} dependent round trip(s) behind the first flight")
 
 
 if __name__ == "__main__":
