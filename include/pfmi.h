@@ -97,7 +97,7 @@ int32_t pfmi_sync(pfmi_ctx *ctx);
  * PFMI_DEVCB_CHUNK_MB, PFMI_LBFGS_REJECT_EVERY, the collective path's PFMI_RCCL_LIB / PFMI_COMM_ALLOW_SHARED_GPU / PFMI_COMM_FORCE_RCCL;
  * INTEGRATION.md section 3).  A hook is read from this explicit table, or from the environment variable of the same name ONLY when
  * the process was started with PFMI_DEBUG_HOOKS=1: a production process is never re-configured by a stray environment variable.
- * value == NULL unsets.  Process-global; set hooks before other threads use the library.  No reference counterpart. */
+ * value == NULL unsets: the hook is then read from the environment again (under PFMI_DEBUG_HOOKS=1) or is off.  Process-global; set hooks before other threads use the library.  No reference counterpart. */
 int32_t pfmi_debug_set(const char *key, const char *value);
 
 /* device-time instrumentation (hipEvents on the ctx stream).  pfmi_timer_* bracket any sequence of
@@ -113,7 +113,14 @@ int32_t pfmi_debug_set(const char *key, const char *value);
  * KC (4 .. 32), target kind TGT (0 none, 1 Gaussian, 2 funnel), target rank padding RPAD (0, 8, 16), NG 16-draw groups per
  * wave (1, 2), factor block resident in LDS or streamed in chunks, and cut "whole" (one workgroup per fit), "split" (few fits,
  * each cut into pieces), "tail-share" (one launch; the fits of the last partial round of CUs cut into pieces that share the
- * per-fit constants) or "tail-two" (the same tail as a second launch). */
+ * per-fit constants) or "tail-two" (the same tail as a second launch).
+ * The three kernels that make draws are counted the same way, one count per kernel launch:
+ * "xw:<KC>:<res|stream>:<whole|split>": the streaming draw writer -- column padding KC (4 .. 32), factor block resident in LDS
+ * or streamed in chunks, one workgroup per fit ("whole") or each fit's draw groups cut over several ("split").
+ * "mf:<KC>,<NBW>,<TGT>,<RPAD>:<x|nox>:<whole|split>": the two-pass MFMA kernel -- KC (4 .. 16), NBW 16-row blocks per wave
+ * (1, 2, 4, 8), TGT / RPAD as above, draws written ("x") or only their log densities ("nox"), and the cut as for the writer.
+ * "lane:<KPAD>,<TGT>,<RPAD>:<u|rng>:<x|nox>": the lane-per-draw kernel -- column padding KPAD (4 .. 64), normals supplied by
+ * the caller ("u") or made by the in-kernel generator ("rng"), draws written or not. */
 int32_t pfmi_timer_start(pfmi_ctx *ctx);
 int32_t pfmi_timer_stop(pfmi_ctx *ctx, double *milliseconds);
 int32_t pfmi_profile(pfmi_ctx *ctx, int32_t enable);

@@ -215,7 +215,9 @@ namespace {
 std::mutex g_dbg_mu;
 // key -> value.  A value is an immutable heap string that is NEVER freed or modified once published (a later pfmi_debug_set of the same key
 // installs a new string and leaks the old one: a few bytes per call of a test hook), so the pointer pf_debug_get hands out stays valid after
-// the mutex is released, whatever other threads set meanwhile.  An unset key keeps a nullptr tombstone.
+// the mutex is released, whatever other threads set meanwhile.  Unsetting a key erases its entry (the string stays allocated): the
+// environment governs that hook again.  (It used to leave a nullptr tombstone, which hid the environment from every later reader of the
+// process: after one set / unset of PFMI_ELBO_KERNEL, tests that selected a kernel through the environment ran the default one.)
 std::map<std::string, const char *> g_dbg;
 }
 const char *pf_debug_get(const char *name) {
@@ -257,7 +259,8 @@ int32_t pfmi_debug_set(const char *key, const char *value) {
     const char *copy = (value && value[0]) ? strdup(value) : nullptr;
     PF_CHECK(copy != nullptr || !(value && value[0]), PFMI_ERR_ARG, "debug_set: out of memory");
     std::lock_guard<std::mutex> lk(g_dbg_mu);
-    g_dbg[key] = copy;                                   // the previous string (if any) is deliberately leaked: readers may still hold it
+    if (copy) g_dbg[key] = copy;                         // the previous string (if any) is deliberately leaked: readers may still hold it
+    else g_dbg.erase(key);
     return PFMI_OK;
 }
 int32_t pfmi_version(void) { return 100; }
@@ -365,6 +368,12 @@ int32_t pfmi_kernel_time(pfmi_ctx *c, const char *name, double *ms, int64_t *lau
         auto pl = c->qf_plans.find(name);
         if (ms) *ms = 0.0;
         if (launches) *launches = (pl == c->qf_plans.end()) ? 0 : pl->second;
+        return PFMI_OK;
+    }
+    if (strncmp(name, "xw:", 3) == 0 || strncmp(name, "mf:", 3) == 0 || strncmp(name, "lane:", 5) == 0) {   // launches of one draw-kernel plan, host-side count
+        auto pl = c->draw_plans.find(name);
+        if (ms) *ms = 0.0;
+        if (launches) *launches = (pl == c->draw_plans.end()) ? 0 : pl->second;
         return PFMI_OK;
     }
     auto it = c->kstats.find(name);

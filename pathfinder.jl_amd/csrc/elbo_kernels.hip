@@ -413,6 +413,11 @@ int32_t pf_launch_elbo_draws(pfmi_ctx *c, const int32_t *d_points, const uint64_
         if (!pf_dispatch_kpad<4, 8, 12, 16, 20, 32, 64>(c->kpad, [&](auto KP) { rc = launch_draws_k<KP()>(b, grid, c->stream, mem, tgt, rpad); })) {
             pf_set_error("unsupported kpad %d", c->kpad); rc = PFMI_ERR_UNSUPPORTED;
         }
+        if (rc == PFMI_OK) {
+            char nm[64];
+            snprintf(nm, sizeof nm, "lane:%d,%d,%d:%s:%s", c->kpad, tgt, rpad, mem ? "u" : "rng", d_x ? "x" : "nox");
+            pf_note_draw_plan(c, nm);
+        }
         pf_kernel_end(c, d_x ? "elbo_draws_x" : "elbo_draws");
         PF_TRY(rc);
         PF_HIP(hipGetLastError());

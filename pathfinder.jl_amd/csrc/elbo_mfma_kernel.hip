@@ -505,6 +505,9 @@ static int32_t launch_mf(pfmi_ctx *c, const ElboArgs &a, int64_t nfits) {
         if (b.x) b.x += s0 * a.x_stride;
         if (!a.by_point) { b.logp += s0 * a.log_stride; b.logq += s0 * a.log_stride; }
         hipLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)ns), dim3(MF_THREADS), lds_bytes, c->stream, b, gpb, ngroups);
+        char nm[64];
+        snprintf(nm, sizeof nm, "mf:%d,%d,%d,%d:%s:%s", KC, NBW, TGT, RPAD, WX ? "x" : "nox", split > 1 ? "split" : "whole");
+        pf_note_draw_plan(c, nm);
     }
     return PFMI_OK;
 }

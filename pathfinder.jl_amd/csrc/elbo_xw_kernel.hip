@@ -502,6 +502,9 @@ static int32_t launch_xw(pfmi_ctx *c, const ElboArgs &a, int64_t nfits) {
         b.x = a.x + s0 * a.x_stride;
         if (!a.by_point) { b.logp += s0 * a.log_stride; b.logq += s0 * a.log_stride; }
         hipLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)ns), dim3(XW_THREADS), lds_bytes, c->stream, b, ch_blocks, nchunks, gpw, ngroups);
+        char nm[48];
+        snprintf(nm, sizeof nm, "xw:%d:%s:%s", KC, nchunks > 1 ? "stream" : "res", split > 1 ? "split" : "whole");
+        pf_note_draw_plan(c, nm);
     }
     return PFMI_OK;
 }

@@ -70,8 +70,7 @@ def test_closure_lbfgs_traces_match_oracle_driver(pfmi_mod, eng, name, d, J, max
 
 def test_closure_lbfgs_rejected_pair_branch(pfmi_mod, eng, monkeypatch):
     """PFMI_LBFGS_REJECT_EVERY: every 3rd pair fails the curvature test, as the host driver's _reject_every.  (The hook is set through the
-    environment, which the test process honours, as test_device_lbfgs_rejected_pairs_follow_the_host_driver does: a key once set with
-    pfmi_debug_set keeps a tombstone that would hide the environment from the later tests of the process.)"""
+    environment, which the test process honours, as test_device_lbfgs_rejected_pairs_follow_the_host_driver does.)"""
     from pfmi.optimize import optimize_with_trace
     tg = pfmi_mod.t_lowrank(200, 8, 2)
     x0 = pfmi_mod.HostRNG(5).rand(2 * 200).reshape(2, 200) * 4 - 2
