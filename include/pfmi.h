@@ -431,6 +431,33 @@ int32_t pfmi_pool_mixture_ratios(pfmi_ctx *ctx, double *log_mix, double *log_rat
  * return.  Valid until the next pfmi_pool_build* on this ctx; no pfmi_pool_mixture_ratios on the current pool: PFMI_ERR_STATE. */
 int32_t pfmi_pool_mixture_ratios_dev(pfmi_ctx *ctx, void **dev_ptr, int64_t *count);
 
+/* One affine map for every column of the pool, and the target at the moved columns: the pass of importance-weighted moment matching
+ * (Paananen, Piironen, Buerkner, Vehtari 2021).  With x0 the pool AS BUILT by pfmi_pool_build[_best], every column becomes
+ *   x' = fma(scale, x0, shift)   (elementwise over the d rows; scale[d] all > 0 and finite, shift[d] finite)
+ * The map is CUMULATIVE: it is always applied to x0, never on top of an earlier call, so the bits do not depend on the calls before
+ * and a rebuilt pool plus one call reproduces them.  In the same pass logp(x') is formed for the built-in targets (host and device
+ * closures are called on the moved pool as pfmi_pool_build calls them), then
+ *   logq' = logq0 - sum_i log scale_i      (every run's proposal under the same map; the sum is taken once on the host, in index order)
+ *   log ratio' = logp' - logq'
+ * and, when pfmi_pool_mixture_ratios ran on the pool as built, mixture ratio' = logp' - (log qbar0 - sum_i log scale_i).
+ * After the call the ctx's pool IS the moved pool: pfmi_pool_get, pfmi_pool_moments / _cdf / _cross / _apply, pfmi_pool_psis_runs, the
+ * gather, pfmi_pool_*_dev (pointers fetched AFTER the call) and the communicator's PSIS and resampling see it without change.  The
+ * state before the call is kept for pfmi_pool_transform_revert.  A column whose run's fit failed keeps NaN densities.
+ * scale == NULL: all ones; shift == NULL: zeros; both NULL: the pool as built is put back (no pass).
+ * logp_out, log_ratios_out: K_local * N_r doubles, either may be NULL.  The ctx's PSIS weights are not touched.
+ * Ordering guarantee: the terms of a column's logp are added in an order that depends on d alone.
+ * While the pool is moved pfmi_pool_mixture_ratios returns PFMI_ERR_STATE (put the pool as built back first).
+ * No pool: PFMI_ERR_STATE; a scale that is not positive and finite or a shift that is not finite: PFMI_ERR_ARG, the pool is left as
+ * it was -- a refused call changes NOTHING, including what pfmi_pool_transform_revert would undo: a revert after it still puts back the
+ * state from before the last call that succeeded.  A new pfmi_pool_build* drops all transform state.  Stage names under pfmi_profile:
+ * "pool_transform" (the pass), "pool_transform_ratio".  Memory: the pool as built and the state before the last call stay resident
+ * (up to three pools) while the pool is one that was transformed; the next pfmi_pool_build* of a pool of ANOTHER size frees the two
+ * spare sets (a rebuild of the same size, as the summaries of a moment-matched result do, keeps them and allocates nothing). */
+int32_t pfmi_pool_transform(pfmi_ctx *ctx, const double *scale, const double *shift, double *logp_out, double *log_ratios_out);
+/* Puts the state from before the last pfmi_pool_transform back (a buffer swap, no pass): how a rejected trial is undone.  A second
+ * revert in a row, a revert with nothing to undo or without a pool: PFMI_ERR_STATE.  The ctx's PSIS weights are not touched. */
+int32_t pfmi_pool_transform_revert(pfmi_ctx *ctx);
+
 /* Per-run Pareto diagnostics of the pool: PSIS.psis of every run's own N_r log ratios, all K runs in one launch (one workgroup per
  * run).  source selects the ratios: */
 #define PFMI_RATIOS_COMPONENT 0   /* logp - logq of the run that drew the column (pfmi_pool_get) */

@@ -1,6 +1,7 @@
 // api_pool.hip -- the pooled stage: pool of draws, PSIS, resampling, gather.
 #include "api_internal.h"
 
+#include <math.h>
 #include <vector>
 
 // ---- pool / PSIS / resample ---------------------------------------------------------------------------
@@ -15,6 +16,16 @@ static int32_t pool_alloc(pfmi_ctx *c, int64_t N_r) {
     PF_TRY(c->pool_points.ensure(sizeof(int32_t) * K));
     PF_TRY(c->pool_seeds.ensure(sizeof(uint64_t) * K));
     c->pool_mix_done = false;              // the mixture-proposal ratios belong to the pool they were formed on
+    c->pool_lmix_ok = false;
+    c->tr_base = 0;                        // a new pool is a pool as built: no transform state survives
+    c->tr_undo = 0;
+    if (c->tr_bytes != 0 && c->tr_bytes != sizeof(double) * S * d) {   // spare sets made for a pool of another size are freed (a rebuild
+        PF_HIP(hipStreamSynchronize(c->stream));                       // of the same size -- the summaries of a moment-matched result --
+        for (pfmi_ctx::PoolSet *s : {&c->tr_a, &c->tr_b}) {            // keeps them and allocates nothing)
+            s->x.release(); s->lp.release(); s->lq.release(); s->lr.release(); s->lr_mix.release();
+        }
+        c->tr_bytes = 0;
+    }
     return PFMI_OK;
 }
 
@@ -60,7 +71,109 @@ static int32_t upload_optional(pfmi_ctx *c, DevBuf &buf, const double *host, siz
     return PFMI_OK;
 }
 
+// ---- pfmi_pool_transform: the current pool state against a spare set, whole buffers at a time
+#define PF_TR_UNDO_TO_BUILT 1     // the call moved the pool as built: swap with tr_a, the current state is the pool as built again
+#define PF_TR_UNDO_TO_MOVED 2     // the call moved a moved pool: swap with tr_b
+#define PF_TR_UNDO_IDENTITY 3     // the call restored the pool as built over a moved pool: swap with tr_a, then with tr_b
+#define PF_TR_UNDO_NOTHING 4      // the call restored the pool as built and it was current already
+
+static void devbuf_swap(DevBuf &a, DevBuf &b) {
+    void *p = a.p; a.p = b.p; b.p = p;
+    const size_t cap = a.cap; a.cap = b.cap; b.cap = cap;
+}
+static void pool_set_swap(pfmi_ctx *c, pfmi_ctx::PoolSet &s) {
+    devbuf_swap(c->pool, s.x); devbuf_swap(c->pool_lp, s.lp); devbuf_swap(c->pool_lq, s.lq); devbuf_swap(c->pool_lr, s.lr);
+    devbuf_swap(c->pool_lr_mix, s.lr_mix);
+}
+
+// the moved pool into the current buffers (tr_a holds the pool as built): the pass, the closures as pool_fill runs them, the ratios
+static int32_t pool_transform_fill(pfmi_ctx *c, const double *d_scale, const double *d_shift, double sla) {
+    const int K = c->K;
+    const int64_t N_r = c->N_r;
+    const size_t S = (size_t)K * N_r;
+    const bool cb = c->target.kind == PFMI_TARGET_HOST_CALLBACK, dcb = c->target.kind == PFMI_TARGET_DEVICE_CALLBACK;
+    PF_TRY(pf_launch_pool_transform(c, c->tr_a.x.as<double>(), d_scale, d_shift, c->pool.as<double>(), c->pool_lp.as<double>()));
+    if (cb) PF_TRY(callback_logp(c, c->pool.as<double>(), (int64_t)S, c->pool_lp.as<double>()));
+    if (dcb) PF_TRY(devcb_logp(c, c->pool.as<double>(), (int64_t)S, c->pool_lp.as<double>(), c->pool_points.as<int32_t>(), K, N_r));
+    return pf_launch_pool_transform_ratio(c, sla, c->tr_a.lq.as<double>(), c->pool_lmix_ok ? c->pool_lmix.as<double>() : nullptr,
+                                          c->pool_lp.as<double>(), c->pool_lq.as<double>(), c->pool_lr.as<double>(),
+                                          c->pool_lmix_ok ? c->pool_lr_mix.as<double>() : nullptr);
+}
+
 extern "C" {
+
+int32_t pfmi_pool_transform(pfmi_ctx *c, const double *scale, const double *shift, double *logp_out, double *log_ratios_out) {
+    PF_CTX_MUT(c);
+    PF_CHECK(c->pooled, PFMI_ERR_STATE, "pool_transform: call pfmi_pool_build first");
+    const int d = c->d;
+    const size_t S = (size_t)c->K * c->N_r;
+    double sla = 0.0;
+    for (int i = 0; i < d; ++i) {
+        PF_CHECK(!scale || (scale[i] > 0.0 && scale[i] <= 1.7976931348623157e308), PFMI_ERR_ARG,
+                 "pool_transform: scale[%d] = %g is not positive and finite", i, scale[i]);
+        PF_CHECK(!shift || (shift[i] >= -1.7976931348623157e308 && shift[i] <= 1.7976931348623157e308), PFMI_ERR_ARG,
+                 "pool_transform: shift[%d] = %g is not finite", i, shift[i]);
+        if (scale) sla += log(scale[i]);                                // index order: the ONE statement of sum log scale
+    }
+    const bool mix_before = c->pool_mix_done;
+    if (!scale && !shift) {                                             // the pool as built, without a pass
+        if (c->tr_base == 0) {
+            c->tr_undo = PF_TR_UNDO_NOTHING;
+        } else {
+            pool_set_swap(c, c->tr_b);
+            pool_set_swap(c, c->tr_a);
+            c->tr_base = 0;
+            c->tr_undo = PF_TR_UNDO_IDENTITY;
+            c->pool_mix_done = c->pool_lmix_ok;
+        }
+        c->tr_undo_mix = mix_before;
+    } else {
+        std::vector<double> h((size_t)2 * d);
+        for (int i = 0; i < d; ++i) { h[(size_t)i] = scale ? scale[i] : 1.0; h[(size_t)d + i] = shift ? shift[i] : 0.0; }
+        PF_TRY(c->tr_scale.ensure(sizeof(double) * d));
+        PF_TRY(c->tr_shift.ensure(sizeof(double) * d));
+        pfmi_ctx::PoolSet &keep = c->tr_base == 0 ? c->tr_a : c->tr_b;  // where the state before the call goes
+        PF_TRY(keep.x.ensure(sizeof(double) * S * d));                  // (every allocation before the first swap: a failure leaves the pool as it was)
+        PF_TRY(keep.lp.ensure(sizeof(double) * S));
+        PF_TRY(keep.lq.ensure(sizeof(double) * S));
+        PF_TRY(keep.lr.ensure(sizeof(double) * S));
+        if (c->pool_lmix_ok) PF_TRY(keep.lr_mix.ensure(sizeof(double) * S));
+        PF_TRY(pf_upload(c, c->tr_scale.p, h.data(), sizeof(double) * d));
+        PF_TRY(pf_upload(c, c->tr_shift.p, h.data() + d, sizeof(double) * d));
+        c->tr_bytes = sizeof(double) * S * d;
+        const int base_before = c->tr_base;
+        pool_set_swap(c, keep);
+        c->tr_base = 1;
+        const int32_t rc = pool_transform_fill(c, c->tr_scale.as<double>(), c->tr_shift.as<double>(), sla);
+        if (rc != PFMI_OK) {                                            // nothing happened
+            pool_set_swap(c, keep);
+            c->tr_base = base_before;
+            return rc;
+        }
+        c->tr_undo = base_before == 0 ? PF_TR_UNDO_TO_BUILT : PF_TR_UNDO_TO_MOVED;
+        c->tr_undo_mix = mix_before;
+        c->pool_mix_done = c->pool_lmix_ok;
+    }
+    if (logp_out) PF_TRY(pf_download(c, logp_out, c->pool_lp.p, sizeof(double) * S));
+    if (log_ratios_out) PF_TRY(pf_download(c, log_ratios_out, c->pool_lr.p, sizeof(double) * S));
+    return pf_stream_sync(c);
+}
+
+int32_t pfmi_pool_transform_revert(pfmi_ctx *c) {
+    PF_CTX_MUT(c);
+    PF_CHECK(c->pooled, PFMI_ERR_STATE, "pool_transform_revert: call pfmi_pool_build first");
+    PF_CHECK(c->tr_undo != 0, PFMI_ERR_STATE, "pool_transform_revert: no pfmi_pool_transform to undo");
+    PF_HIP(hipStreamSynchronize(c->stream));
+    switch (c->tr_undo) {
+    case PF_TR_UNDO_TO_BUILT: pool_set_swap(c, c->tr_a); c->tr_base = 0; break;
+    case PF_TR_UNDO_TO_MOVED: pool_set_swap(c, c->tr_b); break;
+    case PF_TR_UNDO_IDENTITY: pool_set_swap(c, c->tr_a); pool_set_swap(c, c->tr_b); c->tr_base = 1; break;
+    default: break;
+    }
+    c->pool_mix_done = c->tr_undo_mix;
+    c->tr_undo = 0;
+    return PFMI_OK;
+}
 
 int32_t pfmi_pool_build(pfmi_ctx *c, int64_t N_r, const int64_t *points, const uint64_t *seeds) {
     PF_CTX_MUT(c);
@@ -204,9 +317,14 @@ int32_t pfmi_pool_log_ratios_dev(pfmi_ctx *c, void **dev_ptr, int64_t *count) {
 int32_t pfmi_pool_mixture_ratios(pfmi_ctx *c, double *log_mix, double *log_ratios) {
     PF_CTX_MUT(c);
     PF_CHECK(c->pooled, PFMI_ERR_STATE, "pool_mixture_ratios: call pfmi_pool_build first");
+    PF_CHECK(c->tr_base == 0, PFMI_ERR_STATE,
+             "pool_mixture_ratios: the pool is moved (pfmi_pool_transform): its mixture ratios follow from those of the pool as built");
     c->pool_mix_done = false;
+    c->pool_lmix_ok = false;
+    c->tr_undo = 0;                        // (a state to put back would not have these ratios)
     PF_TRY(pf_launch_pool_mixture_ratios(c));
     c->pool_mix_done = true;
+    c->pool_lmix_ok = true;
     const size_t S = (size_t)c->K * c->N_r;
     if (log_mix) PF_TRY(pf_download(c, log_mix, c->pool_lmix.p, sizeof(double) * S));
     if (log_ratios) PF_TRY(pf_download(c, log_ratios, c->pool_lr_mix.p, sizeof(double) * S));

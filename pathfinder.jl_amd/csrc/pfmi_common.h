@@ -285,6 +285,17 @@ struct pfmi_ctx {
     DevBuf pool_mix_comp;          // its scratch comp [K][chunk] (at most 64 MB: the pool is walked in chunks of columns)
     DevBuf runs_lw, runs_w;        // pfmi_pool_psis_runs: log weights and weights [K*N_r], every run normalised on its own (never c->lw / c->w)
     DevBuf runs_out;               // its per-run results [K][PF_PSIS_RUN_OUT]: pareto_k, tail length, sigma, logsumexp, sum of squared weights
+    // pfmi_pool_transform: two spare sets of the pool's buffers.  The CURRENT state is always pool / pool_lp / pool_lq / pool_lr /
+    // pool_lr_mix above (what every pass, the gather and the communicator read); a transform or a revert SWAPS whole sets, never copies.
+    struct PoolSet { DevBuf x, lp, lq, lr, lr_mix; };
+    PoolSet tr_a;                  // tr_base == 1: the pool AS BUILT (x0, lp0, lq0, lr0, lr_mix0), the source of every transform
+    PoolSet tr_b;                  // the state before the last transform when that state was itself a moved pool
+    int tr_base = 0;               // 0: the current state is the pool as built; 1: it is a moved pool and tr_a holds the pool as built
+    int tr_undo = 0;               // what pfmi_pool_transform_revert does (PF_TR_UNDO_*; 0: nothing to undo)
+    size_t tr_bytes = 0;           // bytes of the pool the spare sets were allocated for (0: none); pool_alloc frees them when the size changes
+    bool tr_undo_mix = false;      // pool_mix_done of the state a revert puts back
+    bool pool_lmix_ok = false;     // pool_lmix holds log qbar of the pool AS BUILT (pfmi_pool_mixture_ratios ran on it)
+    DevBuf tr_scale, tr_shift;     // the map's two vectors [d]
 };
 
 // small host -> device upload on the ctx stream WITHOUT synchronising it (pinned arena); large blocks take the synchronous path
@@ -319,6 +330,11 @@ int32_t pf_launch_mixture_logpdf(pfmi_ctx *c, int K, const int32_t *d_points, in
 int32_t pf_launch_mixture_comp(pfmi_ctx *c, int K, const int32_t *d_points, int64_t N, const double *d_x, double *d_comp);
 // mixture-proposal log ratios of the ctx's pool into c->pool_lmix (log qbar) and c->pool_lr_mix (pool_lp - log qbar), pool_mixture_kernels.hip
 int32_t pf_launch_pool_mixture_ratios(pfmi_ctx *c);
+// pool_transform_kernels.hip: x1 = scale .* x0 + shift over the ctx's K N_r columns (d_scale, d_shift: d doubles on the device) and, for a
+// built-in target, lp = logp(x1); then lq = lq0 - sla, lr = lp - lq and, with lmix0, lr_mix = lp - (lmix0 - sla) (lp of a NaN lq0 becomes NaN)
+int32_t pf_launch_pool_transform(pfmi_ctx *c, const double *x0, const double *d_scale, const double *d_shift, double *x1, double *lp);
+int32_t pf_launch_pool_transform_ratio(pfmi_ctx *c, double sla, const double *lq0, const double *lmix0, double *lp, double *lq, double *lr,
+                                       double *lr_mix);
 int32_t pf_launch_psis(pfmi_ctx *c, const double *d_lr, int64_t S);
 #define PF_PSIS_RUN_OUT 5
 // PSIS of each of the K runs' N_r log ratios on its own (d_lr: device, run-major) into c->runs_lw, c->runs_w, c->runs_out; psis_kernels.hip

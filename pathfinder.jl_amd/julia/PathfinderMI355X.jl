@@ -1105,6 +1105,32 @@ function pool_mixture_ratios_dev(b::Batch)
 end
 
 """
+    pool_transform(b::Batch, ncolumns; scale=nothing, shift=nothing) -> (logp, log_ratios)
+
+One affine map for every column of the engine's pool and the target at the moved columns, in one pass on the device: every column
+becomes `fma.(scale, x0, shift)` with `x0` the pool as built -- the map is cumulative, never applied on top of an earlier call -- and
+`logp`, `logq` (minus `sum(log, scale)`), the log ratios and the mixture ratios (when `pool_mixture_ratios` ran on the pool as built)
+are those of the moved pool, which every later pool pass, the gather and the communicator see.  `scale === nothing`: ones;
+`shift === nothing`: zeros; both: the pool as built is put back.  `pool_transform_revert` undoes the last call without a pass.  The
+engine's PSIS weights stay as they are.
+"""
+function pool_transform(b::Batch, ncolumns::Integer; scale::Union{Nothing,Vector{Float64}}=nothing,
+                        shift::Union{Nothing,Vector{Float64}}=nothing)
+    _live(b.eng, b.gen)
+    lp = Vector{Float64}(undef, ncolumns)
+    lr = Vector{Float64}(undef, ncolumns)
+    check(ccall((:pfmi_pool_transform, libpfmi), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                b.eng.ptr, scale === nothing ? C_NULL : scale, shift === nothing ? C_NULL : shift, lp, lr))
+    return lp, lr
+end
+
+function pool_transform_revert(b::Batch)
+    _live(b.eng, b.gen)
+    check(ccall((:pfmi_pool_transform_revert, libpfmi), Int32, (Ptr{Cvoid},), b.eng.ptr))
+    return nothing
+end
+
+"""
     pool_psis_runs(b::Batch, nruns, ndraws_per_run; source=:component, want_weights=false)
         -> (; pareto_shape, tail_length, lse, sumsq, log_weights, weights)
 

@@ -6,7 +6,7 @@ requires the built HIP library and a visible MI355X, and raises otherwise.
 from ._lib import PfmiError, build, lib  # noqa: F401
 from .api import (DEFAULT_HISTORY_LENGTH, DEFAULT_NDRAWS_ELBO, ELBOEstimate, ImportanceCovariance, ImportanceSummary, LowRankCovariance, MixtureModel, MultiPathfinderResult,  # noqa: F401
                   MvNormal, PathfinderResult, PosDefException, PSISResult, RunDiagnostics, UniformSampler, WoodburyPDMat,
-                  fit_mvnormals, importance_covariance, importance_lowrank_covariance, importance_quantiles, importance_run_diagnostics, importance_summary, maximize_elbo, multipathfinder, pathfinder, resample)
+                  fit_mvnormals, importance_covariance, importance_lowrank_covariance, importance_quantiles, importance_run_diagnostics, importance_summary, maximize_elbo, moment_match, moment_match_step, multipathfinder, pathfinder, resample)
 from .core import Comm, Engine, StaleHandleError  # noqa: F401
 from .hostrng import HostRNG  # noqa: F401
 from .optimize import OptimizationTrace, optimize_with_trace  # noqa: F401

@@ -51,6 +51,7 @@ SYMBOLS = [
     "pfmi_set_target_gradient", "pfmi_optimize_batch_pump", "pfmi_optimize_batch_cancel", "pfmi_optimize_stats",
     "pfmi_pool_mixture_ratios", "pfmi_pool_mixture_ratios_dev",
     "pfmi_pool_psis_runs",
+    "pfmi_pool_transform", "pfmi_pool_transform_revert",
 ]
 
 # declared argument types (entry points not listed here take what the caller wraps by hand)
@@ -61,6 +62,8 @@ ARGTYPES = {
     "pfmi_pool_cross": [C.c_void_p, C.c_int64, C.c_int32, _dp, _dp, _dp],
     "pfmi_pool_apply": [C.c_void_p, C.c_int64, C.c_int32, _dp, C.c_int32, _dp, _dp, _dp, _dp],
     "pfmi_pool_mixture_ratios": [C.c_void_p, _dp, _dp],
+    "pfmi_pool_transform": [C.c_void_p, _dp, _dp, _dp, _dp],
+    "pfmi_pool_transform_revert": [C.c_void_p],
     "pfmi_pool_psis_runs": [C.c_void_p, C.c_int32, _dp, C.POINTER(C.c_int64), _dp, _dp, _dp, _dp],
 }
 

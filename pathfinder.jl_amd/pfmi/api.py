@@ -13,6 +13,7 @@ src/multipath.jl:190-193), then ONE fit_batch / elbo_batch / pool_build covers e
 (The north-star host language is Julia; no Julia toolchain exists in this image, so the host mirror
 is Python and the Julia `ccall` wrapper lives, untested, in pathfinder.jl_amd/julia/ -- INTEGRATION.md.)
 """
+import dataclasses
 import gc
 import os
 import warnings
@@ -363,6 +364,8 @@ class MultiPathfinderResult:        # src/multipath.jl:31-44
     ndraws_per_run: int = 0
     engines: Any = field(repr=False, default=None)      # the engines the runs are sharded over (contiguous blocks)
     proposal: str = "component"                         # what the PSIS weights divide logp by: the run's own fit, or the "mixture" of all
+    pool_transform: Any = None                          # moment_match: the (scale, shift) every pooled candidate is moved by; None: as drawn
+    moment_match_history: Any = None                    # moment_match: [(step name, k-hat, accepted), ...]
 
     @property
     def fit_distribution_transformed(self): return self.fit_distribution
@@ -391,6 +394,10 @@ class MultiPathfinderResult:        # src/multipath.jl:31-44
         """the top `rank` eigenpairs of the importance-weighted posterior covariance plus its residual diagonal, the (d, d) matrix
         never formed: importance_lowrank_covariance(self, rank, **kw)"""
         return importance_lowrank_covariance(self, rank, **kw)
+
+    def moment_match(self, **kw):
+        """importance-weighted moment matching of the pooled candidates on the device: moment_match(self, **kw)"""
+        return moment_match(self, **kw)
 
     def run_diagnostics(self, source="component"):
         """every run's own Pareto k-hat, effective sample size and evidence estimate -- which runs a bad pooled k-hat comes from --
@@ -883,18 +890,21 @@ def _check_proposal(proposal, importance, engs):
     return proposal
 
 
-def _mixture_pool_psis(eng, npr, points, seeds, want_weights=True):
+def _mixture_pool_psis(eng, npr, points, seeds, want_weights=True, moved=None):
     """pool of the runs' fits `points` drawn with `seeds`, its mixture-proposal log ratios and their PSIS, all on the device of `eng`
-    (the weights stay there for the index selection and the pool passes); returns the PSIS result"""
+    (the weights stay there for the index selection and the pool passes); returns the PSIS result.  moved: the (scale, shift) of a
+    moment-matched result, applied to the pool once the ratios of the pool as built exist."""
     eng.pool_build(npr, points, seeds)
     eng.pool_mixture_ratios(want=False)
+    if moved is not None:
+        eng.pool_transform(moved[0], moved[1], want=False)
     ptr, S = eng.pool_mixture_ratios_dev()
     return eng.psis_dev(ptr, S, want_weights=want_weights)
 
 
-def _mixture_pooled_stage(eng, npr, points, seeds, ndraws, seed, replace=True):
+def _mixture_pooled_stage(eng, npr, points, seeds, ndraws, seed, replace=True, moved=None):
     """the pooled stage under the mixture proposal: (PSIS result, indices, draws)"""
-    res = _mixture_pool_psis(eng, npr, points, seeds)
+    res = _mixture_pool_psis(eng, npr, points, seeds, moved=moved)
     idx = eng.resample_indices(len(points) * npr, ndraws, importance=True, replace=replace, seed=seed)
     return res, idx, eng.pool_gather(idx)
 
@@ -1004,24 +1014,31 @@ def _combine_moments(blocks):
     return total
 
 
-def _rebuild_pool(result, importance):
+def _rebuild_pool(result, importance, mixture_ratios=False):
     """The preamble of the pooled summaries: every engine of `result` rebuilds its block of the pool from the runs' stored
     (fit, draw_seed, ndraws_per_run) and, with importance weighting, the pooled PSIS is re-run so that every engine holds the weights
     of the global pool.  Returns (owners, weighted, pareto_shape); owners: one (engine, col_offset) per engine in global run order,
-    col_offset the global pool column of the engine's first draw."""
+    col_offset the global pool column of the engine's first draw.  mixture_ratios: every engine also forms the mixture-proposal
+    ratios of its pool (Engine.pool_mixture_ratios) -- on the pool AS BUILT, before a moment-matched result's map is applied, which
+    then carries them along (a moved pool's mixture ratios follow from those of the pool as built and are not formed afresh)."""
     engs = result.engines or [result.engine]
     runs = result.pathfinder_results
     for r in runs:
         r.fit_distribution._live()                                  # the fits must still be the engine's current ones
     npr = runs[0].ndraws_per_run
     seeds = [r.draw_seed for r in runs]
+    moved = getattr(result, "pool_transform", None)                 # a moment-matched result: its map follows every rebuild
     if getattr(result, "proposal", "component") == "mixture" and bool(importance) and result.psis_result is not None:
         _check_proposal("mixture", True, engs)                      # the weights of the mixture route, as multipathfinder formed them
-        res = _mixture_pool_psis(engs[0], npr, [r.fit_distribution.point for r in runs], seeds, want_weights=False)
+        res = _mixture_pool_psis(engs[0], npr, [r.fit_distribution.point for r in runs], seeds, want_weights=False, moved=moved)
         return [(engs[0], 0)], True, res["pareto_shape"]
     owners = []
     for eng, (k0, k1) in zip(engs, _blocks(len(runs), len(engs))):
         eng.pool_build(npr, [r.fit_distribution.point for r in runs[k0:k1]], seeds[k0:k1])
+        if mixture_ratios:
+            eng.pool_mixture_ratios(want=False)
+        if moved is not None:
+            eng.pool_transform(moved[0], moved[1], want=False)
         owners.append((eng, k0 * npr))
     weighted = bool(importance) and result.psis_result is not None
     pareto_shape = float("nan")
@@ -1107,9 +1124,7 @@ def importance_run_diagnostics(result, *, source="component"):
         raise ValueError(f"source must be one of {PROPOSALS}, got {source!r}")
     if source == "mixture":
         _check_proposal("mixture", True, result.engines or [result.engine])
-    owners, _, _ = _rebuild_pool(result, False)
-    if source == "mixture":
-        owners[0][0].pool_mixture_ratios(want=False)
+    owners, _, _ = _rebuild_pool(result, False, mixture_ratios=(source == "mixture"))
     parts = [eng.pool_psis_runs(source) for eng, _ in owners]
     runs = result.pathfinder_results
     elbo = [r.elbo_estimates[r.fit_iteration - 1].value if r.fit_iteration >= 1 else float("nan") for r in runs]
@@ -1452,15 +1467,19 @@ def resample(result, ndraws, *, rng=None, replace=True, importance=True, ndraws_
         npr = runs[0].ndraws_per_run                                # pathfinder_results[k].draws, whatever an earlier
         seeds = [r.draw_seed for r in runs]                         # resample() drew fresh
     S = K * npr
+    # a moment-matched result's map belongs to its stored candidates: fresh candidates are taken as drawn
+    moved = getattr(result, "pool_transform", None) if ndraws_per_run is None else None
     if proposal == "mixture":
         engs[0].set_callback_threads(ntasks)
         res, idx, draws = _mixture_pooled_stage(engs[0], npr, [r.fit_distribution.point for r in runs], seeds, ndraws,
-                                                int(rng.rand_u64(1)[0]), replace=replace)
+                                                int(rng.rand_u64(1)[0]), replace=replace, moved=moved)
         ids = idx // npr + 1
     else:
         for eng, (k0, k1) in zip(engs, blocks):
             eng.set_callback_threads(ntasks)                        # src/resample.jl:85-92: logp over `ntasks` tasks
             eng.pool_build(npr, [r.fit_distribution.point for r in runs[k0:k1]], seeds[k0:k1])
+            if moved is not None:
+                eng.pool_transform(moved[0], moved[1], want=False)
         # PSIS of the (re)built pool: for stored draws this reproduces result.psis_result bit for bit
         res, draws, ids = _resample(rng, _comm_for(engs), importance, npr, ndraws, replace=replace)
     psis_result = None
@@ -1475,4 +1494,123 @@ def resample(result, ndraws, *, rng=None, replace=True, importance=True, ndraws_
             w, lw = engs[0].psis_weights(S)
             psis_result = PSISResult(w, lw, res["pareto_shape"], res["tail_length"])
     return MultiPathfinderResult(result.input, result.rng, result.logp, result.fit_distribution, draws, ids,
-                                 runs, psis_result, engs[0], npr, engs, proposal)
+                                 runs, psis_result, engs[0], npr, engs, proposal, moved,
+                                 getattr(result, "moment_match_history", None) if moved is not None else None)
+
+
+# ---- importance-weighted moment matching of the pool (Paananen, Piironen, Buerkner, Vehtari 2021; loo::moment_match) --------------
+MOMENT_MATCH_STEPS = ("T1", "T2")
+
+
+def moment_match_step(step, sums0, sums, scale, shift):
+    """The arithmetic of one moment-matching step, a pure function of moment sums of the CURRENT pool x (already moved by the
+    cumulative map x = scale * x0 + shift).  sums0: the unweighted sums, sums: the importance-weighted ones, each
+    (W, s1, c1, c2) = (sum w, sum w x, sum w (x - s1 / W), sum w (x - s1 / W)^2) as two Engine.pool_moments passes (about the origin,
+    then about the mean) and _combine_moments give them.  step "T1" matches the mean: a = 1, b = m - m0; "T2" the mean and the
+    marginal variance: a = sqrt(v / v0), b = m - a m0, with m = s1 / W and v = c2 / W - (c1 / W)^2 (m0, v0 from sums0).
+    Returns (a, b, new_scale, new_shift): the candidate step x -> a x + b and its composition with the cumulative map,
+    new_scale = a scale, new_shift = a shift + b."""
+    if step not in MOMENT_MATCH_STEPS:
+        raise ValueError(f"step must be one of {MOMENT_MATCH_STEPS}, got {step!r}")
+    W0, s1_0, c1_0, c2_0 = sums0
+    W, s1, c1, c2 = sums
+    m0, m = s1_0 / W0, s1 / W
+    if step == "T1":
+        a = np.ones_like(m)
+    else:
+        v0 = c2_0 / W0 - (c1_0 / W0) ** 2
+        v = c2 / W - (c1 / W) ** 2
+        with np.errstate(divide="ignore", invalid="ignore"):
+            a = np.sqrt(v / v0)
+    b = m - a * m0
+    return a, b, a * scale, a * shift + b
+
+
+def _moment_sums(owners, weighted):
+    """(W, s1, c1, c2) of the pool the owners hold now: the two moment passes of importance_summary"""
+    _, _, W, mean = _first_moments(owners, weighted)
+    _, c1_b, c2_b, _ = _moment_pass(owners, weighted, mean)
+    return W, mean * W, _combine_moments(c1_b), _combine_moments(c2_b)
+
+
+def _map_ok(scale, shift):
+    return bool(np.all(np.isfinite(scale)) and np.all(scale > 0.0) and np.all(np.isfinite(shift)))
+
+
+def moment_match(result, *, k_threshold=0.7, max_iters=30, ndraws=None, rng=None, replace=True):
+    """Importance-weighted moment matching of a multipathfinder result (Paananen, Piironen, Buerkner, Vehtari 2021; `moment_match` of
+    the loo package) with the pool resident on the device.  All S pooled candidates are moved by ONE affine map x' = scale x0 + shift
+    so that their plain moments meet their importance-weighted ones; the target is re-evaluated at the moved candidates in the same
+    pass (Engine.pool_transform) and every run's proposal density changes by the constant -sum log scale, for the per-run proposals
+    and for proposal="mixture" alike.  Per iteration, from the rebuilt pool and its pooled PSIS: stop when k-hat <= k_threshold;
+    otherwise take the unweighted and the weighted mean and variance of the current pool (Engine.pool_moments of every engine, added
+    across runs by _combine_moments in run order), try T1 (mean), then T2 (mean and marginal variance), each composed with the
+    accepted cumulative map and applied to the pool AS BUILT; a trial is kept iff its pooled k-hat is finite and strictly smaller,
+    otherwise reverted (a buffer swap); stop when neither is kept or after max_iters iterations.
+    Returns a new MultiPathfinderResult: pool_transform = (scale, shift), moment_match_history = [(step, k-hat, accepted), ...]
+    starting with ("start", k-hat of the pool as built, True), the PSIS result of the matched pool and `ndraws` (default: as many as
+    the result holds) draws resampled from it.  summary(), quantiles(), covariance(), correlation(), lowrank_covariance(),
+    run_diagnostics() and resample() of the returned result act on the matched pool.  The matching always starts from the pool as
+    built, whatever map `result` carries, and is bit-identical for any number of engines.  Needs importance weights."""
+    if result.psis_result is None:
+        raise ValueError("moment_match needs a result with importance weights (importance=True)")
+    engs = result.engines or [result.engine]
+    runs = result.pathfinder_results
+    npr = runs[0].ndraws_per_run
+    S = len(runs) * npr
+    mixture = getattr(result, "proposal", "component") == "mixture"
+    base = dataclasses.replace(result, pool_transform=None, moment_match_history=None)
+    owners, _, k = _rebuild_pool(base, True)                        # the pool as built and its pooled PSIS; the weights are on every engine
+    d = owners[0][0].d
+
+    def pooled_k():
+        if mixture:
+            ptr, n = engs[0].pool_mixture_ratios_dev()
+            return engs[0].psis_dev(ptr, n, want_weights=False)["pareto_shape"]
+        return _comm_for(engs).pool_psis()["pareto_shape"]
+
+    scale, shift = np.ones(d), np.zeros(d)
+    history = [("start", float(k), True)]
+    weights_current = True                                          # the engines' PSIS weights are those of the current pool
+    for _ in range(int(max_iters)):
+        if not k > k_threshold:                                     # (a NaN k-hat stops too)
+            break
+        if not weights_current:
+            pooled_k()
+            weights_current = True
+        sums0, sums = _moment_sums(owners, False), _moment_sums(owners, True)
+        accepted = False
+        for step in MOMENT_MATCH_STEPS:
+            _, _, sc, sh = moment_match_step(step, sums0, sums, scale, shift)
+            if not _map_ok(sc, sh):
+                history.append((step, float("nan"), False))
+                continue
+            for eng, _ in owners:
+                eng.pool_transform(sc, sh, want=False)
+            k_new = pooled_k()
+            if np.isfinite(k_new) and k_new < k:
+                scale, shift, k, accepted = sc, sh, k_new, True
+                history.append((step, float(k_new), True))
+                break
+            for eng, _ in owners:
+                eng.pool_transform_revert()
+            weights_current = False
+            history.append((step, float(k_new), False))
+        if not accepted:
+            break
+    moved = None if len(history) == 1 or not any(h[2] for h in history[1:]) else (scale, shift)
+    rng = rng if rng is not None else result.rng
+    ndraws = int(ndraws) if ndraws is not None else int(np.asarray(result.draws).shape[1])
+    seed = int(rng.rand_u64(1)[0])
+    if mixture:
+        ptr, n = engs[0].pool_mixture_ratios_dev()
+        res = engs[0].psis_dev(ptr, n)
+        idx = engs[0].resample_indices(S, ndraws, importance=True, replace=replace, seed=seed)
+        draws = engs[0].pool_gather(idx)
+        w, lw = res["weights"], res["log_weights"]
+    else:
+        res, idx, draws = _comm_for(engs).psis_resample(ndraws, importance=True, replace=replace, seed=seed)
+        w, lw = engs[0].psis_weights(S)
+    psis_result = PSISResult(w, lw, res["pareto_shape"], res["tail_length"])
+    return MultiPathfinderResult(result.input, result.rng, result.logp, result.fit_distribution, draws, idx // npr + 1, runs, psis_result,
+                                 engs[0], npr, engs, getattr(result, "proposal", "component"), moved, history)

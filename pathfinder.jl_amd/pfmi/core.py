@@ -608,6 +608,27 @@ class Engine:
         check(self.L.pfmi_pool_mixture_ratios_dev(self.ctx, C.byref(p), C.byref(n)))
         return p.value, n.value
 
+    def pool_transform(self, scale=None, shift=None, want=True):
+        """One affine map for every column of this engine's pool, and the target at the moved columns, in one pass on the device
+        (include/pfmi.h pfmi_pool_transform): every column becomes fma(scale, x0, shift) with x0 the pool AS BUILT -- the map is
+        cumulative, never applied on top of an earlier call -- and logp, logq (minus sum log scale), the log ratios and, when
+        pool_mixture_ratios ran on the pool as built, the mixture ratios are those of the moved pool.  Every later pool pass, the
+        gather and the communicator see the moved pool.  scale None: ones; shift None: zeros; both None: the pool as built is put
+        back.  Returns (logp, log_ratios), K N_r doubles each, or None with want=False.  The engine's PSIS weights stay as they are."""
+        d = self.d
+        scale = _f64_of_shape("pool_transform", "scale", scale, (d,))
+        shift = _f64_of_shape("pool_transform", "shift", shift, (d,))
+        S = self.K * getattr(self, "N_r", 0)                # (no pool yet: the library says so)
+        lp = np.empty(S) if want and S else None
+        lr = np.empty(S) if want and S else None
+        check(self.L.pfmi_pool_transform(self.ctx, _d(scale), _d(shift), _d(lp), _d(lr)))
+        self._raise_target_error()
+        return (lp, lr) if want else None
+
+    def pool_transform_revert(self):
+        """the state from before the last pool_transform back, without a pass (a rejected trial undone); nothing to undo: PfmiError"""
+        check(self.L.pfmi_pool_transform_revert(self.ctx))
+
     def pool_psis_runs(self, source="component", want_weights=False):
         """PSIS of every run of this engine's pool on its own N_r log ratios, all runs in one launch (include/pfmi.h
         pfmi_pool_psis_runs): a dict of pareto_shape, tail_length, lse (logsumexp of the run's smoothed log ratios) and sumsq (sum of
