@@ -48,6 +48,9 @@
 #ifndef QF_PSEUDO_FLIGHT
 #define QF_PSEUDO_FLIGHT 1             // 0: the c/s column of the pseudo group loads its inputs row by row, behind guards (A/B builds)
 #endif
+#ifndef QF_CS_LDS
+#define QF_CS_LDS 1                    // 0: the c/s column is never staged in LDS, every block of the pseudo group loads and divides (A/B builds)
+#endif
 #ifndef QF_NG2_MAXKC
 #define QF_NG2_MAXKC 20                // two groups per wave up to this KC (round 2: 12; KC = 16, 20 take the register-lean block body)
 #endif
@@ -111,14 +114,23 @@ __device__ __forceinline__ int qf_vh_pos(int lrow, int col) {
 
 // the kernel's argument block (same members, same order: the kernarg segment is laid out like this struct).  The hand-over pointers are
 // read from the segment where they are needed -- as named parameters they would sit in SGPRs across the whole block loop, and the scan
-// has none to spare (measured: +0.1 ms per config-3 scan from the extra spills)
-struct QfKernArgs { ElboArgs A; int ch_blocks, nchunks, groups_per_wg, ngroups, n_whole, n_tail, ndep; double *cshare; unsigned *cflag; unsigned epoch; };
+// has none to spare (measured: +0.1 ms per config-3 scan from the extra spills).  cs_off: offset (in doubles from `lds`) of the staged c/s
+// column, 16 * ch_blocks doubles behind the rest of the allocation; 0 = the launch has no room for it (launch_qf_ng)
+struct QfKernArgs { ElboArgs A; int ch_blocks, nchunks, groups_per_wg, ngroups, n_whole, n_tail, ndep; double *cshare; unsigned *cflag; unsigned epoch; int cs_off; };
+// which instantiations stage the c/s column: those with a pseudo group, except the register-lean body (two groups at KC >= 16), where it
+// costs 8 B of scratch (<20, 2, 0, 2>: 64 -> 72 B, over the pin of tests/test_kernel_resources.py)
+__host__ __device__ constexpr bool qf_cs_lds(int KC, int TGT, int NG) { return QF_CS_LDS != 0 && TGT != 0 && !(NG == 2 && KC >= 16); }
+__device__ __forceinline__ int qf_arg_cs_off() {
+    const char *ka = (const char *)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ka));                                   // read here, not carried from the kernel's entry
+    return *reinterpret_cast<const int *>(ka + offsetof(QfKernArgs, cs_off));
+}
 #ifndef QF_SHARE_SPINS
 #define QF_SHARE_SPINS 2000000          // x ~1 us: how long a dependent piece waits for its fit's constants before it gives up
 #endif
 template <int KC, int TGT, int RPAD, int NG>
 __global__ __launch_bounds__(QF_THREADS) void pf_elbo_qf_kernel(ElboArgs A, int ch_blocks, int nchunks, int groups_per_wg, int ngroups, int n_whole,
-                                                                  int n_tail, int ndep, double *, unsigned *, unsigned) {
+                                                                  int n_tail, int ndep, double *, unsigned *, unsigned, int) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
 #if QF_PROF
     const long long qf_t0 = wall_clock64();
@@ -213,6 +225,10 @@ __global__ __launch_bounds__(QF_THREADS) void pf_elbo_qf_kernel(ElboArgs A, int 
                 }
             }
         }
+        // the c/s column of the pseudo group (column KC, see pseudo_cols), when the launch has room for it: formed here once per fit from the
+        // row inputs that are in registers anyway, instead of twelve loads and four divisions per block in the wave that publishes
+        int cs_o = 0;
+        if constexpr (qf_cs_lds(KC, TGT, NG)) { if (npg > 0) cs_o = qf_arg_cs_off(); }
         for (int l0 = tid; l0 < ch_blocks * 16; l0 += QF_THREADS * 2) {
             double a[2], cc[2], s[2];
 #pragma unroll
@@ -228,6 +244,7 @@ __global__ __launch_bounds__(QF_THREADS) void pf_elbo_qf_kernel(ElboArgs A, int 
                     const bool in = row < d;
                     double *o = rs + (lrow >> 4) * 48 + (lrow & 15);
                     o[0] = in ? a[u] * s[u] * s[u] : 0.0; o[16] = in ? 2.0 * a[u] * cc[u] * s[u] : 0.0; o[32] = in ? s[u] : 0.0;
+                    if constexpr (qf_cs_lds(KC, TGT, NG)) { if (cs_o) lds[cs_o + lrow] = in ? cc[u] / s[u] : 0.0; }
                 }
             }
         }
@@ -490,9 +507,20 @@ __global__ __launch_bounds__(QF_THREADS) void pf_elbo_qf_kernel(ElboArgs A, int 
                     }
                 };
                 // pseudo group: column j of this lane is Vh[:, j] (j < KC) or c/s (j == KC); no RNG, no head transform
-                auto pseudo_cols = [&](const int g, const int blk, const int bl, double (&z)[4]) {
+                // (cs_o != 0: the c/s column was staged by stage_direct -- the same operands, the same division -- and is read back: no global
+                //  load and no division here, for every target)
+                auto pseudo_cols = [&](const int g, const int blk, const int bl, const int cs_o, double (&z)[4]) {
                     const int j = 16 * sl[g] + c;
-                    if constexpr (QF_PSEUDO_FLIGHT != 0 && TGT == 1) {
+                    if (qf_cs_lds(KC, TGT, NG) && cs_o != 0) {
+                        const double *cs = lds + cs_o + bl * 16 + 4 * q;
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            double v = 0.0;
+                            if (j < KC) v = vs[qf_vh_pos<KC>(bl * 16 + 4 * q + r, j)];
+                            else if (j == KC) v = cs[r];                                     // (rows >= d were staged as 0)
+                            z[r] = v;
+                        }
+                    } else if constexpr (QF_PSEUDO_FLIGHT != 0 && TGT == 1) {
                         // Gaussian targets: the inputs of the c/s column's four rows in one flight, from clamped addresses, then the
                         // subtractions and divisions.  As guarded loads they were one round trip per row (the loads, s_waitcnt vmcnt(0), the
                         // division), each of them waiting for the block's Wd loads as well, in the wave every other wave of the workgroup
@@ -529,7 +557,11 @@ __global__ __launch_bounds__(QF_THREADS) void pf_elbo_qf_kernel(ElboArgs A, int 
                         }
                     }
                 };
-                if (any_pseudo) {                            // first batch only: mixed pseudo / real wave, no need to be fast
+                if (any_pseudo) {
+                    // first batch only: the mixed pseudo / real wave.  Every other wave of the workgroup waits for it at the publish barrier
+                    // (and a tail fit's dependents for their publisher), so its latencies are nobody's to hide but its own.
+                    int cs_o = 0;
+                    if constexpr (qf_cs_lds(KC, TGT, NG)) cs_o = qf_arg_cs_off();
                     for (int bl = 0; bl < nb; ++bl) {
                         Ops oa;
                         load_ops(bl, oa);
@@ -537,7 +569,7 @@ __global__ __launch_bounds__(QF_THREADS) void pf_elbo_qf_kernel(ElboArgs A, int 
                         for (int g = 0; g < NG; ++g) {
                             if (!active[g]) continue;
                             double z[4];
-                            if (pseudo[g]) { pseudo_cols(g, blk0 + bl, bl, z); contract(g, z, oa, false); }
+                            if (pseudo[g]) { pseudo_cols(g, blk0 + bl, bl, cs_o, z); contract(g, z, oa, false); }
                             else { normals(g, blk0 + bl, z); contract(g, z, oa, true); }
                         }
                     }
@@ -880,7 +912,16 @@ static int32_t launch_qf_ng(pfmi_ctx *c, const ElboArgs &a, int64_t nfits) {
     int ch_blocks = nblk, nchunks = 1;
     constexpr int QF_CHB = qf_chb<KC>::v;
     if (qf_lds_bytes(nblk, 1, KC, RPAD, NG) > 156 * 1024) { ch_blocks = QF_CHB; nchunks = (nblk + QF_CHB - 1) / QF_CHB; }
-    const size_t lds_bytes = qf_lds_bytes(ch_blocks, nchunks, KC, RPAD, NG);
+    size_t lds_bytes = qf_lds_bytes(ch_blocks, nchunks, KC, RPAD, NG);
+    // the staged c/s column of the pseudo group (QF_CS_LDS): 16 doubles per block behind everything else, for a resident block, when the
+    // request with it stays within the limit checked below.  The resident / streamed decision above does not look at it.
+    int cs_off = 0;
+    const char *no_cs = pf_debug_get("PFMI_QF_NO_CS_LDS");           // test hook: the column's loads and divisions in every block, as without room
+    if (qf_cs_lds(KC, TGT, NG) && nchunks == 1 && !(no_cs && no_cs[0] == '1') &&
+        lds_bytes + sizeof(double) * 16 * (size_t)ch_blocks <= 160 * 1024) {
+        cs_off = (int)(lds_bytes / sizeof(double));
+        lds_bytes += sizeof(double) * 16 * (size_t)ch_blocks;
+    }
     PF_CHECK(lds_bytes <= 160 * 1024, PFMI_ERR_UNSUPPORTED, "qf kernel LDS %zu too large", lds_bytes);
     auto kern = pf_elbo_qf_kernel<KC, TGT, RPAD, NG>;
     PF_TRY(pf_raise_lds_limit(c, reinterpret_cast<const void *>(kern), 160 * 1024));
@@ -902,7 +943,7 @@ static int32_t launch_qf_ng(pfmi_ctx *c, const ElboArgs &a, int64_t nfits) {
             b.points = a.points + s0; b.seeds = a.seeds + s0;
             if (!a.by_point) { b.logp += s0 * a.log_stride; b.logq += s0 * a.log_stride; }
             hipLaunchKernelGGL(kern, dim3((unsigned)gx_, (unsigned)ns), dim3(QF_THREADS), lds_bytes, c->stream, b, ch_blocks, nchunks, gpw_,
-                               ngroups, 0, 0, 0, (double *)nullptr, (unsigned *)nullptr, 0u);
+                               ngroups, 0, 0, 0, (double *)nullptr, (unsigned *)nullptr, 0u, cs_off);
         }
     };
     // Workgroups of one launch all take the same time, so the fits beyond the last full round of CUs (nfits mod #CU) would keep a
@@ -943,7 +984,7 @@ static int32_t launch_qf_ng(pfmi_ctx *c, const ElboArgs &a, int64_t nfits) {
             // flags live at the END of the buffer so that a larger tail of a later launch never reads constants as flags
             unsigned *cflag = reinterpret_cast<unsigned *>(share.as<char>() + share.cap) - (tail + 1);
             hipLaunchKernelGGL(kern, dim3(1, (unsigned)((nfits - tail) + tail * (1 + ndep))), dim3(QF_THREADS), lds_bytes, c->stream, a, ch_blocks,
-                               nchunks, gpw, ngroups, (int)(nfits - tail), (int)tail, ndep, share.as<double>(), cflag, ++epoch);
+                               nchunks, gpw, ngroups, (int)(nfits - tail), (int)tail, ndep, share.as<double>(), cflag, ++epoch, cs_off);
             qf_note_plan(c, KC, TGT, RPAD, NG, nchunks > 1, "tail-share");
             return PFMI_OK;
         }

@@ -46,7 +46,7 @@ def compile_asm(src=SRC, extra=()):
 
 
 def mangled(kc, tgt, rpad, ng):
-    return f"_Z17pf_elbo_qf_kernelILi{kc}ELi{tgt}ELi{rpad}ELi{ng}EEv8ElboArgsiiiiiiiPdPjj"
+    return f"_Z17pf_elbo_qf_kernelILi{kc}ELi{tgt}ELi{rpad}ELi{ng}EEv8ElboArgsiiiiiiiPdPjji"
 
 
 def kernel_lines(asm, sym):
