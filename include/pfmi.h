@@ -49,7 +49,7 @@ typedef struct pfmi_ctx pfmi_ctx;
 #define PFMI_FIT_OK 0
 #define PFMI_FIT_A_NOT_PD 1
 #define PFMI_FIT_C_NOT_PD 2
-#define PFMI_FIT_NONFINITE 3
+#define PFMI_FIT_NONFINITE 3    /* reserved; not produced: no kernel sets it (a non-finite pair is rejected by the history walk instead) */
 #define PFMI_FIT_ABSENT 4       /* streaming layout (pfmi_stream_enqueue): the path ended before this slot -- there is no such trace point */
 
 /* target kinds: the hot path only ever sees logp(x) = -f(x) (src/singlepath.jl:186, src/multipath.jl:159) */
@@ -120,7 +120,15 @@ int32_t pfmi_debug_set(const char *key, const char *value);
  * "mf:<KC>,<NBW>,<TGT>,<RPAD>:<x|nox>:<whole|split>": the two-pass MFMA kernel -- KC (4 .. 16), NBW 16-row blocks per wave
  * (1, 2, 4, 8), TGT / RPAD as above, draws written ("x") or only their log densities ("nox"), and the cut as for the writer.
  * "lane:<KPAD>,<TGT>,<RPAD>:<u|rng>:<x|nox>": the lane-per-draw kernel -- column padding KPAD (4 .. 64), normals supplied by
- * the caller ("u") or made by the in-kernel generator ("rng"), draws written or not. */
+ * the caller ("u") or made by the in-kernel generator ("rng"), draws written or not.
+ * The fit kernels likewise, one count per kernel launch (the stage name "fit" keeps its meaning):
+ * "fit:reg:<KPAD>,<RPT>": the register-resident kernel (d <= 1024, history_length <= 8) -- column padding KPAD (4 .. 16), RPT
+ * rows per thread (1: d <= 256, 2: d <= 512, 4: d <= 1024).
+ * "fit:gen:<KPAD>": the general column-by-column kernel -- KPAD (4 .. 64): history_length >= 9 at d <= 1024, every shape the
+ * large-d kernels decline, and PFMI_FIT_KERNEL=mem.
+ * "fit:tsqr:<KPAD>": the TSQR kernel with Householder reconstruction (d > 1024) -- KPAD (8 .. 32).
+ * "fit:panel:<KPAD>,<RPT>,<cols>": the left-looking panel kernel (d > 1024) -- KPAD (8 .. 32), RPT the bucket of rows per thread
+ * (5, 10, 20, 32), cols the panel width (4; 2 in the last bucket). */
 int32_t pfmi_timer_start(pfmi_ctx *ctx);
 int32_t pfmi_timer_stop(pfmi_ctx *ctx, double *milliseconds);
 int32_t pfmi_profile(pfmi_ctx *ctx, int32_t enable);

@@ -1224,6 +1224,12 @@ int32_t pf_launch_history(pfmi_ctx *c, double eps, const HistSeg *seg) {
     return PFMI_OK;
 }
 
+static void note_fit_reg(pfmi_ctx *c, int kpad, int rpt) {
+    char nm[32];
+    snprintf(nm, sizeof nm, "fit:reg:%d,%d", kpad, rpt);
+    pf_note_fit_plan(c, nm);
+}
+
 template <int KPAD>
 static void launch_fit_t(pfmi_ctx *c, const FitArgs &a) {
     const char *force = pf_debug_get("PFMI_FIT_KERNEL");            // "mem" forces the general (memory-resident) kernel
@@ -1232,11 +1238,14 @@ static void launch_fit_t(pfmi_ctx *c, const FitArgs &a) {
     if constexpr (KPAD <= 16) {
         // register-resident kernel: 256 threads x RPT rows (measured faster than 512 x 2: the kernel is bound by
         // block-reduction / serial O(m^3) latency, and 8-wave barriers cost more than the extra occupancy buys)
-        if (allow_reg && a.d <= 256) { hipLaunchKernelGGL((pf_fit_reg_kernel<KPAD, 1, 256>), grid, dim3(256), 0, c->stream, a); return; }
-        if (allow_reg && a.d <= 512) { hipLaunchKernelGGL((pf_fit_reg_kernel<KPAD, 2, 256>), grid, dim3(256), 0, c->stream, a); return; }
-        if (allow_reg && a.d <= 1024) { hipLaunchKernelGGL((pf_fit_reg_kernel<KPAD, 4, 256>), grid, dim3(256), 0, c->stream, a); return; }
+        if (allow_reg && a.d <= 256) { hipLaunchKernelGGL((pf_fit_reg_kernel<KPAD, 1, 256>), grid, dim3(256), 0, c->stream, a); note_fit_reg(c, KPAD, 1); return; }
+        if (allow_reg && a.d <= 512) { hipLaunchKernelGGL((pf_fit_reg_kernel<KPAD, 2, 256>), grid, dim3(256), 0, c->stream, a); note_fit_reg(c, KPAD, 2); return; }
+        if (allow_reg && a.d <= 1024) { hipLaunchKernelGGL((pf_fit_reg_kernel<KPAD, 4, 256>), grid, dim3(256), 0, c->stream, a); note_fit_reg(c, KPAD, 4); return; }
     }
     hipLaunchKernelGGL(pf_fit_kernel<KPAD>, grid, block, 0, c->stream, a);
+    char nm[32];
+    snprintf(nm, sizeof nm, "fit:gen:%d", KPAD);
+    pf_note_fit_plan(c, nm);
 }
 
 int32_t pf_launch_fit_panel(pfmi_ctx *c, const FitArgs &a, bool *handled);   // fit_panel_kernel.hip

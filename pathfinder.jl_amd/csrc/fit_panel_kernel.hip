@@ -617,6 +617,9 @@ static int32_t launch_panel_t(pfmi_ctx *c, const FitArgs &a, int ncu) {
     int *counter = reinterpret_cast<int *>(c->fit_scratch.as<char>() + scr_bytes);
     PF_HIP(hipMemsetAsync(counter, 0, 8 * sizeof(int), c->stream));               // one work counter per XCD
     hipLaunchKernelGGL(kern, dim3(grid), dim3(FP_NT), lds, c->stream, a, KPAD, c->fit_scratch.as<double>(), counter);
+    char nm[40];
+    snprintf(nm, sizeof nm, "fit:panel:%d,%d,%d", KPAD, RPT, PW);
+    pf_note_fit_plan(c, nm);
     return PFMI_OK;
 }
 

@@ -851,6 +851,9 @@ static int32_t launch_tsqr_t(pfmi_ctx *c, const FitArgs &a, int ncu, bool *handl
     int *counter = reinterpret_cast<int *>(c->fit_scratch.as<char>() + scr_bytes);
     PF_HIP(hipMemsetAsync(counter, 0, 8 * sizeof(int), c->stream));               // one work counter per XCD
     hipLaunchKernelGGL(kern, dim3(grid), dim3(TS_NT), lds, c->stream, a, DP, nch, c->fit_scratch.as<double>(), counter);
+    char nm[32];
+    snprintf(nm, sizeof nm, "fit:tsqr:%d", MC);
+    pf_note_fit_plan(c, nm);
     return PFMI_OK;
 }
 
