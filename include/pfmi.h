@@ -330,6 +330,53 @@ int32_t pfmi_woodbury_apply(pfmi_ctx *ctx, int64_t point, int32_t op, int64_t N,
 /* diag(W) = diag(A) + rowwise b' D b   (src/woodbury.jl:326-329); diag[d] */
 int32_t pfmi_woodbury_diag(pfmi_ctx *ctx, int64_t point, double *diag);
 
+/* ---- static HMC with a fitted metric, for gradient closures ------------------------------------------------------------ */
+/* "Use Pathfinder's metric estimate for sampling" (docs/src/examples/initializing-hmc.md, third way;
+ * AdvancedHMC.RankUpdateEuclideanMetric(result.fit_distribution.Sigma), ext/PathfinderAdvancedHMCExt.jl:17-23), kept on the device: K
+ * independent chains of static HMC -- nleapfrog leapfrog steps per transition, Metropolis correction, full momentum refresh; no NUTS.
+ * Chain k uses the Woodbury factor of fit points[k] as its metric and the ctx's DEVICE_CALLBACK target with its gradient closure
+ * (pfmi_set_target_gradient); built-in targets, host closures and device closures without a gradient: PFMI_ERR_UNSUPPORTED.
+ *
+ * The transition.  Sigma = L R, R = L' (L = PFMI_OP_UNWHITEN, R = PFMI_OP_RMUL); the momentum is carried whitened, v = R p ~ N(0, I).
+ * Per chain: the point x, lp = logp(x), wg = R grad logp(x), v, the trial point x~, the transition counter t.  Transition t with step size
+ * e, Lf = nleapfrog and the chain's seed s:
+ *   1. v <- the d standard normals of draw index t under seed s (the library's generator, stream 0);  H0 = -lp + |v|^2 / 2
+ *   2. v <- v + (e/2) wg;  x~ <- x + e L v
+ *   3. for i = 1 .. Lf: the closure gives (lp~, g~) at x~, w~ = R g~;  i < Lf: v <- v + e w~, x~ <- x~ + e L v;  i = Lf: v <- v + (e/2) w~
+ *   4. H1 = -lp~ + |v|^2 / 2,  a = min(1, exp(H0 - H1)).  A non-finite lp~, g~ or H1, or H1 - H0 > 1000: a = 0 and the transition is
+ *      divergent; the trial never enters the state (nothing non-finite is ever stored in x, lp, wg)
+ *   5. u = (rand_u64(s, t, stream 3) >> 11) 2^-53 (pfmi_host_rand_u64's generator);  accept iff u < a:  (x, lp, wg) <- (x~, lp~, w~)
+ *   6. row t records x, lp, a, H1 - H0 (DBL_MAX when it is not finite) and the divergent flag.
+ * The closure cannot be called from a kernel, so a run is 1 + T Lf ROUNDS (the first evaluates the start points): one call of the closure
+ * on all K trial points (d x K, with the ctx's stream as its `stream`), then one launch of the step kernel, one workgroup per chain.  The
+ * round count is known up front: _enqueue issues every round from the calling thread and returns without waiting.  A chain's output
+ * depends on its own inputs alone (not on K, not on the other chains).
+ * x0: d x K column-major start points; seeds, step_size: K values; points: K fit points (0-based, any path). */
+#define PFMI_HMC_CONTINUE 1      /* go on from the chains' resident states and counters; x0 ignored (may be NULL) */
+#define PFMI_HMC_RECORD_PATH 2   /* keep every round's X, closure output and v (tests / diagnostics) */
+/* PFMI_ERR_STATE: not fitted, or CONTINUE without K resident chains.  PFMI_ERR_UNSUPPORTED: no gradient closure.  PFMI_ERR_ARG: K < 1, a
+ * point outside [0, P), a step size that is not positive and finite, nleapfrog < 1, ntransitions < 1, a NULL required pointer.
+ * PFMI_ERR_NUMERIC: a point whose fit status is not PFMI_FIT_OK.  An error drains this ctx's stream before returning.  pfmi_set_target,
+ * pfmi_set_target_gradient, pfmi_set_traces, a new fit, pfmi_optimize_batch_enqueue and pfmi_stream_enqueue forget the chains.
+ * Stage names under pfmi_profile: "hmc" (the step kernel), "hmc_closure" (the closure's kernels); "hmc:<KPAD>:<res|stream>" counts the step
+ * launches of one plan -- column padding KPAD (4 .. 64), the chain's factor rows staged in LDS or streamed from HBM. */
+int32_t pfmi_hmc_enqueue(pfmi_ctx *ctx, int32_t K, const int64_t *points, const double *x0, const uint64_t *seeds, const double *step_size,
+                         int32_t nleapfrog, int64_t ntransitions, int32_t flags);
+/* waits for the rounds (AbstractMCMC's sample loop has returned).  PFMI_ERR_NUMERIC: a start point with a non-finite log density or
+ * gradient (the chains are forgotten).  PFMI_ERR_STATE without a run. */
+int32_t pfmi_hmc_wait(pfmi_ctx *ctx);
+/* The last call's T = ntransitions rows of every chain (the chain of AdvancedHMC.sample, docs/src/examples/initializing-hmc.md): draws
+ * (d, T, K) column-major like the pool; logp, accept_prob, energy_error, divergent [K][T].  Any may be NULL.  Waits. */
+int32_t pfmi_hmc_get(pfmi_ctx *ctx, double *draws, double *logp, double *accept_prob, double *energy_error, int32_t *divergent);
+/* device pointer to those draws (K T columns of d doubles; valid until the next pfmi_hmc_enqueue); *count = K T */
+int32_t pfmi_hmc_draws_dev(pfmi_ctx *ctx, void **dev_ptr, int64_t *count);
+/* PFMI_HMC_RECORD_PATH: rounds round0 .. round0 + nrounds - 1 of the last call -- X (d, K, nrounds) the closure's input of the round,
+ * closure_out (K + d K, nrounds) its output (logp [K], then grad (d, K)), v (d, K, nrounds) the whitened momenta after the round's launch.
+ * Any may be NULL.  No reference counterpart (AdvancedHMC keeps no leapfrog path). */
+int32_t pfmi_hmc_get_path(pfmi_ctx *ctx, int64_t round0, int64_t nrounds, double *X, double *closure_out, double *v);
+/* rounds and columns handed to the closure by the last pfmi_hmc_enqueue (pfmi_optimize_stats' counterpart) */
+int32_t pfmi_hmc_stats(pfmi_ctx *ctx, int64_t *rounds, int64_t *closure_columns);
+
 /* ---- pooling, _compute_psis_result, _resample ---------------------------------------------------- */
 /* draws_per_component = stack(draws) (src/multipath.jl:217): for path k take N_r draws of fit
  * `points[k]` with seed seeds[k] into the device-resident pool (d, N_r, K) and

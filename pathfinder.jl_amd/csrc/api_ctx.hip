@@ -376,6 +376,12 @@ int32_t pfmi_kernel_time(pfmi_ctx *c, const char *name, double *ms, int64_t *lau
         if (launches) *launches = (pl == c->draw_plans.end()) ? 0 : pl->second;
         return PFMI_OK;
     }
+    if (strncmp(name, "hmc:", 4) == 0) {                              // launches of one plan of the HMC step kernel, host-side count ("hmc" is the stage)
+        auto pl = c->hmc_plans.find(name);
+        if (ms) *ms = 0.0;
+        if (launches) *launches = (pl == c->hmc_plans.end()) ? 0 : pl->second;
+        return PFMI_OK;
+    }
     if (strncmp(name, "fit:", 4) == 0) {                              // launches of one fit-kernel plan, host-side count ("fit" itself stays the stage)
         auto pl = c->fit_plans.find(name);
         if (ms) *ms = 0.0;

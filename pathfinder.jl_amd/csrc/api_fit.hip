@@ -33,6 +33,7 @@ static int32_t fit_batch_impl(pfmi_ctx *c, int32_t J, double eps) {
     //  global memory, lane-per-draw kernel for every draw / scan; the tuned kernels stop at 32 columns)
     const int kpad = pf_kpad_for(J);
     PF_CHECK(kpad != 0, PFMI_ERR_UNSUPPORTED, "history_length %d > 32 unsupported", J);
+    hmc_forget(c);                                            // the chains' metrics are about to be rewritten
     c->J = J; c->kpad = kpad;
     PF_TRY(fit_reserve(c, (size_t)c->P, c->K, (size_t)c->d, J, kpad));
     if (c->virt) {                                            // streaming layout: every path's slots, the absent ones marked as such

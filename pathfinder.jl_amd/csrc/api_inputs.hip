@@ -98,6 +98,7 @@ int32_t pfmi_set_target(pfmi_ctx *c, const pfmi_target *t) {
     PF_CHECK(t != nullptr, PFMI_ERR_ARG, "null target");
     PF_CHECK(t->d > 0, PFMI_ERR_ARG, "target dimension must be positive");
     lbc_abandon(c);
+    hmc_forget(c);
     if (c->sr.active && c->sr.closure) stream_abandon(c);   // its pump would call the closures being replaced
     TargetDev &T = c->target;
     T.kind = t->kind; T.d = t->d; T.r = 0; T.rpad = 0; T.offset = 0.0; T.fn = nullptr; T.dev_fn = nullptr; T.user = nullptr;
@@ -149,6 +150,7 @@ int32_t pfmi_set_traces(pfmi_ctx *c, int32_t K, const int64_t *npoints, int32_t 
     PF_CTX_MUT(c);
     if (c->sr.active || c->stream_drain) stream_abandon(c);
     lbc_abandon(c);
+    hmc_forget(c);
     PF_CHECK(K > 0 && d > 0 && npoints && theta && grad, PFMI_ERR_ARG, "set_traces: bad arguments");
     for (int k = 0; k < K; ++k) PF_CHECK(npoints[k] >= 1, PFMI_ERR_ARG, "path %d has no points", k);
     results_reset(c);
@@ -165,6 +167,7 @@ int32_t pfmi_optimize_batch_enqueue(pfmi_ctx *c, int32_t K, const double *x0, in
     PF_CTX_MUT(c);
     if (c->sr.active || c->stream_drain) stream_abandon(c);
     lbc_abandon(c);
+    hmc_forget(c);
     const TargetDev &T = c->target;
     if (T.kind == PFMI_TARGET_DEVICE_CALLBACK && T.grad_fn) return lbc_enqueue(c, K, x0, J, maxiters, g_tol);
     c->lbc.rounds = 0; c->lbc.columns = 0;
@@ -231,6 +234,7 @@ int32_t pfmi_set_target_gradient(pfmi_ctx *c, pfmi_logp_dev_fn logp_grad_fn, voi
     PF_CHECK(c->target.kind == PFMI_TARGET_DEVICE_CALLBACK, PFMI_ERR_ARG, "set_target_gradient: the current target is not a DEVICE_CALLBACK target");
     PF_CHECK(logp_grad_fn != nullptr, PFMI_ERR_ARG, "set_target_gradient: null closure");
     lbc_abandon(c);
+    hmc_forget(c);
     if (c->sr.active && c->sr.closure) stream_abandon(c);
     c->target.grad_fn = logp_grad_fn; c->target.grad_user = user;
     return PFMI_OK;

@@ -43,6 +43,7 @@ inline void results_reset(pfmi_ctx *c) { c->fitted = false; c->elbo_done = false
 // ---- api_ctx.hip
 void stream_abandon(pfmi_ctx *c);          // drain and forget a streaming call that was never waited for
 void lbc_abandon(pfmi_ctx *c);             // the same for a packed closure optimisation
+void hmc_forget(pfmi_ctx *c);              // drain an HMC call that was never waited for and forget the chains (api_hmc.hip)
 int32_t ensure_pinned(pfmi_ctx *c, size_t x_bytes, size_t lp_bytes);
 
 // ---- api_inputs.hip

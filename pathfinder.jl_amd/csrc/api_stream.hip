@@ -65,6 +65,7 @@ static int32_t stream_enqueue_impl(pfmi_ctx *c, int32_t K, const double *x0, int
     // A packed closure optimisation still in flight writes the same staging trace: drained too.
     if (c->sr.active || c->stream_drain) stream_abandon(c);
     lbc_abandon(c);
+    hmc_forget(c);
     if (c->s_opt) PF_TRY(pf_stream_sync(c));      // the page-locked progress words and work lists are reused: the previous call's copies must have landed
     const int ncu = c->ncu > 0 ? c->ncu : 256;
     const int d = T.d;

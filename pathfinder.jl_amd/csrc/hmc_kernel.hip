@@ -1,0 +1,327 @@
+// hmc_kernel.hip -- static HMC for DEVICE_CALLBACK targets that carry a value-and-gradient closure (pfmi_set_target_gradient), with the
+// Woodbury factor of one fitted point as each chain's metric (the reference's "use Pathfinder's metric estimate for sampling",
+// docs/src/examples/initializing-hmc.md, ext/PathfinderAdvancedHMCExt.jl:17-23).
+//
+// The function is the user's, so -- as in lbfgs_closure_kernel.hip -- the run is cut into ROUNDS: one call of the closure on all K
+// columns of X, then one launch of pf_hmc_step_kernel (one workgroup per chain).  The round count is known up front (1 + T Lf: the
+// start points, then Lf evaluations per transition), so the host enqueues everything and never waits.
+//
+// The fit is Sigma = L R, R = L': L = PFMI_OP_UNWHITEN, R = PFMI_OP_RMUL (modes 0 and 2 of pf_woodbury_kernel), both in the compact-WY
+// form Q = I - Vh T Vh'.  The momentum is carried whitened, v = R p ~ N(0, I): the refresh needs no operator, the kinetic energy is
+// |v|^2 / 2, a kick is v += e R grad logp and a drift x += e L v.
+//
+// A launch of chain k
+//   * reads its column of the closure's output (logp, grad at the trial point it wrote in the previous launch),
+//   * forms wt = R grad:  z = s . grad, w = Vh'z (block reduction 1), tv = T'w, y = z - Vh tv, head <- V head,
+//   * finishes the pending kick with it (a full one inside a trajectory, a half one at its end),
+//   * at a trajectory's end sums |v|^2 (one more reduction), decides, records row t, draws the next momentum, gives it its first half
+//     kick and takes |v|^2 of the fresh normals along in the reduction of the drift,
+//   * applies L to v:  z = [V'v_head; v_tail], w = Vh'z (block reduction 2), tv = T w, and writes x~ + e s . (z - Vh tv) into column k of X.
+// The chain's rows of Vh are kept in LDS once per launch when they fit (RES): the first pass reads them from HBM and leaves each thread's
+// rows in its own LDS slots, so that the other three passes (the second half of R, both halves of L) do not read HBM again.
+//
+// Every control-flow scalar comes out of a fixed-order block reduction (pf_block_sum_mv / pf_block_sum1_pp: six butterfly steps inside a
+// wave, then the waves' partials in wave order, read back from LDS by every thread): all threads of a chain take the same branch, and a
+// chain's output depends on nothing but its own inputs.
+#include "pfmi_common.h"
+#include <float.h>
+
+#define HM_NT 256                      // threads per chain (4 waves)
+#define HM_NW (HM_NT / 64)
+#define HM_LDS_RES (150 * 1024)        // most dynamic LDS the staged factor rows may take (of 160 KB, beside the static buffers below)
+
+enum { HM_OPEN = -1, HM_START = 0 };   // HmChain::i: open a trajectory without reading the closure; the start point is being evaluated;
+                                       // 1 .. Lf: the leapfrog evaluation the next launch consumes
+
+struct HmChain {                       // per-chain scalar state (HBM); read by every thread, written back by thread 0
+    double lp, H0;
+    int64_t t;                         // transitions made so far = draw index of the next momentum
+    int32_t i, bad, dead, pad_;
+};
+
+struct HmArgs {
+    int d, K, nleap, record;
+    int64_t t0, t_end, T;              // this call records transitions t0 .. t_end - 1 as rows 0 .. T - 1
+    int64_t round;                     // index of this launch among the call's closure rounds (row of the recorded path)
+    const int32_t *pts;                // [K] fit point of each chain
+    const uint64_t *seeds;             // [K]
+    const double *eps;                 // [K]
+    const double *x0;                  // [K][d] (init kernel)
+    double *X;                         // closure input: d x K column-major
+    const double *out;                 // closure output: logp [K], then grad [K][d]
+    double *x, *wg, *wt, *v;           // [K][d]: state, R grad logp(x), R grad at the trial point (scratch), whitened momentum
+    HmChain *st;                       // [K]
+    double *draws, *rlp, *racc, *rde;  // records [K][T][d], [K][T]
+    int32_t *rdiv;
+    double *pX, *pout, *pv;            // PFMI_HMC_RECORD_PATH: [rounds][K][d], [rounds][K + K d], [rounds][K][d]
+    const double *vh, *tmat, *vchol, *sqa;
+};
+
+// the standard normal of row i of draw n under `seed`: the value pf_randn4(seed, i / 4, n, stream 0) gives row i (full table in global
+// memory: the same values as the LDS copy's)
+__device__ __forceinline__ double hm_normal(uint64_t seed, uint32_t n, int i) {
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32), g = (uint32_t)i >> 2, q = (uint32_t)i & 3u;
+    uint32_t x[4];
+    pf_philox_normals(n, g, 0u, 0u, k0, k1, x);
+    const uint32_t xw = q == 0 ? x[0] : q == 1 ? x[1] : q == 2 ? x[2] : x[3];
+    uint32_t x2w = 0u;
+    if ((xw & 0x7FFFFFFFu) < (1u << PF_ICDF_TAILBITS)) {
+        uint32_t x2[4];
+        pf_philox_normals(n, g, 0u, 1u, k0, k1, x2);
+        x2w = q == 0 ? x2[0] : q == 1 ? x2[1] : q == 2 ? x2[2] : x2[3];
+    }
+    return pf_icdf_any(xw, x2w);
+}
+
+// w[j] += row[j] z and y - row . tv, KPAD columns in groups of 4 (one 32-byte load each)
+template <int KPAD, int NV, bool KEEP>
+__device__ __forceinline__ void hm_row_axpy(const double *row, double *keep, double z, double (&w)[NV]) {
+#pragma unroll
+    for (int c = 0; c < KPAD; c += 4) {
+        const double4 r = *reinterpret_cast<const double4 *>(row + c);
+        if (KEEP) *reinterpret_cast<double4 *>(keep + c) = r;           // the thread's own LDS copy of the row, for the later passes
+        w[c] = fma(r.x, z, w[c]); w[c + 1] = fma(r.y, z, w[c + 1]); w[c + 2] = fma(r.z, z, w[c + 2]); w[c + 3] = fma(r.w, z, w[c + 3]);
+    }
+}
+template <int KPAD>
+__device__ __forceinline__ double hm_row_sub(const double *row, const double *tv, double y) {
+#pragma unroll
+    for (int c = 0; c < KPAD; c += 4) {
+        const double4 r = *reinterpret_cast<const double4 *>(row + c);
+        y = fma(-r.x, tv[c], y); y = fma(-r.y, tv[c + 1], y); y = fma(-r.z, tv[c + 2], y); y = fma(-r.w, tv[c + 3], y);
+    }
+    return y;
+}
+
+__global__ __launch_bounds__(HM_NT) void pf_hmc_init_kernel(HmArgs A) {
+    const int k = blockIdx.x, d = A.d;
+    const double *x0 = A.x0 + (size_t)k * d;
+    double *X = A.X + (size_t)k * d, *x = A.x + (size_t)k * d;
+    for (int i = threadIdx.x; i < d; i += HM_NT) { const double v = x0[i]; X[i] = v; x[i] = v; }
+    if (threadIdx.x == 0) {
+        HmChain S = {};
+        S.i = HM_START;
+        A.st[k] = S;
+    }
+}
+
+template <int KPAD, bool RES>
+__global__ __launch_bounds__(HM_NT) void pf_hmc_step_kernel(HmArgs A) {
+    extern __shared__ __attribute__((aligned(32))) double sVh[];      // RES: the chain's factor rows [d][KPAD]
+    constexpr int NVM = KPAD + 4;                        // KPAD sums + one rider, padded to the multiple of 4 pf_block_sum_mv takes
+    __shared__ double red[2 * HM_NW * NVM];
+    __shared__ double sHead[KPAD], sZ[KPAD], sTv[KPAD];
+    const int k = blockIdx.x, tid = threadIdx.x, d = A.d, K = A.K;
+    int flip = 0;
+    HmChain S = A.st[k];
+    const int p = A.pts[k];
+    const size_t kd = (size_t)k * d;
+    const double *gVh = A.vh + (size_t)p * d * KPAD, *T = A.tmat + (size_t)p * KPAD * KPAD, *Vc = A.vchol + (size_t)p * KPAD * KPAD;
+    const double *sqa = A.sqa + (size_t)p * d;
+    double *X = A.X + kd, *x = A.x + kd, *wg = A.wg + kd, *wt = A.wt + kd, *v = A.v + kd;
+    const double eps = A.eps[k];
+    const uint64_t seed = A.seeds[k];
+    // RES: a thread reads only the rows it owns (i = tid, tid + 256, ...), in every pass.  The first pass over the factor reads them from
+    // HBM and leaves them in LDS; the later ones (three more per launch) read the thread's own copy: no staging pass, no barrier.
+    bool staged = false;
+    auto vrow = [&](int i) -> const double * {
+        if constexpr (RES) return sVh + (size_t)i * KPAD;
+        else return gVh + (size_t)i * KPAD;
+    };
+    bool open = S.i == HM_OPEN, drift = false;
+    if (S.i != HM_OPEN) {
+        const double lpt = A.out[k];
+        const double *g = A.out + K + kd;
+        if (A.record) {                                  // what the closure saw and what it answered, before X is rewritten
+            double *pX = A.pX + ((size_t)A.round * K + k) * d, *pout = A.pout + (size_t)A.round * ((size_t)K * (d + 1));
+            for (int i = tid; i < d; i += HM_NT) { pX[i] = X[i]; pout[K + kd + i] = g[i]; }
+            if (tid == 0) pout[k] = lpt;
+        }
+        // ---- wt = R g: z = s . g, w = Vh'z, tv = T'w, y = z - Vh tv, head <- V head
+        double w[NVM];
+#pragma unroll
+        for (int j = 0; j < NVM; ++j) w[j] = 0.0;
+        for (int i = tid; i < d; i += HM_NT) {
+            const double gi = g[i], zi = sqa[i] * gi;
+            if (RES) hm_row_axpy<KPAD, NVM, true>(gVh + (size_t)i * KPAD, sVh + (size_t)i * KPAD, zi, w);
+            else hm_row_axpy<KPAD, NVM, false>(gVh + (size_t)i * KPAD, nullptr, zi, w);
+            w[KPAD] += isfinite(gi) ? 0.0 : 1.0;
+        }
+        staged = true;
+        pf_block_sum_mv<NVM, NVM>(w, red, flip);
+        const double nbad = w[KPAD];
+        if (tid < KPAD) {
+            double s = 0.0;
+#pragma unroll
+            for (int b = 0; b < KPAD; ++b) if (b <= tid) s = fma(T[b * KPAD + tid], w[b], s);
+            sTv[tid] = s;
+        }
+        __syncthreads();
+        for (int i = tid; i < d; i += HM_NT) {
+            const double y = hm_row_sub<KPAD>(vrow(i), sTv, sqa[i] * g[i]);
+            if (i < KPAD) sHead[i] = y; else wt[i] = y;
+        }
+        if (tid < KPAD && tid >= d) sHead[tid] = 0.0;
+        __syncthreads();
+        if (tid < KPAD && tid < d) {
+            double s = 0.0;
+#pragma unroll
+            for (int b = 0; b < KPAD; ++b) if (b >= tid) s = fma(Vc[tid * KPAD + b], sHead[b], s);
+            wt[tid] = s;                                 // (row tid is thread tid's own: every thread reads back only rows it wrote)
+        }
+        // ---- the pending kick
+        if (S.i == HM_START) {
+            const bool bad = nbad > 0.0 || !isfinite(lpt);       // a start point the chain cannot leave: reported by pfmi_hmc_wait
+            for (int i = tid; i < d; i += HM_NT) wg[i] = bad ? 0.0 : wt[i];
+            S.lp = bad ? -DBL_MAX : lpt;
+            S.dead = bad ? 1 : 0;
+            open = true;
+        } else if (S.i < A.nleap) {
+            for (int i = tid; i < d; i += HM_NT) v[i] = fma(eps, wt[i], v[i]);
+            if (nbad > 0.0 || !isfinite(lpt)) S.bad = 1;
+            ++S.i;
+            drift = true;
+        } else {
+            // ---- the trajectory's end: last half kick, H1, the decision, row t
+            double e = 0.0;
+            for (int i = tid; i < d; i += HM_NT) { const double vi = fma(0.5 * eps, wt[i], v[i]); e = fma(vi, vi, e); }
+            e = pf_block_sum1_pp<NVM>(e, red, flip);
+            const double H1 = -lpt + 0.5 * e, dH = H1 - S.H0;
+            const bool div = S.bad || nbad > 0.0 || !isfinite(lpt) || !isfinite(H1) || dH > 1000.0;
+            const double a = div ? 0.0 : fmin(1.0, exp(-dH));
+            const double u = (double)(pf_rand_u64(seed, (uint64_t)S.t, PF_RNG_STREAM_HMC_ACCEPT) >> 11) * 0x1p-53;
+            const bool acc = u < a;
+            const int64_t row = S.t - A.t0;
+            double *dr = A.draws + ((size_t)k * A.T + row) * d;
+            for (int i = tid; i < d; i += HM_NT) {
+                double xi = x[i];
+                if (acc) { xi = X[i]; x[i] = xi; wg[i] = wt[i]; }
+                dr[i] = xi;
+            }
+            if (acc) S.lp = lpt;
+            if (tid == 0) {
+                const size_t r = (size_t)k * A.T + row;
+                A.rlp[r] = S.lp; A.racc[r] = a; A.rde[r] = isfinite(dH) ? dH : DBL_MAX; A.rdiv[r] = div ? 1 : 0;
+            }
+            ++S.t; S.bad = 0;
+            if (S.t < A.t_end) open = true; else S.i = HM_OPEN;
+        }
+    }
+    double vv0 = 0.0;
+    if (open) {
+        // ---- the next trajectory: fresh momentum (draw index t of the chain's seed), first half kick
+        const uint32_t n = (uint32_t)S.t;
+        for (int i = tid; i < d; i += HM_NT) {
+            const double z = hm_normal(seed, n, i);
+            vv0 = fma(z, z, vv0);
+            v[i] = fma(0.5 * eps, wg[i], z);
+        }
+        S.i = 1;
+        drift = true;
+    }
+    if (drift) {
+        // ---- x~ <- base + e L v: z = [V'v_head; v_tail], w = Vh'z, tv = T w, y = s . (z - Vh tv)
+        const double *base = open ? x : X;
+        __syncthreads();                                 // the head product above has read sHead
+        if (tid < KPAD) sHead[tid] = tid < d ? v[tid] : 0.0;
+        __syncthreads();
+        if (tid < KPAD) {
+            double s = 0.0;
+#pragma unroll
+            for (int b = 0; b < KPAD; ++b) if (b <= tid) s = fma(Vc[b * KPAD + tid], sHead[b], s);
+            sZ[tid] = s;
+        }
+        __syncthreads();
+        double w[NVM];
+#pragma unroll
+        for (int j = 0; j < NVM; ++j) w[j] = 0.0;
+        if (RES && !staged) {                            // (the opening launch of PFMI_HMC_CONTINUE: no R-apply came before)
+            for (int i = tid; i < d; i += HM_NT)
+                hm_row_axpy<KPAD, NVM, true>(gVh + (size_t)i * KPAD, sVh + (size_t)i * KPAD, i < KPAD ? sZ[i] : v[i], w);
+        } else {
+            for (int i = tid; i < d; i += HM_NT) hm_row_axpy<KPAD, NVM, false>(vrow(i), nullptr, i < KPAD ? sZ[i] : v[i], w);
+        }
+        w[KPAD] = vv0;
+        pf_block_sum_mv<NVM, NVM>(w, red, flip);
+        if (open) S.H0 = -S.lp + 0.5 * w[KPAD];
+        if (tid < KPAD) {
+            double s = 0.0;
+#pragma unroll
+            for (int b = 0; b < KPAD; ++b) if (b >= tid) s = fma(T[tid * KPAD + b], w[b], s);
+            sTv[tid] = s;
+        }
+        __syncthreads();
+        for (int i = tid; i < d; i += HM_NT) {
+            const double y = hm_row_sub<KPAD>(vrow(i), sTv, i < KPAD ? sZ[i] : v[i]);
+            X[i] = fma(eps, sqa[i] * y, base[i]);
+        }
+    }
+    if (A.record && A.round >= 0) {
+        double *pv = A.pv + ((size_t)A.round * K + k) * d;
+        for (int i = tid; i < d; i += HM_NT) pv[i] = v[i];
+    }
+    __syncthreads();                                     // every thread has read S before thread 0 writes
+    if (tid == 0) A.st[k] = S;
+}
+
+// ---------------------------------------------------------------------------------------------------
+static HmArgs hm_args(pfmi_ctx *c, int64_t round) {
+    const HmcState &H = c->hmc;
+    HmArgs A;
+    A.d = c->d; A.K = H.K; A.nleap = H.nleap; A.record = H.record ? 1 : 0;
+    A.t0 = H.t0; A.t_end = H.t0 + H.T; A.T = H.T; A.round = round;
+    A.pts = c->hm_pts.as<int32_t>(); A.seeds = c->hm_seeds.as<uint64_t>(); A.eps = c->hm_eps.as<double>(); A.x0 = c->hm_x0.as<double>();
+    A.X = c->hm_X.as<double>(); A.out = c->hm_out.as<double>();
+    A.x = c->hm_x.as<double>(); A.wg = c->hm_wg.as<double>(); A.wt = c->hm_wt.as<double>(); A.v = c->hm_v.as<double>();
+    A.st = c->hm_st.as<HmChain>();
+    A.draws = c->hm_draws.as<double>(); A.rlp = c->hm_lp.as<double>(); A.racc = c->hm_acc.as<double>(); A.rde = c->hm_de.as<double>();
+    A.rdiv = c->hm_div.as<int32_t>();
+    A.pX = c->hm_pX.as<double>(); A.pout = c->hm_pout.as<double>(); A.pv = c->hm_pv.as<double>();
+    A.vh = c->vh.as<double>(); A.tmat = c->tmat.as<double>(); A.vchol = c->vchol.as<double>(); A.sqa = c->sqrt_alpha.as<double>();
+    return A;
+}
+
+size_t pf_hmc_chain_bytes() { return sizeof(HmChain); }
+// the staged factor rows of one chain fit in LDS beside the reduction buffers
+bool pf_hmc_resident(int d, int kpad) { return (size_t)d * kpad * sizeof(double) <= (size_t)HM_LDS_RES; }
+
+int32_t pf_launch_hmc_init(pfmi_ctx *c, hipStream_t s) {
+    hipLaunchKernelGGL(pf_hmc_init_kernel, dim3(c->hmc.K), dim3(HM_NT), 0, s, hm_args(c, 0));
+    PF_HIP(hipGetLastError());
+    return PFMI_OK;
+}
+
+template <int KPAD, bool RES>
+static int32_t hm_launch(pfmi_ctx *c, const HmArgs &A, hipStream_t s) {
+    const size_t lds = RES ? (size_t)A.d * KPAD * sizeof(double) : 0;
+    if (RES) PF_TRY(pf_raise_lds_limit(c, reinterpret_cast<const void *>(&pf_hmc_step_kernel<KPAD, RES>), HM_LDS_RES));
+    char name[32];
+    snprintf(name, sizeof name, "hmc:%d:%s", KPAD, RES ? "res" : "stream");
+    ++c->hmc_plans[name];
+    hipLaunchKernelGGL((pf_hmc_step_kernel<KPAD, RES>), dim3(A.K), dim3(HM_NT), lds, s, A);
+    return PFMI_OK;
+}
+
+// the dying chains' start flags: dead[k] != 0 when chain k's start point had a non-finite log density or gradient
+int32_t pf_hmc_dead_flags(pfmi_ctx *c, std::vector<int32_t> &dead) {
+    const int K = c->hmc.K;
+    std::vector<HmChain> st((size_t)K);
+    PF_HIP(hipMemcpyAsync(st.data(), c->hm_st.p, sizeof(HmChain) * K, hipMemcpyDeviceToHost, c->stream));
+    PF_HIP(hipStreamSynchronize(c->stream));
+    dead.resize((size_t)K);
+    for (int k = 0; k < K; ++k) dead[(size_t)k] = st[(size_t)k].dead;
+    return PFMI_OK;
+}
+
+int32_t pf_launch_hmc_step(pfmi_ctx *c, int64_t round, hipStream_t s) {
+    const HmArgs A = hm_args(c, round);
+    const bool res = pf_hmc_resident(A.d, c->kpad);
+    int32_t rc = PFMI_OK;
+    const bool ok = pf_dispatch_kpad<4, 8, 12, 16, 20, 32, 64>(c->kpad, [&](auto KP) {
+        rc = res ? hm_launch<KP(), true>(c, A, s) : hm_launch<KP(), false>(c, A, s);
+    });
+    PF_CHECK(ok, PFMI_ERR_UNSUPPORTED, "unsupported kpad %d", c->kpad);
+    PF_TRY(rc);
+    PF_HIP(hipGetLastError());
+    return PFMI_OK;
+}

@@ -106,6 +106,16 @@ struct LbcState {
     int32_t *h_prog = nullptr;                        // streaming: the pipeline's progress words (pf_lbc_step_kernel publishes); null: packed
 };
 
+// the chains of pfmi_hmc_enqueue (hmc_kernel.hip): resident between calls so that PFMI_HMC_CONTINUE goes on from them
+struct HmcState {
+    bool have = false;            // the chains' states and the last call's records are resident
+    bool active = false;          // rounds may still be in flight on the ctx stream: drain it before the buffers are reused
+    bool record = false;          // PFMI_HMC_RECORD_PATH of the last call
+    int K = 0, nleap = 0;
+    int64_t t0 = 0, T = 0;        // the last call made transitions t0 .. t0 + T - 1
+    int64_t rounds = 0, columns = 0, path_rounds = 0;
+};
+
 struct pfmi_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -264,6 +274,11 @@ struct pfmi_ctx {
     DevBuf lc_X, lc_out, lc_x, lc_g, lc_p, lc_gram, lc_st, lc_ctr;
     int64_t *lc_status = nullptr; // page-locked: round << 32 | active paths, written by the last workgroup of each round
     int32_t opt_K = 0, opt_cap = 0;
+    HmcState hmc;                 // static HMC on a fitted metric (hmc_kernel.hip, api_hmc.hip)
+    DevBuf hm_X, hm_out, hm_x0, hm_x, hm_wg, hm_wt, hm_v, hm_st, hm_pts, hm_seeds, hm_eps;
+    DevBuf hm_draws, hm_lp, hm_acc, hm_de, hm_div;      // the last call's records [K][T][d], [K][T]
+    DevBuf hm_pX, hm_pout, hm_pv;                       // PFMI_HMC_RECORD_PATH: every round's X, closure output and v
+    std::map<std::string, int64_t> hmc_plans;           // step launches per plan "hmc:<KPAD>:<res|stream>" (pfmi_kernel_time)
     bool elbo_pending = false;    // pfmi_elbo_batch_enqueue issued
     bool pool_from_best = false;  // the pool was filled by pfmi_pool_build_best (pool_ok is valid)
     DevBuf pool_ok;               // int32 [K]: 1 = the path's winning fit was a success (pfmi_pool_build_best)
@@ -381,6 +396,11 @@ size_t pf_lbc_path_state_bytes(int J);
 int32_t pf_lbc_alloc(pfmi_ctx *c, int K, int J, int d);
 int32_t pf_launch_lbc_init(pfmi_ctx *c, hipStream_t s);
 int32_t pf_launch_lbc_step(pfmi_ctx *c, int64_t round, hipStream_t s);
+size_t pf_hmc_chain_bytes();
+bool pf_hmc_resident(int d, int kpad);
+int32_t pf_launch_hmc_init(pfmi_ctx *c, hipStream_t s);
+int32_t pf_launch_hmc_step(pfmi_ctx *c, int64_t round, hipStream_t s);      // round < 0: open the next trajectory only (no closure output is read)
+int32_t pf_hmc_dead_flags(pfmi_ctx *c, std::vector<int32_t> &dead);
 int32_t pf_launch_woodbury_prim(pfmi_ctx *c, int mode, int64_t p, int64_t N, const double *d_in, double *d_out);
 int32_t pf_launch_colsumsq(pfmi_ctx *c, int64_t N, const double *d_x, double *d_out);
 int32_t pf_launch_woodbury_diag(pfmi_ctx *c, int64_t p, double *d_out);
@@ -667,6 +687,9 @@ __device__ __forceinline__ void pf_randn4(uint64_t seed, uint32_t g, uint32_t n,
     pf_icdf4<NB>(x, n, g, stream, k0, k1, lds_tab, z);
 }
 
+// Philox stream ids (counter word 2) in use: 0 the normals, 1 and 2 the resampling uniforms (psis_kernels.hip), 9 and 10 the hosts' seed
+// hierarchies (run seeds, per-point seeds)
+#define PF_RNG_STREAM_HMC_ACCEPT 3u     // the Metropolis uniform of transition t of a chain (hmc_kernel.hip)
 __device__ __forceinline__ uint64_t pf_rand_u64(uint64_t seed, uint64_t t, uint32_t stream) {
     uint32_t x[4];
     pf_philox4x32_10((uint32_t)t, (uint32_t)(t >> 32), stream, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), x);

@@ -1323,4 +1323,38 @@ Base.:+(c::LinearAlgebra.UniformScaling, W::DeviceWoodbury) = c + materialise(W)
 Base.:/(x::AbstractVecOrMat{Float64}, W::DeviceWoodbury) = Matrix(transpose(W \ Matrix(transpose(x))))
 PDMats.dim(W::DeviceWoodbury) = W.b.dim
 
+# ---- static HMC with the fitted metric, on the device (docs/src/examples/initializing-hmc.md, third way; the metric of
+# ext/PathfinderAdvancedHMCExt.jl:17-23 without leaving the GPU).  The engine's target must be a device closure with a gradient
+# (pfmi_set_target_gradient); built-in targets and host closures are refused by the library (PFMI_ERR_UNSUPPORTED).
+"""
+    hmc(b::Batch, points, x0, seeds, step_size; nleapfrog = 8, ntransitions, continue_ = false)
+
+`K = length(points)` chains of static HMC (fixed `nleapfrog`, Metropolis correction, full momentum refresh; no NUTS): chain k uses the
+Woodbury factor of fit `points[k]` (0-based) as its metric, starts at `x0[:, k]` and draws from `seeds[k]`.  Returns
+`(draws (d, T, K), logp, accept_prob, energy_error, divergent)`, the last four `(T, K)`.  `continue_ = true` goes on from the chains'
+resident states (`x0` is ignored).
+"""
+function hmc(b::Batch, points::AbstractVector{<:Integer}, x0::AbstractMatrix{Float64}, seeds::AbstractVector{UInt64},
+             step_size::AbstractVector{Float64}; nleapfrog::Integer = 8, ntransitions::Integer, continue_::Bool = false)
+    _live(b.eng, b.gen)
+    K = length(points); d = b.dim; T = Int(ntransitions)
+    (length(seeds) == K && length(step_size) == K && (continue_ || size(x0) == (d, K))) || throw(ArgumentError("hmc: K values per argument"))
+    pts = Vector{Int64}(points); X0 = Matrix{Float64}(x0); sd = Vector{UInt64}(seeds); ϵ = Vector{Float64}(step_size)
+    check(ccall((:pfmi_hmc_enqueue, libpfmi), Int32,
+                (Ptr{Cvoid}, Int32, Ptr{Int64}, Ptr{Float64}, Ptr{UInt64}, Ptr{Float64}, Int32, Int64, Int32),
+                b.eng.ptr, K, pts, X0, sd, ϵ, nleapfrog, T, continue_ ? Int32(1) : Int32(0)))
+    check(ccall((:pfmi_hmc_wait, libpfmi), Int32, (Ptr{Cvoid},), b.eng.ptr))
+    draws = Array{Float64}(undef, d, T, K)
+    lp = Matrix{Float64}(undef, T, K); acc = similar(lp); de = similar(lp); dv = Matrix{Int32}(undef, T, K)
+    check(ccall((:pfmi_hmc_get, libpfmi), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+                b.eng.ptr, draws, lp, acc, de, dv))
+    return (draws = draws, logp = lp, accept_prob = acc, energy_error = de, divergent = dv)
+end
+"rounds and closure columns of the last `hmc` call (pfmi_hmc_stats)"
+function hmc_stats(b::Batch)
+    r = Ref{Int64}(0); n = Ref{Int64}(0)
+    check(ccall((:pfmi_hmc_stats, libpfmi), Int32, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), b.eng.ptr, r, n))
+    return (rounds = r[], closure_columns = n[])
+end
+
 end # module

@@ -52,6 +52,7 @@ SYMBOLS = [
     "pfmi_pool_mixture_ratios", "pfmi_pool_mixture_ratios_dev",
     "pfmi_pool_psis_runs",
     "pfmi_pool_transform", "pfmi_pool_transform_revert",
+    "pfmi_hmc_enqueue", "pfmi_hmc_wait", "pfmi_hmc_get", "pfmi_hmc_draws_dev", "pfmi_hmc_get_path", "pfmi_hmc_stats",
 ]
 
 # declared argument types (entry points not listed here take what the caller wraps by hand)
@@ -65,6 +66,12 @@ ARGTYPES = {
     "pfmi_pool_transform": [C.c_void_p, _dp, _dp, _dp, _dp],
     "pfmi_pool_transform_revert": [C.c_void_p],
     "pfmi_pool_psis_runs": [C.c_void_p, C.c_int32, _dp, C.POINTER(C.c_int64), _dp, _dp, _dp, _dp],
+    "pfmi_hmc_enqueue": [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), _dp, C.POINTER(C.c_uint64), _dp, C.c_int32, C.c_int64, C.c_int32],
+    "pfmi_hmc_wait": [C.c_void_p],
+    "pfmi_hmc_get": [C.c_void_p, _dp, _dp, _dp, _dp, C.POINTER(C.c_int32)],
+    "pfmi_hmc_draws_dev": [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)],
+    "pfmi_hmc_get_path": [C.c_void_p, C.c_int64, C.c_int64, _dp, _dp, _dp],
+    "pfmi_hmc_stats": [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
 }
 
 

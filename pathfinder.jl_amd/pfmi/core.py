@@ -104,6 +104,7 @@ class Engine:
         self.offsets = None
         self.npoints = None
         self.J = 0
+        self._hmc = None                          # (K, T) of the last hmc_enqueue that succeeded
 
     def close(self):
         for cm in list(_LIVE_COMMS):                                    # every group this engine is a member of goes first
@@ -479,6 +480,70 @@ class Engine:
         out = np.empty(self.d)
         check(self.L.pfmi_woodbury_diag(self.ctx, C.c_int64(p), _d(out)))
         return out
+
+    # ---- static HMC with a fitted metric (include/pfmi.h: pfmi_hmc_enqueue) ---------------------------------------------------
+    HMC_CONTINUE, HMC_RECORD_PATH = 1, 2
+
+    def hmc_enqueue(self, points, x0, seeds, step_size, nleapfrog, ntransitions, cont=False, record_path=False):
+        """K chains of static HMC: chain k uses the metric of fit points[k], starts at x0[:, k] (d, K; ignored with cont=True, may be None),
+        draws its momenta and accept uniforms from seeds[k] and steps by step_size[k].  Enqueues every round; does not wait.  A Python
+        closure that raised is re-raised here."""
+        points = np.ascontiguousarray(points, dtype=np.int64)
+        K = len(points)
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
+        eps = np.ascontiguousarray(np.broadcast_to(np.asarray(step_size, dtype=np.float64), (K,)))
+        assert seeds.shape == (K,)
+        x0p = None
+        if x0 is not None:
+            x0 = np.asfortranarray(x0, dtype=np.float64)
+            assert x0.shape == (self.d, K), (x0.shape, self.d, K)
+            x0p = _d(x0)
+        flags = (self.HMC_CONTINUE if cont else 0) | (self.HMC_RECORD_PATH if record_path else 0)
+        rc = self.L.pfmi_hmc_enqueue(self.ctx, K, points.ctypes.data_as(_i64p), x0p, seeds.ctypes.data_as(C.POINTER(C.c_uint64)), _d(eps),
+                                     int(nleapfrog), int(ntransitions), flags)
+        if getattr(self.target, "pending_error", None) is not None:
+            self.sync()
+            self._raise_target_error()
+        check(rc)
+        self._hmc = (K, int(ntransitions))
+
+    def _hmc_run(self, who):
+        if self._hmc is None:
+            raise _lib.PfmiError(f"{who}: no hmc_enqueue has succeeded on this engine")
+        return self._hmc
+
+    def hmc_wait(self):
+        check(self.L.pfmi_hmc_wait(self.ctx))
+        self._raise_target_error()
+
+    def hmc_get(self, draws=True):
+        """the last call's rows: dict of draws (d, T, K), logp, accept_prob, energy_error, divergent (K, T)"""
+        K, T = self._hmc_run("hmc_get")
+        out = {k: np.empty((K, T)) for k in ("logp", "accept_prob", "energy_error")}
+        out["divergent"] = np.empty((K, T), dtype=np.int32)
+        X = np.empty((self.d, T, K), order="F") if draws else None
+        check(self.L.pfmi_hmc_get(self.ctx, _d(X) if draws else None, _d(out["logp"]), _d(out["accept_prob"]), _d(out["energy_error"]),
+                                  out["divergent"].ctypes.data_as(C.POINTER(C.c_int32))))
+        if draws:
+            out["draws"] = X
+        return out
+
+    def hmc_path(self, round0=0, nrounds=None):
+        """PFMI_HMC_RECORD_PATH: (X (d, K, n), logp (K, n), grad (d, K, n), v (d, K, n)) of rounds round0 .. round0 + n - 1"""
+        K, T = self._hmc_run("hmc_path")
+        r, _ = self.hmc_stats()
+        n = r - round0 if nrounds is None else nrounds
+        X = np.empty((self.d, K, n), order="F")
+        v = np.empty((self.d, K, n), order="F")
+        o = np.empty((K * (self.d + 1), n), order="F")
+        check(self.L.pfmi_hmc_get_path(self.ctx, round0, n, _d(X), _d(o), _d(v)))
+        return X, o[:K].copy(), o[K:].reshape(self.d, K, n, order="F").copy(), v
+
+    def hmc_stats(self):
+        """(rounds, closure columns) of the last hmc_enqueue"""
+        r, n = C.c_int64(), C.c_int64()
+        check(self.L.pfmi_hmc_stats(self.ctx, C.byref(r), C.byref(n)))
+        return r.value, n.value
 
     # ---- pool / PSIS / resample -------------------------------------------------------------------------
     def pool_build(self, N_r, points, seeds):

@@ -1,0 +1,136 @@
+"""Static HMC started from a Pathfinder result, with the fitted Woodbury metric, on the device (include/pfmi.h: pfmi_hmc_enqueue).
+
+The reference's worked example docs/src/examples/initializing-hmc.md, third way: "use Pathfinder's metric estimate for sampling"
+(AdvancedHMC.RankUpdateEuclideanMetric(result.fit_distribution.Sigma), ext/PathfinderAdvancedHMCExt.jl:17-23) -- here the chains run
+where the fits already are.  Scope: a fixed number of leapfrog steps per transition, Metropolis correction, full momentum refresh; no
+NUTS.  The target must be a device closure with a gradient (DeviceCallbackTarget(..., grad_fn=...), TorchDeviceTarget(..., grad=...));
+one engine only."""
+import sys
+import types
+from dataclasses import dataclass, field
+from typing import Any
+
+import numpy as np
+
+from .hostrng import HostRNG
+
+# Nesterov dual averaging of the step size (Hoffman & Gelman 2014, Algorithm 5 and section 3.2.1: their constants)
+DA_GAMMA, DA_T0, DA_KAPPA = 0.05, 10.0, 0.75
+
+
+def dual_averaging_init(step_size):
+    """state of dual_averaging_update for initial step sizes `step_size` (any shape): (m, Hbar, log_eps_bar, mu = log(10 eps_0))"""
+    e = np.asarray(step_size, dtype=np.float64)
+    return (0, np.zeros_like(e), np.zeros_like(e), np.log(10.0 * e))
+
+
+def dual_averaging_update(state, accept, target_accept=0.8):
+    """One update of Nesterov's dual averaging on the statistic `accept` (here: a window's mean acceptance probability, per chain):
+        Hbar_m        = (1 - 1/(m + t0)) Hbar_{m-1} + (target_accept - accept) / (m + t0)
+        log eps_m     = mu - sqrt(m) / gamma * Hbar_m
+        log epsbar_m  = m^-kappa log eps_m + (1 - m^-kappa) log epsbar_{m-1}
+    with gamma = 0.05, t0 = 10, kappa = 0.75, mu = log(10 eps_0).  Pure: returns (new state, eps_m, epsbar_m); eps_m is the step size
+    of the next window, epsbar_m the averaged one to sample with."""
+    m, hbar, leb, mu = state
+    m = m + 1
+    a = np.asarray(accept, dtype=np.float64)
+    hbar = (1.0 - 1.0 / (m + DA_T0)) * hbar + (target_accept - a) / (m + DA_T0)
+    le = mu - np.sqrt(m) / DA_GAMMA * hbar
+    w = m ** -DA_KAPPA
+    leb = w * le + (1.0 - w) * leb
+    return (m, hbar, leb, mu), np.exp(le), np.exp(leb)
+
+
+@dataclass
+class HMCResult:
+    draws: np.ndarray                 # (d, ndraws, nchains)
+    logp: np.ndarray                  # (nchains, ndraws)
+    accept_prob: np.ndarray           # (nchains, ndraws)
+    energy_error: np.ndarray          # (nchains, ndraws): H1 - H0 of every transition
+    divergent: np.ndarray             # (nchains, ndraws) int32
+    step_size: np.ndarray             # (nchains,): what the sampling phase used
+    metric_points: np.ndarray         # (nchains,): the fit point whose factor is the chain's metric
+    nleapfrog: int = 0
+    nwarmup: int = 0
+    engine: Any = field(repr=False, default=None)
+
+    def __str__(self):
+        d, n, k = self.draws.shape
+        lines = ["Static HMC result (fitted Woodbury metric)", f"  chains: {k}", f"  draws per chain: {n} (warm-up: {self.nwarmup})",
+                 f"  leapfrog steps: {self.nleapfrog}",
+                 f"  step size: {float(np.min(self.step_size)):.3g} .. {float(np.max(self.step_size)):.3g}",
+                 f"  mean acceptance: {float(np.mean(self.accept_prob)):.2f}", f"  divergent transitions: {int(np.sum(self.divergent))}"]
+        return "\n".join(lines)
+
+
+def _starts_and_points(result):
+    """(engine, draws (d, n), fit point of every draw, the fit token the points were made under)"""
+    from .api import MultiPathfinderResult
+    if isinstance(result, MultiPathfinderResult):
+        engs = list(result.engines) if result.engines else [result.engine]
+        if len(engs) > 1:
+            raise ValueError("pfmi.hmc is limited to one engine: the chains need every run's fit on the GPU that runs them")
+        dists = list(result.fit_distribution)
+        pts = np.array([dists[int(c) - 1].point for c in np.asarray(result.draw_component_ids)], dtype=np.int64)
+        return engs[0], np.asarray(result.draws), pts, dists[0].token
+    dist = result.fit_distribution
+    draws = np.asarray(result.draws)
+    return dist.engine, draws, np.full(draws.shape[1], dist.point, dtype=np.int64), dist.token
+
+
+def hmc(result, ndraws, *, nchains=None, nwarmup=0, step_size="auto", nleapfrog=8, rng=None, target_accept=0.8, window=10):
+    """`ndraws` transitions of `nchains` chains of static HMC from a PathfinderResult / MultiPathfinderResult.
+
+    Chain c starts at result.draws[:, c] (resample(result, nchains, replace=False) first gives distinct starts) and uses the best fit of
+    the run that draw came from as its metric.  step_size: a number, one per chain, or "auto": d^(-1/4), adapted per chain during the
+    `nwarmup` warm-up transitions between windows of `window` transitions by dual averaging on the window's mean acceptance
+    (dual_averaging_update); the warm-up draws are discarded and sampling uses the averaged step size."""
+    eng, starts, pts, token = _starts_and_points(result)
+    if eng is None:
+        raise ValueError("pfmi.hmc needs a result whose fits are still on an engine")
+    eng.check_token(token, "pfmi.hmc")
+    if not getattr(eng.target, "has_device_gradient", False):
+        raise ValueError("pfmi.hmc needs a device closure target with a gradient (built-in targets, host closures and device closures "
+                         "without a gradient are not supported)")
+    nchains = starts.shape[1] if nchains is None else int(nchains)
+    if not 1 <= nchains <= starts.shape[1]:
+        raise ValueError(f"nchains must be in 1 .. {starts.shape[1]} (the result's draws)")
+    d = starts.shape[0]
+    x0 = np.asfortranarray(starts[:, :nchains])
+    pts = pts[:nchains]
+    rng = rng if rng is not None else HostRNG(0)
+    seeds = rng.rand_u64(nchains)
+    auto = isinstance(step_size, str)
+    if auto and step_size != "auto":
+        raise ValueError('step_size must be a number, an array of nchains numbers or "auto"')
+    eps = np.full(nchains, d ** -0.25) if auto else np.broadcast_to(np.asarray(step_size, dtype=np.float64), (nchains,)).copy()
+    done, first = 0, True
+    if nwarmup > 0:
+        state = dual_averaging_init(eps)
+        ebar = eps
+        while done < nwarmup:
+            n = min(int(window), nwarmup - done)
+            eng.hmc_enqueue(pts, x0, seeds, eps, nleapfrog, n, cont=not first)
+            eng.hmc_wait()
+            first = False
+            done += n
+            if auto:
+                acc = eng.hmc_get(draws=False)["accept_prob"].mean(axis=1)
+                state, eps, ebar = dual_averaging_update(state, acc, target_accept)
+        if auto:
+            eps = np.asarray(ebar, dtype=np.float64)
+    eng.hmc_enqueue(pts, x0, seeds, eps, nleapfrog, int(ndraws), cont=not first)
+    eng.hmc_wait()
+    got = eng.hmc_get()
+    return HMCResult(got["draws"], got["logp"], got["accept_prob"], got["energy_error"], got["divergent"], np.array(eps), np.array(pts),
+                     int(nleapfrog), int(nwarmup), eng)
+
+
+class _CallableModule(types.ModuleType):
+    """pfmi.hmc is both the module (pfmi.hmc.dual_averaging_update) and the call pfmi.hmc(result, ndraws, ...)"""
+
+    def __call__(self, *args, **kwargs):
+        return hmc(*args, **kwargs)
+
+
+sys.modules[__name__].__class__ = _CallableModule
