@@ -377,6 +377,36 @@ int32_t pfmi_hmc_get_path(pfmi_ctx *ctx, int64_t round0, int64_t nrounds, double
 /* rounds and columns handed to the closure by the last pfmi_hmc_enqueue (pfmi_optimize_stats' counterpart) */
 int32_t pfmi_hmc_stats(pfmi_ctx *ctx, int64_t *rounds, int64_t *closure_columns);
 
+/* ---- chain diagnostics: rank-normalised split R-hat and ESS ------------------------------------------------------------------- */
+/* The table the reference's worked examples end every chain run with (summarystats(chns), docs/src/examples/turing.md,
+ * initializing-hmc.md): mean, sd, mcse, ess_bulk, ess_tail, rhat per coordinate, computed where the draws are.  Definitions: Vehtari,
+ * Gelman, Simpson, Carpenter, Buerkner (2021).  Per coordinate, x[k][t] with K >= 1 chains of T >= 8 draws:
+ *   split     n = T / 2, M = 2 K; split chain 2k = x[k][0:n], 2k + 1 = x[k][T-n:T] (odd T: the middle draw is in neither); S' = M n
+ *   series y  chain means ybar_m; gamma_m(t) = (1/n) sum_{i < n-t} (y[m][i] - ybar_m)(y[m][i+t] - ybar_m); W = n/(n-1) mean_m gamma_m(0);
+ *             var+ = (n-1)/n W + var_m(ybar_m, ddof 1); Rhat(y) = sqrt(var+ / W); rho_t = 1 - (W - mean_m gamma_m(t)) / var+, rho_0 = 1
+ *   ESS(y)    Geyer: P_j = rho_2j + rho_2j+1 while 2j + 1 <= n - 2; J the first j with P_j <= 0 (or the number of pairs); P'_j the running
+ *             minimum; tau = -1 + 2 sum_{j<J} P'_j + max(rho_2J, 0) (no last term when the pairs ran out); tau >= 1 / log10(S');
+ *             ESS = S' / tau
+ *   z(x)      the normal quantile (Wichura's AS 241, PPND16) of (r - 3/8) / (S' + 1/4), r the rank among the S' values that survive
+ *             the split, ties given their average rank;  fold(x) = |x - median|;  I_p(x) = [x <= q_p]; median and q_p are type 7
+ *   outputs   mean, sd (ddof 1) over all K T draws; ess_mean = ESS(x); mcse_mean = sd / sqrt(ess_mean); ess_bulk = ESS(z(x));
+ *             ess_tail = min(ESS(I_0.05), ESS(I_0.95)); rhat = max(Rhat(z(x)), Rhat(z(fold(x))))
+ * A coordinate with a non-finite draw: NaN in every output.  W = 0 (a constant series or indicator): NaN for that ESS / R-hat.
+ * Neither is an error.  A chain (or coordinate) whose values are all equal has exactly that value as its mean, so W = 0 is exact.  Every sum is formed in a fixed order: two calls give equal bits. */
+#define PFMI_CHAIN_SRC_HMC 0     /* the ctx's resident HMC records; draws NULL; d, T, K the run's values or all 0 */
+#define PFMI_CHAIN_SRC_HOST 1    /* draws: host array [K][T][d] (pfmi_hmc_get's layout), uploaded on the ctx stream; any ctx, no target or fit needed */
+#define PFMI_CHAIN_WITH_LP 1     /* SRC_HMC only: every output has one more entry, at index d, for the recorded logp series */
+/* Outputs: d (+ 1) doubles each; any may be NULL.  Waits.  The HMC records and PFMI_HMC_CONTINUE are untouched.  PFMI_ERR_ARG: T < 8,
+ * K < 1, d < 1, an unknown source or flag, WITH_LP with SRC_HOST, SRC_HMC with draws or with d, T, K that are not the run's.
+ * PFMI_ERR_STATE: SRC_HMC without a resident run (what forgets the chains: pfmi_hmc_enqueue).  PFMI_ERR_UNSUPPORTED: the workspace
+ * (about 8 (4 d K T) bytes) does not fit in free device memory; the message states the bytes.  Ranks are counted against sorted tiles
+ * of 2048 values, O((K T)^2 / 2048 log 2048) per coordinate (profiles/chain_diagnostics.md).  Stage names under pfmi_profile:
+ * "chain_diag_transpose", "chain_diag_moments", "chain_diag_rank", "chain_diag_ess", "chain_diag_final"; "chain_diag:count:<one|tiled>"
+ * counts the calls whose S' values fit one such tile or take several. */
+int32_t pfmi_chain_diagnostics(pfmi_ctx *ctx, int32_t source, const double *draws, int32_t d, int64_t T, int32_t K, int32_t flags,
+                               double *mean, double *sd, double *mcse_mean, double *ess_mean, double *ess_bulk, double *ess_tail,
+                               double *rhat);
+
 /* ---- pooling, _compute_psis_result, _resample ---------------------------------------------------- */
 /* draws_per_component = stack(draws) (src/multipath.jl:217): for path k take N_r draws of fit
  * `points[k]` with seed seeds[k] into the device-resident pool (d, N_r, K) and

@@ -382,6 +382,12 @@ int32_t pfmi_kernel_time(pfmi_ctx *c, const char *name, double *ms, int64_t *lau
         if (launches) *launches = (pl == c->hmc_plans.end()) ? 0 : pl->second;
         return PFMI_OK;
     }
+    if (strncmp(name, "chain_diag:", 11) == 0) {                      // counting launches of one plan of pfmi_chain_diagnostics, host-side count
+        auto pl = c->cd_plans.find(name);
+        if (ms) *ms = 0.0;
+        if (launches) *launches = (pl == c->cd_plans.end()) ? 0 : pl->second;
+        return PFMI_OK;
+    }
     if (strncmp(name, "fit:", 4) == 0) {                              // launches of one fit-kernel plan, host-side count ("fit" itself stays the stage)
         auto pl = c->fit_plans.find(name);
         if (ms) *ms = 0.0;

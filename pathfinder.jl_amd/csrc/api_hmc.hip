@@ -1,4 +1,5 @@
-// api_hmc.hip -- static HMC on a fitted metric for gradient closures: the entry points of include/pfmi.h over hmc_kernel.hip.
+// api_hmc.hip -- static HMC on a fitted metric for gradient closures: the entry points of include/pfmi.h over hmc_kernel.hip, and the
+// diagnostics of its chains (or of any uploaded ones), pfmi_chain_diagnostics over chain_diag_kernels.hip.
 #include "api_internal.h"
 
 #include <math.h>
@@ -182,6 +183,57 @@ int32_t pfmi_hmc_stats(pfmi_ctx *c, int64_t *rounds, int64_t *closure_columns) {
     PF_CHECK(c != nullptr, PFMI_ERR_ARG, "null pfmi_ctx");
     if (rounds) *rounds = c->hmc.rounds;
     if (closure_columns) *closure_columns = c->hmc.columns;
+    return PFMI_OK;
+}
+
+int32_t pfmi_chain_diagnostics(pfmi_ctx *c, int32_t source, const double *draws, int32_t d, int64_t T, int32_t K, int32_t flags,
+                               double *mean, double *sd, double *mcse_mean, double *ess_mean, double *ess_bulk, double *ess_tail,
+                               double *rhat) {
+    PF_CTX(c);
+    const bool resident = source == PFMI_CHAIN_SRC_HMC, with_lp = (flags & PFMI_CHAIN_WITH_LP) != 0;
+    PF_CHECK(resident || source == PFMI_CHAIN_SRC_HOST, PFMI_ERR_ARG, "chain_diagnostics: unknown source %d", source);
+    PF_CHECK((flags & ~PFMI_CHAIN_WITH_LP) == 0, PFMI_ERR_ARG, "chain_diagnostics: unknown flags %d", flags);
+    PF_CHECK(resident || !with_lp, PFMI_ERR_ARG, "chain_diagnostics: PFMI_CHAIN_WITH_LP needs PFMI_CHAIN_SRC_HMC");
+    if (resident) {
+        PF_CHECK(draws == nullptr, PFMI_ERR_ARG, "chain_diagnostics: PFMI_CHAIN_SRC_HMC takes no host draws");
+        PF_CHECK(c->hmc.have, PFMI_ERR_STATE, "chain_diagnostics: no HMC run on this ctx");
+        PF_CHECK((d == 0 && T == 0 && K == 0) || (d == c->d && T == c->hmc.T && K == c->hmc.K), PFMI_ERR_ARG,
+                 "chain_diagnostics: d = %d, T = %lld, K = %d are not the resident run's %d, %lld, %d (or all 0)", d, (long long)T, K, c->d,
+                 (long long)c->hmc.T, c->hmc.K);
+        d = c->d; T = c->hmc.T; K = c->hmc.K;
+    } else {
+        PF_CHECK(draws != nullptr, PFMI_ERR_ARG, "chain_diagnostics: null draws");
+    }
+    PF_CHECK(T >= 8 && K >= 1 && d >= 1, PFMI_ERR_ARG, "chain_diagnostics: needs T >= 8, K >= 1, d >= 1 (T = %lld, K = %d, d = %d)", (long long)T,
+             K, d);
+    PF_CHECK((double)K * (double)T < 2147483648.0, PFMI_ERR_UNSUPPORTED, "chain_diagnostics: K T = %.3g draws per coordinate is beyond 2^31",
+             (double)K * (double)T);
+    const size_t ws_bytes = pf_chain_diag_bytes(d, T, K, with_lp), in_bytes = resident ? 0 : sizeof(double) * (size_t)K * (size_t)T * (size_t)d;
+    {   // what the `ensure`s below will grow, against what is free (as pfmi_hmc_enqueue does)
+        size_t fr = 0, tot = 0;
+        PF_HIP(hipMemGetInfo(&fr, &tot));
+        double need = 0.0;
+        if (ws_bytes > c->cd_ws.cap) need += (double)ws_bytes;
+        if (in_bytes > c->cd_in.cap) need += (double)in_bytes;
+        PF_CHECK(need < 0.8 * (double)fr, PFMI_ERR_UNSUPPORTED,
+                 "chain_diagnostics: %.0f bytes more needed for d = %d, T = %lld, K = %d (workspace %zu, records %zu); %.0f bytes free", need, d,
+                 (long long)T, K, ws_bytes, in_bytes, (double)fr);
+    }
+    PF_TRY(c->cd_ws.ensure(ws_bytes));
+    const double *rec = c->hm_draws.as<double>(), *lp = with_lp ? c->hm_lp.as<double>() : nullptr;
+    if (!resident) {
+        PF_TRY(c->cd_in.ensure(in_bytes));
+        PF_TRY(pf_upload(c, c->cd_in.p, draws, in_bytes));
+        rec = c->cd_in.as<double>();
+    }
+    const double *out = nullptr;
+    PF_TRY(pf_launch_chain_diag(c, rec, lp, d, T, K, &out));
+    const size_t V = (size_t)d + (with_lp ? 1 : 0);
+    double *dst[7] = {mean, sd, mcse_mean, ess_mean, ess_bulk, ess_tail, rhat};
+    for (int q = 0; q < 7; ++q)
+        if (dst[q]) PF_TRY(pf_download(c, dst[q], out + (size_t)q * V, sizeof(double) * V));
+    PF_TRY(pf_stream_sync(c));
+    if (resident) c->hmc.active = false;                  // the stream is drained: the run's rounds are done
     return PFMI_OK;
 }
 

@@ -279,6 +279,8 @@ struct pfmi_ctx {
     DevBuf hm_draws, hm_lp, hm_acc, hm_de, hm_div;      // the last call's records [K][T][d], [K][T]
     DevBuf hm_pX, hm_pout, hm_pv;                       // PFMI_HMC_RECORD_PATH: every round's X, closure output and v
     std::map<std::string, int64_t> hmc_plans;           // step launches per plan "hmc:<KPAD>:<res|stream>" (pfmi_kernel_time)
+    DevBuf cd_ws, cd_in;                                // pfmi_chain_diagnostics: its workspace (chain_diag_kernels.hip) and uploaded host records
+    std::map<std::string, int64_t> cd_plans;            // its counting launches per plan "chain_diag:count:<one|tiled>" (pfmi_kernel_time)
     bool elbo_pending = false;    // pfmi_elbo_batch_enqueue issued
     bool pool_from_best = false;  // the pool was filled by pfmi_pool_build_best (pool_ok is valid)
     DevBuf pool_ok;               // int32 [K]: 1 = the path's winning fit was a success (pfmi_pool_build_best)
@@ -401,6 +403,10 @@ bool pf_hmc_resident(int d, int kpad);
 int32_t pf_launch_hmc_init(pfmi_ctx *c, hipStream_t s);
 int32_t pf_launch_hmc_step(pfmi_ctx *c, int64_t round, hipStream_t s);      // round < 0: open the next trajectory only (no closure output is read)
 int32_t pf_hmc_dead_flags(pfmi_ctx *c, std::vector<int32_t> &dead);
+// chain_diag_kernels.hip: bytes of c->cd_ws for K chains of T draws of d coordinates (+ the logp series), and the seven outputs of the
+// device records d_rec [K][T][d] (d_lp [K][T] or NULL) into *d_out [7][d (+ 1)] inside that workspace; enqueued, not waited for
+size_t pf_chain_diag_bytes(int d, int64_t T, int K, bool with_lp);
+int32_t pf_launch_chain_diag(pfmi_ctx *c, const double *d_rec, const double *d_lp, int d, int64_t T, int K, const double **d_out);
 int32_t pf_launch_woodbury_prim(pfmi_ctx *c, int mode, int64_t p, int64_t N, const double *d_in, double *d_out);
 int32_t pf_launch_colsumsq(pfmi_ctx *c, int64_t N, const double *d_x, double *d_out);
 int32_t pf_launch_woodbury_diag(pfmi_ctx *c, int64_t p, double *d_out);

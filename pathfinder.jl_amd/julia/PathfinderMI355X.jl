@@ -1357,4 +1357,30 @@ function hmc_stats(b::Batch)
     return (rounds = r[], closure_columns = n[])
 end
 
+# ---- chain diagnostics on the device: what summarystats(chns) reports in docs/src/examples/turing.md and initializing-hmc.md
+function _chain_diagnostics(eng::Engine, source::Integer, draws, d::Integer, T::Integer, K::Integer, flags::Integer, len::Integer)
+    out = [Vector{Float64}(undef, len) for _ in 1:7]
+    check(ccall((:pfmi_chain_diagnostics, libpfmi), Int32,
+                (Ptr{Cvoid}, Int32, Ptr{Float64}, Int32, Int64, Int32, Int32,
+                 Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                eng.ptr, source, draws, d, T, K, flags, out[1], out[2], out[3], out[4], out[5], out[6], out[7]))
+    return (mean = out[1], sd = out[2], mcse_mean = out[3], ess_mean = out[4], ess_bulk = out[5], ess_tail = out[6], rhat = out[7])
+end
+"""
+    chain_diagnostics(b::Batch; with_lp = false)
+    chain_diagnostics(eng::Engine, draws::Array{Float64,3})
+
+Rank-normalised split R-hat, bulk and tail ESS, mean, sd and MCSE of the mean per coordinate (Vehtari et al. 2021; pfmi_chain_diagnostics).
+The first form reads the resident records of the batch's last `hmc` call (`with_lp` appends the logp series as one more entry); the
+second uploads any `(d, T, K)` array of `K` chains of `T >= 8` draws and needs no target or fit.
+"""
+function chain_diagnostics(b::Batch; with_lp::Bool = false)
+    _live(b.eng, b.gen)
+    return _chain_diagnostics(b.eng, 0, Ptr{Float64}(C_NULL), 0, 0, 0, with_lp ? 1 : 0, b.dim + (with_lp ? 1 : 0))
+end
+function chain_diagnostics(eng::Engine, draws::Array{Float64,3})
+    d, T, K = size(draws)
+    return _chain_diagnostics(eng, 1, draws, d, T, K, 0, d)
+end
+
 end # module

@@ -105,6 +105,7 @@ class Engine:
         self.npoints = None
         self.J = 0
         self._hmc = None                          # (K, T) of the last hmc_enqueue that succeeded
+        self.hmc_runs = 0                         # hmc_enqueue calls that succeeded (HMCResult.summary: is a result still the resident run?)
 
     def close(self):
         for cm in list(_LIVE_COMMS):                                    # every group this engine is a member of goes first
@@ -506,6 +507,32 @@ class Engine:
             self._raise_target_error()
         check(rc)
         self._hmc = (K, int(ntransitions))
+        self.hmc_runs += 1
+
+    # ---- chain diagnostics (include/pfmi.h: pfmi_chain_diagnostics) ---------------------------------------------------------------
+    CHAIN_SRC_HMC, CHAIN_SRC_HOST, CHAIN_WITH_LP = 0, 1, 1
+    CHAIN_KEYS = ("mean", "sd", "mcse_mean", "ess_mean", "ess_bulk", "ess_tail", "rhat")
+
+    def chain_diagnostics(self, draws=None, with_lp=False):
+        """Rank-normalised split R-hat, bulk / tail ESS, mean, sd and MCSE per coordinate: dict of CHAIN_KEYS -> (d,) arrays.  draws: a
+        (d, T, K) array of K chains of T draws, uploaded (no target or fit needed); None: the resident records of the last hmc_enqueue,
+        with_lp=True appending the recorded logp series as entry d."""
+        if draws is None:
+            K, T = self._hmc_run("chain_diagnostics")
+            n = self.d + (1 if with_lp else 0)
+            src, ptr, dims = self.CHAIN_SRC_HMC, None, (0, 0, 0)
+        else:
+            if with_lp:
+                raise ValueError("chain_diagnostics: with_lp needs the resident records (draws=None)")
+            X = np.asfortranarray(draws, dtype=np.float64)
+            if X.ndim != 3:
+                raise ValueError("chain_diagnostics: draws must be a (d, T, K) array")
+            n = X.shape[0]
+            src, ptr, dims = self.CHAIN_SRC_HOST, _d(X), X.shape
+        out = {k: np.empty(n) for k in self.CHAIN_KEYS}
+        check(self.L.pfmi_chain_diagnostics(self.ctx, src, ptr, int(dims[0]), int(dims[1]), int(dims[2]), self.CHAIN_WITH_LP if with_lp else 0,
+                                            *[_d(out[k]) for k in self.CHAIN_KEYS]))
+        return out
 
     def _hmc_run(self, who):
         if self._hmc is None:

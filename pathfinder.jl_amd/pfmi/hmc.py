@@ -12,6 +12,7 @@ from typing import Any
 
 import numpy as np
 
+from .core import Engine
 from .hostrng import HostRNG
 
 # Nesterov dual averaging of the step size (Hoffman & Gelman 2014, Algorithm 5 and section 3.2.1: their constants)
@@ -41,6 +42,51 @@ def dual_averaging_update(state, accept, target_accept=0.8):
     return (m, hbar, leb, mu), np.exp(le), np.exp(leb)
 
 
+CHAIN_KEYS = Engine.CHAIN_KEYS        # mean, sd, mcse_mean, ess_mean, ess_bulk, ess_tail, rhat
+
+
+@dataclass
+class ChainSummary:
+    """summarystats(chns) of the reference's worked examples (docs/src/examples/turing.md): per coordinate, and for logp in `lp`"""
+    mean: np.ndarray                  # (d,) each
+    sd: np.ndarray
+    mcse_mean: np.ndarray
+    ess_mean: np.ndarray
+    ess_bulk: np.ndarray
+    ess_tail: np.ndarray
+    rhat: np.ndarray
+    lp: dict                          # the same seven values of the logp series, as floats
+    nchains: int = 0
+    ndraws: int = 0
+
+    def ok(self, rhat=1.01, ess_per_chain=100):
+        """Vehtari et al. (2021): every R-hat below 1.01 and bulk and tail ESS of at least 100 per chain, logp included (NaN: not ok)"""
+        need = ess_per_chain * self.nchains
+        r = np.append(self.rhat, self.lp["rhat"])
+        e = np.concatenate([self.ess_bulk, self.ess_tail, [self.lp["ess_bulk"], self.lp["ess_tail"]]])
+        return bool(np.all(r < rhat) and np.all(e >= need))
+
+    def __str__(self):
+        lines = ["Chain diagnostics (rank-normalised split R-hat, ESS)", f"  chains: {self.nchains}", f"  draws per chain: {self.ndraws}",
+                 f"  rhat: max {float(np.max(self.rhat)):.4f} (logp {self.lp['rhat']:.4f})",
+                 f"  ess_bulk: min {float(np.min(self.ess_bulk)):.0f} (logp {self.lp['ess_bulk']:.0f})",
+                 f"  ess_tail: min {float(np.min(self.ess_tail)):.0f} (logp {self.lp['ess_tail']:.0f})",
+                 f"  mcse_mean / sd: max {float(np.max(self.mcse_mean / self.sd)):.3g}"]
+        return "\n".join(lines)
+
+
+def chain_diagnostics(draws, engine=None):
+    """mean, sd, mcse_mean, ess_mean, ess_bulk, ess_tail and rhat (dict of (d,) arrays) of any (d, T, K) array of K chains of T draws, on
+    the device; `engine` needs no target (None: a temporary Engine on GPU 0)"""
+    if engine is not None:
+        return engine.chain_diagnostics(draws)
+    e = Engine(0)
+    try:
+        return e.chain_diagnostics(draws)
+    finally:
+        e.close()
+
+
 @dataclass
 class HMCResult:
     draws: np.ndarray                 # (d, ndraws, nchains)
@@ -53,6 +99,27 @@ class HMCResult:
     nleapfrog: int = 0
     nwarmup: int = 0
     engine: Any = field(repr=False, default=None)
+    run: int = 0                      # engine.hmc_runs after this result's last hmc_enqueue (0: unknown)
+
+    def summary(self):
+        """ChainSummary of the draws and of logp.  While this result is still the engine's latest run the resident records are used; after
+        another run (or once the library has forgotten the chains) the result's own host copy is uploaded: the same numbers either way."""
+        from ._lib import PfmiError
+        eng = self.engine
+        live = eng is not None and getattr(eng, "ctx", None)
+        out = None
+        if live and self.run and eng.hmc_runs == self.run:
+            try:
+                out = eng.chain_diagnostics(with_lp=True)
+            except PfmiError as ex:
+                if getattr(ex, "code", 0) != -3:                      # PFMI_ERR_STATE: the chains were forgotten
+                    raise
+        if out is None:
+            x = chain_diagnostics(self.draws, eng if live else None)
+            lp = chain_diagnostics(self.logp.T[None, :, :], eng if live else None)
+            out = {k: np.append(x[k], lp[k]) for k in CHAIN_KEYS}
+        d, n, k = self.draws.shape
+        return ChainSummary(*[out[q][:d] for q in CHAIN_KEYS], {q: float(out[q][d]) for q in CHAIN_KEYS}, k, n)
 
     def __str__(self):
         d, n, k = self.draws.shape
@@ -123,7 +190,7 @@ def hmc(result, ndraws, *, nchains=None, nwarmup=0, step_size="auto", nleapfrog=
     eng.hmc_wait()
     got = eng.hmc_get()
     return HMCResult(got["draws"], got["logp"], got["accept_prob"], got["energy_error"], got["divergent"], np.array(eps), np.array(pts),
-                     int(nleapfrog), int(nwarmup), eng)
+                     int(nleapfrog), int(nwarmup), eng, eng.hmc_runs)
 
 
 class _CallableModule(types.ModuleType):
