@@ -377,6 +377,67 @@ int32_t pfmi_hmc_get_path(pfmi_ctx *ctx, int64_t round0, int64_t nrounds, double
 /* rounds and columns handed to the closure by the last pfmi_hmc_enqueue (pfmi_optimize_stats' counterpart) */
 int32_t pfmi_hmc_stats(pfmi_ctx *ctx, int64_t *rounds, int64_t *closure_columns);
 
+/* ---- NUTS with a fitted metric, for gradient closures ------------------------------------------------------------------------ */
+/* The sampler the reference's worked example hands Pathfinder's metric to (docs/src/examples/initializing-hmc.md,
+ * ext/PathfinderAdvancedHMCExt.jl, ext/PathfinderDynamicHMCExt.jl): K independent chains of multinomial NUTS (Betancourt 2017) with the
+ * iterative tree builder (checkpoints instead of recursion), on the device, with the metric, the whitened momentum, the target and the
+ * points of pfmi_hmc_enqueue.  No trajectory length to choose: transition t doubles its trajectory until it turns.
+ *   v0 = the normals of draw t under the chain's seed, H0 = -lp + |v0|^2 / 2; the tree is the leaf (x, v0), log-weight 0, rho = v0.
+ *   Doubling j = 0, 1, ..: dir = +1 iff the top bit of rand_u64(s, 16 t + j, stream 4); a sub-tree of 2^j leaves grows from the tree's end
+ *   in that direction by leapfrog steps of size dir e.  Leaf n (0-based) with momentum v, energy H = -lp~ + |v|^2 / 2, lw = H0 - H:
+ *     - divergent (non-finite lp~, g~ or H, or H - H0 > 1000): the sub-tree is discarded and the transition ends;
+ *     - rho_s += v; the leaf replaces the sub-tree's candidate iff u < exp(lw - logaddexp(logW_s, lw)), u = (rand_u64(s, 1024 t + m,
+ *       stream 6) >> 11) 2^-53 with m the leaves made before it in this transition; logW_s <- logaddexp(logW_s, lw);
+ *     - imax = popcount(n >> 1); an even n stores (v, rho_s) as checkpoint imax; an odd n checks the checkpoints imax down to
+ *       imax - (trailing one-bits of n) + 1: with rho_sub = rho_s - rho_ck[i] + v_ck[i], a turn when rho_sub . v_ck[i] <= 0 or
+ *       rho_sub . v <= 0: the sub-tree is discarded and the transition ends.
+ *   A completed sub-tree's candidate replaces the tree's iff u < exp(logW_s - logW), u from rand_u64(s, 16 t + j, stream 5); then
+ *   logW <- logaddexp(logW, logW_s), rho += rho_s; the transition ends when rho . v- <= 0 or rho . v+ <= 0 (the momenta at the two ends), or
+ *   when j + 1 == max_depth.  The tree's candidate becomes the state and row t.
+ * Rows (shared with static HMC: pfmi_hmc_get, pfmi_hmc_draws_dev and pfmi_chain_diagnostics(PFMI_CHAIN_SRC_HMC) serve a NUTS run after its
+ * wait): accept_prob is the mean over the transition's leaves of min(1, exp(H0 - H_leaf)) (a divergent leaf counts 0), energy_error is
+ * H(selected) - H0, divergent as above.
+ * One ROUND is one call of the closure on all K columns and one launch of the step kernel: one leapfrog step of every running chain.  The
+ * round count is not known up front: _enqueue issues a first window of rounds and returns; pfmi_nuts_pump issues more, a bounded window
+ * ahead of the last progress word read from the device, never beyond the cap (fresh ? 1 : 0) + T (2^max_depth - 1).  Chains run
+ * asynchronously: one that ends a transition opens its next in the same launch; one that has made its T transitions idles (its column of X
+ * stays its state: the closure is still called on it).  A chain's output depends on its own inputs alone.
+ * Errors are pfmi_hmc_enqueue's; also PFMI_ERR_ARG for max_depth outside 1 .. 10, PFMI_ERR_STATE for CONTINUE on static-HMC chains (and
+ * PFMI_HMC_CONTINUE on NUTS chains), PFMI_ERR_UNSUPPORTED when the buffers (with RECORD_PATH: one path row per round of the cap) do not fit.
+ * Stage names: "nuts", "nuts_closure"; "nuts:<KPAD>:<res|stream>" counts the step launches of one plan. */
+#define PFMI_NUTS_CONTINUE 1
+#define PFMI_NUTS_RECORD_PATH 2
+int32_t pfmi_nuts_enqueue(pfmi_ctx *ctx, int32_t K, const int64_t *points, const double *x0, const uint64_t *seeds, const double *step_size,
+                          int32_t max_depth, int64_t ntransitions, int32_t flags);
+/* one scheduling pass from the calling thread: never blocks.  *finished = 1 once every chain has made its transitions. */
+int32_t pfmi_nuts_pump(pfmi_ctx *ctx, int32_t *finished);
+/* pumps until finished, then waits for the stream.  PFMI_ERR_NUMERIC: a start point with a non-finite log density or gradient (the chains
+ * are forgotten).  PFMI_ERR_STATE without a NUTS run. */
+int32_t pfmi_nuts_wait(pfmi_ctx *ctx);
+/* tree_depth (doublings made, the discarded one included) and n_leapfrog (leaves made) of the last call's transitions, int32 [K][T] */
+int32_t pfmi_nuts_get_stats(pfmi_ctx *ctx, int32_t *tree_depth, int32_t *n_leapfrog);
+/* what one round decided for one chain (PFMI_NUTS_RECORD_PATH); t = -1: the round evaluated the start point, or the chain was idle */
+typedef struct {
+    int32_t t, j, n, dir;           /* transition, doubling, leaf of the sub-tree, direction */
+    int32_t leaf, flags;            /* leaves made before this one in the transition; PFMI_NUTS_EV_* */
+    double H_leaf, logW_s, logW, H0;/* the leaf's energy; both log weights after the round's updates; the tree's root energy */
+} pfmi_nuts_event;
+#define PFMI_NUTS_EV_DIVERGENT 1
+#define PFMI_NUTS_EV_SUBTREE_TURN 2
+#define PFMI_NUTS_EV_LEAF_TAKEN 4      /* the leaf replaced the sub-tree's candidate */
+#define PFMI_NUTS_EV_SUBTREE_DONE 8    /* the sub-tree was completed and merged */
+#define PFMI_NUTS_EV_TREE_TAKEN 16     /* its candidate replaced the tree's */
+#define PFMI_NUTS_EV_TREE_TURN 32
+#define PFMI_NUTS_EV_MAX_DEPTH 64
+#define PFMI_NUTS_EV_END 128           /* the transition ended in this round */
+/* PFMI_NUTS_RECORD_PATH: rounds round0 .. round0 + nrounds - 1 of the last call (nrounds at most pfmi_nuts_stats' rounds): X and
+ * closure_out as pfmi_hmc_get_path gives them; v (d, K, nrounds) the synchronised whitened momentum of the leaf the round finished (0 in the
+ * start round); events [nrounds][K].  Columns of idle chains are not written.  Any may be NULL. */
+int32_t pfmi_nuts_get_path(pfmi_ctx *ctx, int64_t round0, int64_t nrounds, double *X, double *closure_out, double *v, pfmi_nuts_event *events);
+/* rounds until the last chain went idle, and the columns handed to the closure: K per round issued, idle chains' columns and the rounds
+ * issued ahead of the last progress word included */
+int32_t pfmi_nuts_stats(pfmi_ctx *ctx, int64_t *rounds, int64_t *closure_columns);
+
 /* ---- chain diagnostics: rank-normalised split R-hat and ESS ------------------------------------------------------------------- */
 /* The table the reference's worked examples end every chain run with (summarystats(chns), docs/src/examples/turing.md,
  * initializing-hmc.md): mean, sd, mcse, ess_bulk, ess_tail, rhat per coordinate, computed where the draws are.  Definitions: Vehtari,

@@ -322,6 +322,7 @@ int32_t pfmi_destroy(pfmi_ctx *c) {
     for (hipEvent_t e : c->sg_cb) if (e) (void)hipEventDestroy(e);
     if (c->h_prog) (void)hipHostFree(c->h_prog);
     if (c->lc_status) (void)hipHostFree(c->lc_status);
+    if (c->nt_status) (void)hipHostFree(c->nt_status);
     if (c->h_list) (void)hipHostFree(c->h_list);
     (void)hipStreamDestroy(c->stream);
     delete c;                               // every DevBuf of the context, the target's included, frees its memory: no stream carries work
@@ -376,7 +377,7 @@ int32_t pfmi_kernel_time(pfmi_ctx *c, const char *name, double *ms, int64_t *lau
         if (launches) *launches = (pl == c->draw_plans.end()) ? 0 : pl->second;
         return PFMI_OK;
     }
-    if (strncmp(name, "hmc:", 4) == 0) {                              // launches of one plan of the HMC step kernel, host-side count ("hmc" is the stage)
+    if (strncmp(name, "hmc:", 4) == 0 || strncmp(name, "nuts:", 5) == 0) {                              // launches of one plan of the HMC step kernel, host-side count ("hmc" is the stage)
         auto pl = c->hmc_plans.find(name);
         if (ms) *ms = 0.0;
         if (launches) *launches = (pl == c->hmc_plans.end()) ? 0 : pl->second;

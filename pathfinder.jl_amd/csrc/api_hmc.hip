@@ -31,6 +31,7 @@ static int32_t hmc_enqueue(pfmi_ctx *c, int32_t K, const int64_t *points, const 
         PF_CHECK(isfinite(step_size[k]) && step_size[k] > 0.0, PFMI_ERR_ARG, "hmc_enqueue: step size of chain %d is not positive and finite", k);
     }
     PF_CHECK(!cont || (H.have && H.K == K), PFMI_ERR_STATE, "hmc_enqueue: PFMI_HMC_CONTINUE without %d resident chains", K);
+    PF_CHECK(!cont || H.kind == 0, PFMI_ERR_STATE, "hmc_enqueue: PFMI_HMC_CONTINUE on the chains of pfmi_nuts_enqueue");
     const int d = c->d;
     const int64_t rounds = (cont ? 0 : 1) + T * (int64_t)nleapfrog;
     {   // the fits the chains ask for are successes
@@ -89,7 +90,7 @@ static int32_t hmc_enqueue(pfmi_ctx *c, int32_t K, const int64_t *points, const 
     PF_TRY(pf_upload(c, c->hm_seeds.p, seeds, sizeof(uint64_t) * (size_t)K));
     PF_TRY(pf_upload(c, c->hm_eps.p, step_size, sizeof(double) * (size_t)K));
     if (!cont) PF_TRY(pf_upload(c, c->hm_x0.p, x0, vec));
-    H.K = K; H.nleap = nleapfrog; H.record = rec;
+    H.K = K; H.nleap = nleapfrog; H.record = rec; H.kind = 0; H.finished = true;
     H.t0 = cont ? H.t0 + H.T : 0; H.T = T;
     H.rounds = 0; H.columns = 0; H.path_rounds = rec ? rounds : 0;
     H.have = true; H.active = true;                       // from here on, failure paths drain (pfmi_hmc_enqueue)
@@ -129,6 +130,7 @@ int32_t pfmi_hmc_enqueue(pfmi_ctx *c, int32_t K, const int64_t *points, const do
 int32_t pfmi_hmc_wait(pfmi_ctx *c) {
     PF_CTX(c);
     PF_CHECK(c->hmc.have, PFMI_ERR_STATE, "hmc_wait: no pfmi_hmc_enqueue outstanding");
+    PF_CHECK(c->hmc.kind == 0, PFMI_ERR_STATE, "hmc_wait: the run on this ctx is pfmi_nuts_enqueue's (pfmi_nuts_wait)");
     PF_TRY(pf_stream_sync(c));
     c->hmc.active = false;
     std::vector<int32_t> dead;
@@ -144,6 +146,7 @@ int32_t pfmi_hmc_wait(pfmi_ctx *c) {
 int32_t pfmi_hmc_get(pfmi_ctx *c, double *draws, double *logp, double *accept_prob, double *energy_error, int32_t *divergent) {
     PF_CTX(c);
     PF_CHECK(c->hmc.have, PFMI_ERR_STATE, "hmc_get: no HMC run on this ctx");
+    PF_CHECK(c->hmc.finished, PFMI_ERR_STATE, "hmc_get: the NUTS run has rounds to go (pfmi_nuts_wait)");
     const size_t rows = (size_t)c->hmc.K * (size_t)c->hmc.T;
     if (logp) PF_TRY(pf_download(c, logp, c->hm_lp.p, sizeof(double) * rows));
     if (accept_prob) PF_TRY(pf_download(c, accept_prob, c->hm_acc.p, sizeof(double) * rows));
@@ -167,7 +170,7 @@ int32_t pfmi_hmc_draws_dev(pfmi_ctx *c, void **dev_ptr, int64_t *count) {
 int32_t pfmi_hmc_get_path(pfmi_ctx *c, int64_t round0, int64_t nrounds, double *X, double *closure_out, double *v) {
     PF_CTX(c);
     const HmcState &H = c->hmc;
-    PF_CHECK(H.have && H.record, PFMI_ERR_STATE, "hmc_get_path: the last pfmi_hmc_enqueue did not run with PFMI_HMC_RECORD_PATH");
+    PF_CHECK(H.have && H.record && H.kind == 0, PFMI_ERR_STATE, "hmc_get_path: the last pfmi_hmc_enqueue did not run with PFMI_HMC_RECORD_PATH");
     PF_CHECK(round0 >= 0 && nrounds >= 0 && round0 + nrounds <= H.path_rounds, PFMI_ERR_ARG, "hmc_get_path: rounds [%lld, %lld) outside [0, %lld)",
              (long long)round0, (long long)(round0 + nrounds), (long long)H.path_rounds);
     const size_t vec = (size_t)H.K * c->d, ovec = (size_t)H.K * (c->d + 1);
@@ -197,6 +200,7 @@ int32_t pfmi_chain_diagnostics(pfmi_ctx *c, int32_t source, const double *draws,
     if (resident) {
         PF_CHECK(draws == nullptr, PFMI_ERR_ARG, "chain_diagnostics: PFMI_CHAIN_SRC_HMC takes no host draws");
         PF_CHECK(c->hmc.have, PFMI_ERR_STATE, "chain_diagnostics: no HMC run on this ctx");
+        PF_CHECK(c->hmc.finished, PFMI_ERR_STATE, "chain_diagnostics: the NUTS run has rounds to go (pfmi_nuts_wait)");
         PF_CHECK((d == 0 && T == 0 && K == 0) || (d == c->d && T == c->hmc.T && K == c->hmc.K), PFMI_ERR_ARG,
                  "chain_diagnostics: d = %d, T = %lld, K = %d are not the resident run's %d, %lld, %d (or all 0)", d, (long long)T, K, c->d,
                  (long long)c->hmc.T, c->hmc.K);

@@ -114,6 +114,11 @@ struct HmcState {
     int K = 0, nleap = 0;
     int64_t t0 = 0, T = 0;        // the last call made transitions t0 .. t0 + T - 1
     int64_t rounds = 0, columns = 0, path_rounds = 0;
+    // kind 1 (pfmi_nuts_enqueue, nuts_kernel.hip): the round count is not known up front, the rounds are pumped as the closure L-BFGS's are
+    int kind = 0;                 // 0: static HMC, 1: NUTS -- PFMI_*_CONTINUE goes on only from chains of its own kind
+    int max_depth = 0, md_alloc = 0;                  // the stop rule of the last call; the depth the chains' checkpoints were made for
+    int64_t issued = 0, seen = 0, max_rounds = 0;     // rounds launched / last round whose progress word the host has read / hard cap
+    bool finished = true;         // every chain has made its transitions (or the cap is reached and seen)
 };
 
 struct pfmi_ctx {
@@ -278,6 +283,8 @@ struct pfmi_ctx {
     DevBuf hm_X, hm_out, hm_x0, hm_x, hm_wg, hm_wt, hm_v, hm_st, hm_pts, hm_seeds, hm_eps;
     DevBuf hm_draws, hm_lp, hm_acc, hm_de, hm_div;      // the last call's records [K][T][d], [K][T]
     DevBuf hm_pX, hm_pout, hm_pv;                       // PFMI_HMC_RECORD_PATH: every round's X, closure output and v
+    DevBuf nt_vec, nt_st, nt_depth, nt_nleap, nt_pev, nt_ctr;   // NUTS: the chains' vectors and checkpoints, their scalars, statistics, events
+    int64_t *nt_status = nullptr; // page-locked: round << 32 | chains still running, written by the last workgroup of each NUTS round
     std::map<std::string, int64_t> hmc_plans;           // step launches per plan "hmc:<KPAD>:<res|stream>" (pfmi_kernel_time)
     DevBuf cd_ws, cd_in;                                // pfmi_chain_diagnostics: its workspace (chain_diag_kernels.hip) and uploaded host records
     std::map<std::string, int64_t> cd_plans;            // its counting launches per plan "chain_diag:count:<one|tiled>" (pfmi_kernel_time)
@@ -403,6 +410,12 @@ bool pf_hmc_resident(int d, int kpad);
 int32_t pf_launch_hmc_init(pfmi_ctx *c, hipStream_t s);
 int32_t pf_launch_hmc_step(pfmi_ctx *c, int64_t round, hipStream_t s);      // round < 0: open the next trajectory only (no closure output is read)
 int32_t pf_hmc_dead_flags(pfmi_ctx *c, std::vector<int32_t> &dead);
+// nuts_kernel.hip
+size_t pf_nuts_chain_bytes();
+int pf_nuts_vec_slots(int max_depth);
+int32_t pf_launch_nuts_init(pfmi_ctx *c, hipStream_t s);
+int32_t pf_launch_nuts_step(pfmi_ctx *c, int64_t round, int64_t prow, bool reopen, hipStream_t s);
+int32_t pf_nuts_chain_flags(pfmi_ctx *c, std::vector<int32_t> &dead, int64_t *last_round);
 // chain_diag_kernels.hip: bytes of c->cd_ws for K chains of T draws of d coordinates (+ the logp series), and the seven outputs of the
 // device records d_rec [K][T][d] (d_lp [K][T] or NULL) into *d_out [7][d (+ 1)] inside that workspace; enqueued, not waited for
 size_t pf_chain_diag_bytes(int d, int64_t T, int K, bool with_lp);
@@ -696,6 +709,9 @@ __device__ __forceinline__ void pf_randn4(uint64_t seed, uint32_t g, uint32_t n,
 // Philox stream ids (counter word 2) in use: 0 the normals, 1 and 2 the resampling uniforms (psis_kernels.hip), 9 and 10 the hosts' seed
 // hierarchies (run seeds, per-point seeds)
 #define PF_RNG_STREAM_HMC_ACCEPT 3u     // the Metropolis uniform of transition t of a chain (hmc_kernel.hip)
+#define PF_RNG_STREAM_NUTS_DIR 4u       // nuts_kernel.hip: the direction of doubling j of transition t (counter 16 t + j, top bit)
+#define PF_RNG_STREAM_NUTS_TREE 5u      // the uniform that lets a completed sub-tree's candidate replace the tree's (counter 16 t + j)
+#define PF_RNG_STREAM_NUTS_LEAF 6u      // the uniform that lets a leaf replace its sub-tree's candidate (counter 1024 t + leaf); 7: the hosts' HostRNG
 __device__ __forceinline__ uint64_t pf_rand_u64(uint64_t seed, uint64_t t, uint32_t stream) {
     uint32_t x[4];
     pf_philox4x32_10((uint32_t)t, (uint32_t)(t >> 32), stream, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), x);

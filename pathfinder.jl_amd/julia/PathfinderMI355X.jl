@@ -1357,6 +1357,45 @@ function hmc_stats(b::Batch)
     return (rounds = r[], closure_columns = n[])
 end
 
+# ---- NUTS with the fitted metric, on the device (the sampler docs/src/examples/initializing-hmc.md hands the metric to): the arguments of
+# `hmc` with a tree-depth limit in place of the leapfrog count.
+"""
+    nuts(b::Batch, points, x0, seeds, step_size; max_depth = 10, ntransitions, continue_ = false)
+
+`K = length(points)` chains of multinomial NUTS (iterative tree builder, at most `2^max_depth - 1` leapfrog steps per transition) with the
+metrics, starts and seeds of `hmc`.  Returns `hmc`'s rows and `tree_depth`, `n_leapfrog` `(T, K)`.
+"""
+function nuts(b::Batch, points::AbstractVector{<:Integer}, x0::AbstractMatrix{Float64}, seeds::AbstractVector{UInt64},
+              step_size::AbstractVector{Float64}; max_depth::Integer = 10, ntransitions::Integer, continue_::Bool = false)
+    _live(b.eng, b.gen)
+    K = length(points); d = b.dim; T = Int(ntransitions)
+    (length(seeds) == K && length(step_size) == K && (continue_ || size(x0) == (d, K))) || throw(ArgumentError("nuts: K values per argument"))
+    pts = Vector{Int64}(points); X0 = Matrix{Float64}(x0); sd = Vector{UInt64}(seeds); ϵ = Vector{Float64}(step_size)
+    check(ccall((:pfmi_nuts_enqueue, libpfmi), Int32,
+                (Ptr{Cvoid}, Int32, Ptr{Int64}, Ptr{Float64}, Ptr{UInt64}, Ptr{Float64}, Int32, Int64, Int32),
+                b.eng.ptr, K, pts, X0, sd, ϵ, max_depth, T, continue_ ? Int32(1) : Int32(0)))
+    check(ccall((:pfmi_nuts_wait, libpfmi), Int32, (Ptr{Cvoid},), b.eng.ptr))
+    draws = Array{Float64}(undef, d, T, K)
+    lp = Matrix{Float64}(undef, T, K); acc = similar(lp); de = similar(lp); dv = Matrix{Int32}(undef, T, K)
+    check(ccall((:pfmi_hmc_get, libpfmi), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+                b.eng.ptr, draws, lp, acc, de, dv))
+    depth = Matrix{Int32}(undef, T, K); nleap = Matrix{Int32}(undef, T, K)
+    check(ccall((:pfmi_nuts_get_stats, libpfmi), Int32, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}), b.eng.ptr, depth, nleap))
+    return (draws = draws, logp = lp, accept_prob = acc, energy_error = de, divergent = dv, tree_depth = depth, n_leapfrog = nleap)
+end
+"one scheduling pass of a `pfmi_nuts_enqueue` that is not waited for; `true` once every chain has made its transitions"
+function nuts_pump(b::Batch)
+    fin = Ref{Int32}(0)
+    check(ccall((:pfmi_nuts_pump, libpfmi), Int32, (Ptr{Cvoid}, Ref{Int32}), b.eng.ptr, fin))
+    return fin[] != 0
+end
+"rounds until the last chain went idle and closure columns (idle chains' included) of the last `nuts` call (pfmi_nuts_stats)"
+function nuts_stats(b::Batch)
+    r = Ref{Int64}(0); n = Ref{Int64}(0)
+    check(ccall((:pfmi_nuts_stats, libpfmi), Int32, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), b.eng.ptr, r, n))
+    return (rounds = r[], closure_columns = n[])
+end
+
 # ---- chain diagnostics on the device: what summarystats(chns) reports in docs/src/examples/turing.md and initializing-hmc.md
 function _chain_diagnostics(eng::Engine, source::Integer, draws, d::Integer, T::Integer, K::Integer, flags::Integer, len::Integer)
     out = [Vector{Float64}(undef, len) for _ in 1:7]

@@ -572,6 +572,72 @@ class Engine:
         check(self.L.pfmi_hmc_stats(self.ctx, C.byref(r), C.byref(n)))
         return r.value, n.value
 
+    # ---- NUTS with a fitted metric (include/pfmi.h: pfmi_nuts_enqueue) ---------------------------------------------------------------
+    NUTS_CONTINUE, NUTS_RECORD_PATH = 1, 2
+    # pfmi_nuts_event; flags: divergent 1, sub-tree turn 2, leaf taken 4, sub-tree done 8, tree taken 16, tree turn 32, max depth 64, end 128
+    NUTS_EVENT = np.dtype([("t", np.int32), ("j", np.int32), ("n", np.int32), ("dir", np.int32), ("leaf", np.int32), ("flags", np.int32),
+                           ("H_leaf", np.float64), ("logW_s", np.float64), ("logW", np.float64), ("H0", np.float64)])
+
+    def nuts_enqueue(self, points, x0, seeds, step_size, max_depth, ntransitions, cont=False, record_path=False):
+        """K chains of multinomial NUTS: the arguments of hmc_enqueue with max_depth (1 .. 10) in place of the leapfrog count.  Issues the first
+        window of rounds and returns; nuts_pump / nuts_wait issue the rest.  A Python closure that raised is re-raised here."""
+        points = np.ascontiguousarray(points, dtype=np.int64)
+        K = len(points)
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
+        eps = np.ascontiguousarray(np.broadcast_to(np.asarray(step_size, dtype=np.float64), (K,)))
+        assert seeds.shape == (K,)
+        x0p = None
+        if x0 is not None:
+            x0 = np.asfortranarray(x0, dtype=np.float64)
+            assert x0.shape == (self.d, K), (x0.shape, self.d, K)
+            x0p = _d(x0)
+        flags = (self.NUTS_CONTINUE if cont else 0) | (self.NUTS_RECORD_PATH if record_path else 0)
+        rc = self.L.pfmi_nuts_enqueue(self.ctx, K, points.ctypes.data_as(_i64p), x0p, seeds.ctypes.data_as(C.POINTER(C.c_uint64)), _d(eps),
+                                      int(max_depth), int(ntransitions), flags)
+        if getattr(self.target, "pending_error", None) is not None:
+            self.sync()
+            self._raise_target_error()
+        check(rc)
+        self._hmc = (K, int(ntransitions))
+        self.hmc_runs += 1
+
+    def nuts_pump(self):
+        """one scheduling pass; True once every chain has made its transitions"""
+        fin = C.c_int32(0)
+        check(self.L.pfmi_nuts_pump(self.ctx, C.byref(fin)))
+        return bool(fin.value)
+
+    def nuts_wait(self):
+        check(self.L.pfmi_nuts_wait(self.ctx))
+        self._raise_target_error()
+
+    def nuts_get_stats(self):
+        """(tree_depth, n_leapfrog) of the last call's transitions, int32 (K, T) each; the rows themselves: hmc_get"""
+        K, T = self._hmc_run("nuts_get_stats")
+        dep, nl = np.empty((K, T), dtype=np.int32), np.empty((K, T), dtype=np.int32)
+        i32p = C.POINTER(C.c_int32)
+        check(self.L.pfmi_nuts_get_stats(self.ctx, dep.ctypes.data_as(i32p), nl.ctypes.data_as(i32p)))
+        return dep, nl
+
+    def nuts_stats(self):
+        """(rounds until the last chain went idle, closure columns: idle chains' and the rounds issued ahead included)"""
+        r, n = C.c_int64(), C.c_int64()
+        check(self.L.pfmi_nuts_stats(self.ctx, C.byref(r), C.byref(n)))
+        return r.value, n.value
+
+    def nuts_path(self, round0=0, nrounds=None):
+        """PFMI_NUTS_RECORD_PATH: (X (d, K, n), logp (K, n), grad (d, K, n), v (d, K, n), events (n, K) of NUTS_EVENT) of rounds
+        round0 .. round0 + n - 1; v is the synchronised momentum of the leaf the round finished"""
+        K, T = self._hmc_run("nuts_path")
+        r, _ = self.nuts_stats()
+        n = r - round0 if nrounds is None else nrounds
+        X = np.empty((self.d, K, n), order="F")
+        v = np.empty((self.d, K, n), order="F")
+        o = np.empty((K * (self.d + 1), n), order="F")
+        ev = np.empty((n, K), dtype=self.NUTS_EVENT)
+        check(self.L.pfmi_nuts_get_path(self.ctx, round0, n, _d(X), _d(o), _d(v), ev.ctypes.data_as(C.c_void_p)))
+        return X, o[:K].copy(), o[K:].reshape(self.d, K, n, order="F").copy(), v, ev
+
     # ---- pool / PSIS / resample -------------------------------------------------------------------------
     def pool_build(self, N_r, points, seeds):
         points = np.ascontiguousarray(points, dtype=np.int64)

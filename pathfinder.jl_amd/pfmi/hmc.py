@@ -1,10 +1,11 @@
-"""Static HMC started from a Pathfinder result, with the fitted Woodbury metric, on the device (include/pfmi.h: pfmi_hmc_enqueue).
+"""Static HMC and NUTS started from a Pathfinder result, with the fitted Woodbury metric, on the device (include/pfmi.h:
+pfmi_hmc_enqueue, pfmi_nuts_enqueue).
 
 The reference's worked example docs/src/examples/initializing-hmc.md, third way: "use Pathfinder's metric estimate for sampling"
 (AdvancedHMC.RankUpdateEuclideanMetric(result.fit_distribution.Sigma), ext/PathfinderAdvancedHMCExt.jl:17-23) -- here the chains run
 where the fits already are.  Scope: a fixed number of leapfrog steps per transition, Metropolis correction, full momentum refresh; no
 NUTS.  The target must be a device closure with a gradient (DeviceCallbackTarget(..., grad_fn=...), TorchDeviceTarget(..., grad=...));
-one engine only."""
+one engine only.  `nuts` below is the dynamic sampler with the same starts, metric and step-size adaptation."""
 import sys
 import types
 from dataclasses import dataclass, field
@@ -191,6 +192,71 @@ def hmc(result, ndraws, *, nchains=None, nwarmup=0, step_size="auto", nleapfrog=
     got = eng.hmc_get()
     return HMCResult(got["draws"], got["logp"], got["accept_prob"], got["energy_error"], got["divergent"], np.array(eps), np.array(pts),
                      int(nleapfrog), int(nwarmup), eng, eng.hmc_runs)
+
+
+@dataclass
+class NUTSResult(HMCResult):
+    """the fields of HMCResult (nleapfrog is 0: the trajectory length is dynamic) and the trees' statistics"""
+    tree_depth: np.ndarray = None     # (nchains, ndraws) int32: doublings of the transition, the discarded one included
+    n_leapfrog: np.ndarray = None     # (nchains, ndraws) int32: leapfrog steps of the transition
+    max_depth: int = 0
+
+    def __str__(self):
+        d, n, k = self.draws.shape
+        lines = ["NUTS result (fitted Woodbury metric)", f"  chains: {k}", f"  draws per chain: {n} (warm-up: {self.nwarmup})",
+                 f"  tree depth: mean {float(np.mean(self.tree_depth)):.2f}, max {int(np.max(self.tree_depth))} (limit {self.max_depth})",
+                 f"  leapfrog steps per draw: {float(np.mean(self.n_leapfrog)):.1f}",
+                 f"  step size: {float(np.min(self.step_size)):.3g} .. {float(np.max(self.step_size)):.3g}",
+                 f"  mean acceptance: {float(np.mean(self.accept_prob)):.2f}", f"  divergent transitions: {int(np.sum(self.divergent))}"]
+        return "\n".join(lines)
+
+
+def nuts(result, ndraws, *, nchains=None, nwarmup=0, step_size="auto", max_depth=10, rng=None, target_accept=0.8, window=10):
+    """`ndraws` transitions of `nchains` chains of multinomial NUTS from a PathfinderResult / MultiPathfinderResult: the starts, metrics,
+    seeds and step-size rule of `hmc` (dual averaging between windows of `window` warm-up transitions on the windows' mean accept_prob,
+    the mean over a tree's leaves of min(1, exp(H0 - H))), with trees of at most 2^max_depth - 1 leapfrog steps instead of a fixed count."""
+    eng, starts, pts, token = _starts_and_points(result)
+    if eng is None:
+        raise ValueError("pfmi.nuts needs a result whose fits are still on an engine")
+    eng.check_token(token, "pfmi.nuts")
+    if not getattr(eng.target, "has_device_gradient", False):
+        raise ValueError("pfmi.nuts needs a device closure target with a gradient (built-in targets, host closures and device closures "
+                         "without a gradient are not supported)")
+    if not 1 <= int(max_depth) <= 10:
+        raise ValueError("max_depth must be in 1 .. 10")
+    nchains = starts.shape[1] if nchains is None else int(nchains)
+    if not 1 <= nchains <= starts.shape[1]:
+        raise ValueError(f"nchains must be in 1 .. {starts.shape[1]} (the result's draws)")
+    d = starts.shape[0]
+    x0 = np.asfortranarray(starts[:, :nchains])
+    pts = pts[:nchains]
+    rng = rng if rng is not None else HostRNG(0)
+    seeds = rng.rand_u64(nchains)
+    auto = isinstance(step_size, str)
+    if auto and step_size != "auto":
+        raise ValueError('step_size must be a number, an array of nchains numbers or "auto"')
+    eps = np.full(nchains, d ** -0.25) if auto else np.broadcast_to(np.asarray(step_size, dtype=np.float64), (nchains,)).copy()
+    done, first = 0, True
+    if nwarmup > 0:
+        state = dual_averaging_init(eps)
+        ebar = eps
+        while done < nwarmup:
+            n = min(int(window), nwarmup - done)
+            eng.nuts_enqueue(pts, x0, seeds, eps, max_depth, n, cont=not first)
+            eng.nuts_wait()
+            first = False
+            done += n
+            if auto:
+                acc = eng.hmc_get(draws=False)["accept_prob"].mean(axis=1)
+                state, eps, ebar = dual_averaging_update(state, acc, target_accept)
+        if auto:
+            eps = np.asarray(ebar, dtype=np.float64)
+    eng.nuts_enqueue(pts, x0, seeds, eps, max_depth, int(ndraws), cont=not first)
+    eng.nuts_wait()
+    got = eng.hmc_get()
+    depth, nleap = eng.nuts_get_stats()
+    return NUTSResult(got["draws"], got["logp"], got["accept_prob"], got["energy_error"], got["divergent"], np.array(eps), np.array(pts),
+                      0, int(nwarmup), eng, eng.hmc_runs, depth, nleap, int(max_depth))
 
 
 class _CallableModule(types.ModuleType):
