@@ -438,6 +438,47 @@ int32_t pfmi_nuts_get_path(pfmi_ctx *ctx, int64_t round0, int64_t nrounds, doubl
  * issued ahead of the last progress word included */
 int32_t pfmi_nuts_stats(pfmi_ctx *ctx, int64_t *rounds, int64_t *closure_columns);
 
+/* ---- device-resident warm-up: step-size adaptation inside static HMC and NUTS ---------------------------------------------------- */
+/* What the samplers the reference hands the metric to do during warm-up (AdvancedHMC's StepSizeAdaptor / StanHMCAdaptor, DynamicHMC's
+ * dual averaging): the step size of every chain is updated after EVERY warm-up transition, here by the launch that ends the transition,
+ * so that one enqueue runs nwarmup = W warm-up and ntransitions = T sampling transitions back to back with no host round trip in between.
+ * Nesterov dual averaging (Hoffman & Gelman 2014, Algorithm 5; gamma = 0.05, t0 = 10, kappa = 0.75), per chain and per transition.  a_t is
+ * the acceptance statistic of warm-up transition t (0-based, t < W) -- exactly the row's accept_prob, so 0 for a divergent transition.  With
+ * m = t + 1, the target delta = target_accept and mu = log(10 eps_0):
+ *     Hbar <- (1 - 1/(m + t0)) Hbar + (delta - a_t)/(m + t0)        Hbar_0 = 0
+ *     le    = mu - (sqrt(m)/gamma) Hbar
+ *     w     = m^(-3/4) = 1 / (sqrt(m) sqrt(sqrt(m)))                (no pow)
+ *     leb  <- w le + (1 - w) leb                                     leb_0 = 0
+ * Transition t + 1 uses exp(le) while t + 1 < W; every transition t >= W uses exp(leb_W).  An update that yields a step size that is zero
+ * or not finite leaves the chain the step size it has and sets PFMI_ADAPT_KEPT_STEP in the chain's status.  There is no initial step-size
+ * search and no clamp.
+ * Rows: the warm-up transitions write none.  pfmi_hmc_get, pfmi_hmc_draws_dev, pfmi_nuts_get_stats and pfmi_chain_diagnostics(SRC_HMC) see
+ * the T sampling transitions W .. W + T - 1 as rows 0 .. T - 1; the random numbers of transition t are those of transition t of a plain
+ * run.  A later plain PFMI_HMC_CONTINUE / PFMI_NUTS_CONTINUE goes on from transition W + T with the step sizes it is given.
+ * flags must be 0 (an adaptive run is a fresh run; no CONTINUE, no RECORD_PATH): anything else, nwarmup < 1 or target_accept outside (0, 1)
+ * is PFMI_ERR_ARG; every other error is that of pfmi_hmc_enqueue / pfmi_nuts_enqueue.  Every error, a refused argument included, drains
+ * this ctx's stream and leaves no chains and no traces behind.  Waiting and reading stay pfmi_hmc_wait,
+ * pfmi_nuts_pump / pfmi_nuts_wait and pfmi_hmc_get; the NUTS cap is 1 + (W + T) (2^max_depth - 1) rounds.
+ * Stage names: "hmc_adapt", "hmc_adapt_closure", "nuts_adapt", "nuts_adapt_closure"; "hmc_adapt:<KPAD>:<res|stream>" and
+ * "nuts_adapt:<KPAD>:<res|stream>" count the launches of one plan of the warm kernels (the plain runs' counters are untouched). */
+#define PFMI_ADAPT_KEPT_STEP 1   /* status bit: an update gave a step size that was zero or not finite; the chain kept its previous one */
+int32_t pfmi_hmc_adapt_enqueue(pfmi_ctx *ctx, int32_t K, const int64_t *points, const double *x0, const uint64_t *seeds,
+                               const double *step_size0, int32_t nleapfrog, int64_t nwarmup, int64_t ntransitions, double target_accept,
+                               int32_t flags);
+int32_t pfmi_nuts_adapt_enqueue(pfmi_ctx *ctx, int32_t K, const int64_t *points, const double *x0, const uint64_t *seeds,
+                                const double *step_size0, int32_t max_depth, int64_t nwarmup, int64_t ntransitions, double target_accept,
+                                int32_t flags);
+/* The last adaptive run: step_size [K] the one its sampling transitions used (a later plain CONTINUE with step sizes of the caller's own
+ * does not change what is reported here); eps_trace, accept_trace [K][W] the step size warm-up transition
+ * t used and its a_t; divergent, n_leapfrog int32 [K][W]; status [K] (PFMI_ADAPT_*).  Any may be NULL.  Waits for the stream (a NUTS run
+ * must be finished: pfmi_nuts_wait).  PFMI_ERR_STATE without an adaptive run: whatever forgets the chains forgets the traces. */
+int32_t pfmi_adapt_get(pfmi_ctx *ctx, double *step_size, double *eps_trace, double *accept_trace, int32_t *divergent, int32_t *n_leapfrog,
+                       int32_t *status);
+/* The host build of the update the warm kernels run (one source, csrc/adapt.h): n updates on accept[0 .. n - 1] from eps0.  eps [n + 1]:
+ * eps[0] = eps0, eps[m] the step size after m updates (exp(le_m), or eps[m - 1] where that is zero or not finite); eps_bar [n] (may be
+ * NULL): exp(leb_m) at index m - 1.  Needs no GPU and no ctx. */
+int32_t pfmi_host_dual_averaging(int64_t n, double eps0, double target_accept, const double *accept, double *eps, double *eps_bar);
+
 /* ---- chain diagnostics: rank-normalised split R-hat and ESS ------------------------------------------------------------------- */
 /* The table the reference's worked examples end every chain run with (summarystats(chns), docs/src/examples/turing.md,
  * initializing-hmc.md): mean, sd, mcse, ess_bulk, ess_tail, rhat per coordinate, computed where the draws are.  Definitions: Vehtari,

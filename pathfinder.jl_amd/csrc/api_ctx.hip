@@ -377,7 +377,9 @@ int32_t pfmi_kernel_time(pfmi_ctx *c, const char *name, double *ms, int64_t *lau
         if (launches) *launches = (pl == c->draw_plans.end()) ? 0 : pl->second;
         return PFMI_OK;
     }
-    if (strncmp(name, "hmc:", 4) == 0 || strncmp(name, "nuts:", 5) == 0) {                              // launches of one plan of the HMC step kernel, host-side count ("hmc" is the stage)
+    bool sampler_plan = false;                                        // launches of one plan of a step or warm kernel, host-side count ("hmc", "nuts", ... are the stages)
+    for (const char *pre : {"hmc:", "nuts:", "hmc_adapt:", "nuts_adapt:"}) sampler_plan = sampler_plan || strncmp(name, pre, strlen(pre)) == 0;
+    if (sampler_plan) {
         auto pl = c->hmc_plans.find(name);
         if (ms) *ms = 0.0;
         if (launches) *launches = (pl == c->hmc_plans.end()) ? 0 : pl->second;

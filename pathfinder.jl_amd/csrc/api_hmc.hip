@@ -11,10 +11,13 @@ void hmc_forget(pfmi_ctx *c) {
     if (c->hmc.active) (void)hipStreamSynchronize(c->stream);
     c->hmc.active = false;
     c->hmc.have = false;
+    c->hmc.adapting = false;
+    c->hmc.W = 0;
+    c->hmc.eps_kept = false;
 }
 
-static int32_t hmc_enqueue(pfmi_ctx *c, int32_t K, const int64_t *points, const double *x0, const uint64_t *seeds, const double *step_size,
-                           int32_t nleapfrog, int64_t T, int32_t flags) {
+int32_t hmc_enqueue(pfmi_ctx *c, int32_t K, const int64_t *points, const double *x0, const uint64_t *seeds, const double *step_size,
+                    int32_t nleapfrog, int64_t T, int32_t flags, int64_t W, double delta) {
     HmcState &H = c->hmc;
     const TargetDev &Tg = c->target;
     const bool cont = (flags & PFMI_HMC_CONTINUE) != 0, rec = (flags & PFMI_HMC_RECORD_PATH) != 0;
@@ -33,7 +36,8 @@ static int32_t hmc_enqueue(pfmi_ctx *c, int32_t K, const int64_t *points, const 
     PF_CHECK(!cont || (H.have && H.K == K), PFMI_ERR_STATE, "hmc_enqueue: PFMI_HMC_CONTINUE without %d resident chains", K);
     PF_CHECK(!cont || H.kind == 0, PFMI_ERR_STATE, "hmc_enqueue: PFMI_HMC_CONTINUE on the chains of pfmi_nuts_enqueue");
     const int d = c->d;
-    const int64_t rounds = (cont ? 0 : 1) + T * (int64_t)nleapfrog;
+    const int64_t rounds = (cont ? 0 : 1) + (W + T) * (int64_t)nleapfrog;
+    const char *stage = W ? "hmc_adapt" : "hmc", *cstage = W ? "hmc_adapt_closure" : "hmc_closure";
     {   // the fits the chains ask for are successes
         std::vector<int32_t> st((size_t)c->P);
         PF_TRY(d2h(c, st.data(), c->status.p, sizeof(int32_t) * (size_t)c->P));
@@ -56,6 +60,7 @@ static int32_t hmc_enqueue(pfmi_ctx *c, int32_t K, const int64_t *points, const 
         grow(c->hm_draws, sizeof(double) * rows * d);
         for (const DevBuf *b : {&c->hm_lp, &c->hm_acc, &c->hm_de}) grow(*b, sizeof(double) * rows);
         grow(c->hm_div, sizeof(int32_t) * rows);
+        if (W) grow(c->hm_adapt, adapt_bytes(K, W));
         if (rec) {
             grow(c->hm_pX, vec * (size_t)rounds);
             grow(c->hm_pv, vec * (size_t)rounds);
@@ -88,27 +93,31 @@ static int32_t hmc_enqueue(pfmi_ctx *c, int32_t K, const int64_t *points, const 
     for (int k = 0; k < K; ++k) p32[(size_t)k] = (int32_t)points[k];
     PF_TRY(pf_upload(c, c->hm_pts.p, p32.data(), sizeof(int32_t) * (size_t)K));
     PF_TRY(pf_upload(c, c->hm_seeds.p, seeds, sizeof(uint64_t) * (size_t)K));
+    if (cont) PF_TRY(adapt_keep_step_sizes(c));
     PF_TRY(pf_upload(c, c->hm_eps.p, step_size, sizeof(double) * (size_t)K));
     if (!cont) PF_TRY(pf_upload(c, c->hm_x0.p, x0, vec));
+    if (W) PF_TRY(adapt_reserve(c, K, W, step_size, delta));
     H.K = K; H.nleap = nleapfrog; H.record = rec; H.kind = 0; H.finished = true;
-    H.t0 = cont ? H.t0 + H.T : 0; H.T = T;
+    H.t0 = cont ? H.t0 + H.T : W; H.T = T;
+    H.adapting = W > 0;
+    if (W) H.W = W;
     H.rounds = 0; H.columns = 0; H.path_rounds = rec ? rounds : 0;
     H.have = true; H.active = true;                       // from here on, failure paths drain (pfmi_hmc_enqueue)
     if (!cont) PF_TRY(pf_launch_hmc_init(c, c->stream));
     else {
         pf_kernel_begin(c);
         PF_TRY(pf_launch_hmc_step(c, -1, c->stream));
-        pf_kernel_end(c, "hmc");
+        pf_kernel_end(c, stage);
     }
     for (int64_t r = 0; r < rounds; ++r) {
         // the closure on all K trial points (written by the launch before), then the step kernel that consumes its answer
         pf_kernel_begin(c);
         Tg.grad_fn(c->hm_X.as<double>(), d, K, c->hm_out.as<double>(), (void *)c->stream, Tg.grad_user);
-        pf_kernel_end(c, "hmc_closure");
+        pf_kernel_end(c, cstage);
         H.columns += K;
         pf_kernel_begin(c);
         PF_TRY(pf_launch_hmc_step(c, r, c->stream));
-        pf_kernel_end(c, "hmc");
+        pf_kernel_end(c, stage);
         ++H.rounds;
     }
     return PFMI_OK;
@@ -119,7 +128,7 @@ extern "C" {
 int32_t pfmi_hmc_enqueue(pfmi_ctx *c, int32_t K, const int64_t *points, const double *x0, const uint64_t *seeds, const double *step_size,
                          int32_t nleapfrog, int64_t ntransitions, int32_t flags) {
     PF_CTX_MUT(c);
-    const int32_t rc = hmc_enqueue(c, K, points, x0, seeds, step_size, nleapfrog, ntransitions, flags);
+    const int32_t rc = hmc_enqueue(c, K, points, x0, seeds, step_size, nleapfrog, ntransitions, flags, 0, 0.0);
     if (rc != PFMI_OK) {                                  // an error exit drains this ctx's stream and leaves no chains behind
         (void)hipStreamSynchronize(c->stream);
         c->hmc.active = false; c->hmc.have = false;

@@ -44,6 +44,16 @@ inline void results_reset(pfmi_ctx *c) { c->fitted = false; c->elbo_done = false
 void stream_abandon(pfmi_ctx *c);          // drain and forget a streaming call that was never waited for
 void lbc_abandon(pfmi_ctx *c);             // the same for a packed closure optimisation
 void hmc_forget(pfmi_ctx *c);              // drain an HMC call that was never waited for and forget the chains (api_hmc.hip)
+// ---- api_hmc.hip, api_nuts.hip: the enqueues behind the plain and the adaptive entry points (api_adapt.hip).  W = 0: a plain run.
+// W >= 1: a fresh run whose first W transitions adapt the step size towards the acceptance `delta` and record no rows.
+int32_t hmc_enqueue(pfmi_ctx *c, int32_t K, const int64_t *points, const double *x0, const uint64_t *seeds, const double *step_size,
+                    int32_t nleapfrog, int64_t T, int32_t flags, int64_t W, double delta);
+int32_t nuts_enqueue(pfmi_ctx *c, int32_t K, const int64_t *points, const double *x0, const uint64_t *seeds, const double *step_size,
+                     int32_t max_depth, int64_t T, int32_t flags, int64_t W, double delta);
+int32_t adapt_reserve(pfmi_ctx *c, int32_t K, int64_t W, const double *step_size, double delta);   // api_adapt.hip: states and traces of a fresh adaptive run
+size_t adapt_bytes(int32_t K, int64_t W);
+// a plain CONTINUE is about to replace hm_eps: keep the adaptive run's final step sizes for pfmi_adapt_get (stream-ordered copy, once)
+int32_t adapt_keep_step_sizes(pfmi_ctx *c);
 int32_t ensure_pinned(pfmi_ctx *c, size_t x_bytes, size_t lp_bytes);
 
 // ---- api_inputs.hip

@@ -20,12 +20,12 @@ static int32_t nuts_issue_rounds(pfmi_ctx *c) {
     while (!H.finished && H.issued < H.max_rounds && H.issued - H.seen < PF_NUTS_WINDOW) {
         pf_kernel_begin(c);
         Tg.grad_fn(c->hm_X.as<double>(), c->d, H.K, c->hm_out.as<double>(), (void *)c->stream, Tg.grad_user);
-        pf_kernel_end(c, "nuts_closure");
+        pf_kernel_end(c, H.adapting ? "nuts_adapt_closure" : "nuts_closure");
         H.columns += H.K;
         const int64_t prow = H.issued++;
         pf_kernel_begin(c);
         PF_TRY(pf_launch_nuts_step(c, H.issued, prow, false, c->stream));
-        pf_kernel_end(c, "nuts");
+        pf_kernel_end(c, H.adapting ? "nuts_adapt" : "nuts");
     }
     if (!H.finished && H.issued >= H.max_rounds && H.seen >= H.issued) H.finished = true;      // the hard cap: a stuck flag cannot loop forever
     return PFMI_OK;
@@ -51,8 +51,8 @@ static int32_t nuts_drain(pfmi_ctx *c) {                  // pump to the end (ev
     return PFMI_OK;
 }
 
-static int32_t nuts_enqueue(pfmi_ctx *c, int32_t K, const int64_t *points, const double *x0, const uint64_t *seeds, const double *step_size,
-                            int32_t max_depth, int64_t T, int32_t flags) {
+int32_t nuts_enqueue(pfmi_ctx *c, int32_t K, const int64_t *points, const double *x0, const uint64_t *seeds, const double *step_size,
+                     int32_t max_depth, int64_t T, int32_t flags, int64_t W, double delta) {
     HmcState &H = c->hmc;
     const TargetDev &Tg = c->target;
     const bool cont = (flags & PFMI_NUTS_CONTINUE) != 0, rec = (flags & PFMI_NUTS_RECORD_PATH) != 0;
@@ -73,9 +73,9 @@ static int32_t nuts_enqueue(pfmi_ctx *c, int32_t K, const int64_t *points, const
     PF_CHECK(!cont || H.kind == 1, PFMI_ERR_STATE, "nuts_enqueue: PFMI_NUTS_CONTINUE on the chains of pfmi_hmc_enqueue");
     PF_CHECK(!cont || H.md_alloc >= max_depth, PFMI_ERR_ARG, "nuts_enqueue: PFMI_NUTS_CONTINUE with max_depth %d above the chains' %d", max_depth,
              H.md_alloc);
-    PF_CHECK((double)T * 1024.0 < 2147483648.0, PFMI_ERR_UNSUPPORTED, "nuts_enqueue: %lld transitions in one call", (long long)T);
+    PF_CHECK(((double)W + (double)T) * 1024.0 < 2147483648.0, PFMI_ERR_UNSUPPORTED, "nuts_enqueue: %lld transitions in one call", (long long)(W + T));
     const int d = c->d;
-    const int64_t rounds = (cont ? 0 : 1) + T * (((int64_t)1 << max_depth) - 1);
+    const int64_t rounds = (cont ? 0 : 1) + (W + T) * (((int64_t)1 << max_depth) - 1);
     {   // the fits the chains ask for are successes
         std::vector<int32_t> st((size_t)c->P);
         PF_TRY(d2h(c, st.data(), c->status.p, sizeof(int32_t) * (size_t)c->P));
@@ -99,6 +99,7 @@ static int32_t nuts_enqueue(pfmi_ctx *c, int32_t K, const int64_t *points, const
         grow(c->hm_draws, sizeof(double) * rows * d);
         for (const DevBuf *b : {&c->hm_lp, &c->hm_acc, &c->hm_de}) grow(*b, sizeof(double) * rows);
         for (const DevBuf *b : {&c->hm_div, &c->nt_depth, &c->nt_nleap}) grow(*b, sizeof(int32_t) * rows);
+        if (W) grow(c->hm_adapt, adapt_bytes(K, W));
         if (rec) {
             grow(c->hm_pX, vec * (size_t)rounds);
             grow(c->hm_pv, vec * (size_t)rounds);
@@ -139,12 +140,16 @@ static int32_t nuts_enqueue(pfmi_ctx *c, int32_t K, const int64_t *points, const
     for (int k = 0; k < K; ++k) p32[(size_t)k] = (int32_t)points[k];
     PF_TRY(pf_upload(c, c->hm_pts.p, p32.data(), sizeof(int32_t) * (size_t)K));
     PF_TRY(pf_upload(c, c->hm_seeds.p, seeds, sizeof(uint64_t) * (size_t)K));
+    if (cont) PF_TRY(adapt_keep_step_sizes(c));
     PF_TRY(pf_upload(c, c->hm_eps.p, step_size, sizeof(double) * (size_t)K));
     if (!cont) PF_TRY(pf_upload(c, c->hm_x0.p, x0, vec));
+    if (W) PF_TRY(adapt_reserve(c, K, W, step_size, delta));
+    H.adapting = W > 0;
+    if (W) H.W = W;
     H.K = K; H.nleap = 0; H.record = rec; H.kind = 1;
     H.max_depth = max_depth;
     if (!cont) H.md_alloc = max_depth;                    // (a CONTINUE never asks for more checkpoints than the chains were given)
-    H.t0 = cont ? H.t0 + H.T : 0; H.T = T;
+    H.t0 = cont ? H.t0 + H.T : W; H.T = T;
     H.rounds = 0; H.columns = 0; H.path_rounds = rec ? rounds : 0;
     H.issued = 0; H.seen = 0; H.max_rounds = rounds; H.finished = false;
     H.have = true; H.active = true;                       // from here on, failure paths drain (pfmi_nuts_enqueue)
@@ -164,7 +169,7 @@ extern "C" {
 int32_t pfmi_nuts_enqueue(pfmi_ctx *c, int32_t K, const int64_t *points, const double *x0, const uint64_t *seeds, const double *step_size,
                           int32_t max_depth, int64_t ntransitions, int32_t flags) {
     PF_CTX_MUT(c);
-    const int32_t rc = nuts_enqueue(c, K, points, x0, seeds, step_size, max_depth, ntransitions, flags);
+    const int32_t rc = nuts_enqueue(c, K, points, x0, seeds, step_size, max_depth, ntransitions, flags, 0, 0.0);
     if (rc != PFMI_OK) {                                  // an error exit drains this ctx's stream and leaves no chains behind
         (void)hipStreamSynchronize(c->stream);
         c->hmc.active = false; c->hmc.have = false; c->hmc.finished = true;

@@ -25,6 +25,7 @@
 // chain's output depends on nothing but its own inputs.
 #include "pfmi_common.h"
 #include "hmc_rows.h"
+#include "adapt.h"
 #include <float.h>
 
 #define HM_NT 256                      // threads per chain (4 waves)
@@ -46,7 +47,7 @@ struct HmArgs {
     int64_t round;                     // index of this launch among the call's closure rounds (row of the recorded path)
     const int32_t *pts;                // [K] fit point of each chain
     const uint64_t *seeds;             // [K]
-    const double *eps;                 // [K]
+    double *eps;                       // [K]; a warm-up launch that ends a transition writes the chain's next step size
     const double *x0;                  // [K][d] (init kernel)
     double *X;                         // closure input: d x K column-major
     const double *out;                 // closure output: logp [K], then grad [K][d]
@@ -56,6 +57,7 @@ struct HmArgs {
     int32_t *rdiv;
     double *pX, *pout, *pv;            // PFMI_HMC_RECORD_PATH: [rounds][K][d], [rounds][K + K d], [rounds][K][d]
     const double *vh, *tmat, *vchol, *sqa;
+    PfAdapt *ad;                       // adaptive runs: [K] adaptation states, then the warm-up traces PfWarmRow [K][t0]
 };
 
 __global__ __launch_bounds__(HM_NT) void pf_hmc_init_kernel(HmArgs A) {
@@ -70,8 +72,10 @@ __global__ __launch_bounds__(HM_NT) void pf_hmc_init_kernel(HmArgs A) {
     }
 }
 
-template <int KPAD, bool RES>
-__global__ __launch_bounds__(HM_NT) void pf_hmc_step_kernel(HmArgs A) {
+// ADAPT (pf_hmc_warm_kernel): transitions t < t0 are the warm-up.  They write no row but a PfWarmRow, and thread 0 applies pf_adapt_update
+// between recording transition t and opening transition t + 1, whose first half kick and drift already use the new step size.
+template <int KPAD, bool RES, bool ADAPT>
+__device__ __forceinline__ void hm_step_body(const HmArgs &A) {
     extern __shared__ __attribute__((aligned(32))) double sVh[];      // RES: the chain's factor rows [d][KPAD]
     constexpr int NVM = KPAD + 4;                        // KPAD sums + one rider, padded to the multiple of 4 pf_block_sum_mv takes
     __shared__ double red[2 * HM_NW * NVM];
@@ -84,7 +88,7 @@ __global__ __launch_bounds__(HM_NT) void pf_hmc_step_kernel(HmArgs A) {
     const double *gVh = A.vh + (size_t)p * d * KPAD, *T = A.tmat + (size_t)p * KPAD * KPAD, *Vc = A.vchol + (size_t)p * KPAD * KPAD;
     const double *sqa = A.sqa + (size_t)p * d;
     double *X = A.X + kd, *x = A.x + kd, *wg = A.wg + kd, *wt = A.wt + kd, *v = A.v + kd;
-    const double eps = A.eps[k];
+    double eps = A.eps[k];
     const uint64_t seed = A.seeds[k];
     // RES: a thread reads only the rows it owns (i = tid, tid + 256, ...), in every pass.  The first pass over the factor reads them from
     // HBM and leaves them in LDS; the later ones (three more per launch) read the thread's own copy: no staging pass, no barrier.
@@ -157,18 +161,34 @@ __global__ __launch_bounds__(HM_NT) void pf_hmc_step_kernel(HmArgs A) {
             const double u = (double)(pf_rand_u64(seed, (uint64_t)S.t, PF_RNG_STREAM_HMC_ACCEPT) >> 11) * 0x1p-53;
             const bool acc = u < a;
             const int64_t row = S.t - A.t0;
-            double *dr = A.draws + ((size_t)k * A.T + row) * d;
+            const bool warm = ADAPT && row < 0;
+            double *dr = A.draws + ((size_t)k * A.T + (warm ? 0 : row)) * d;
             for (int i = tid; i < d; i += HM_NT) {
                 double xi = x[i];
                 if (acc) { xi = X[i]; x[i] = xi; wg[i] = wt[i]; }
-                dr[i] = xi;
+                if (!warm) dr[i] = xi;
             }
             if (acc) S.lp = lpt;
-            if (tid == 0) {
+            if (tid == 0 && !warm) {
                 const size_t r = (size_t)k * A.T + row;
                 A.rlp[r] = S.lp; A.racc[r] = a; A.rde[r] = isfinite(dH) ? dH : DBL_MAX; A.rdiv[r] = div ? 1 : 0;
             }
             ++S.t; S.bad = 0;
+            if constexpr (ADAPT) {
+                if (warm) {
+                    __shared__ double sNext;
+                    if (tid == 0) {
+                        PfWarmRow *tr = reinterpret_cast<PfWarmRow *>(A.ad + K) + (size_t)k * A.t0 + (S.t - 1);
+                        tr->eps = eps; tr->acc = a; tr->div = div ? 1 : 0; tr->nleap = A.nleap;
+                        PfAdapt Ad = A.ad[k];
+                        const double le = pf_adapt_update(Ad, a);
+                        const double en = pf_adapt_pick(Ad, S.t < A.t0 ? le : Ad.leb, eps);
+                        A.ad[k] = Ad; A.eps[k] = en; sNext = en;
+                    }
+                    __syncthreads();
+                    eps = sNext;
+                }
+            }
             if (S.t < A.t_end) open = true; else S.i = HM_OPEN;
         }
     }
@@ -229,6 +249,12 @@ __global__ __launch_bounds__(HM_NT) void pf_hmc_step_kernel(HmArgs A) {
     if (tid == 0) A.st[k] = S;
 }
 
+template <int KPAD, bool RES>
+__global__ __launch_bounds__(HM_NT) void pf_hmc_step_kernel(HmArgs A) { hm_step_body<KPAD, RES, false>(A); }
+
+template <int KPAD, bool RES>
+__global__ __launch_bounds__(HM_NT) void pf_hmc_warm_kernel(HmArgs A) { hm_step_body<KPAD, RES, true>(A); }
+
 // ---------------------------------------------------------------------------------------------------
 static HmArgs hm_args(pfmi_ctx *c, int64_t round) {
     const HmcState &H = c->hmc;
@@ -243,6 +269,7 @@ static HmArgs hm_args(pfmi_ctx *c, int64_t round) {
     A.rdiv = c->hm_div.as<int32_t>();
     A.pX = c->hm_pX.as<double>(); A.pout = c->hm_pout.as<double>(); A.pv = c->hm_pv.as<double>();
     A.vh = c->vh.as<double>(); A.tmat = c->tmat.as<double>(); A.vchol = c->vchol.as<double>(); A.sqa = c->sqrt_alpha.as<double>();
+    A.ad = c->hm_adapt.as<PfAdapt>();
     return A;
 }
 
@@ -256,14 +283,15 @@ int32_t pf_launch_hmc_init(pfmi_ctx *c, hipStream_t s) {
     return PFMI_OK;
 }
 
-template <int KPAD, bool RES>
+template <int KPAD, bool RES, bool ADAPT>
 static int32_t hm_launch(pfmi_ctx *c, const HmArgs &A, hipStream_t s) {
     const size_t lds = RES ? (size_t)A.d * KPAD * sizeof(double) : 0;
-    if (RES) PF_TRY(pf_raise_lds_limit(c, reinterpret_cast<const void *>(&pf_hmc_step_kernel<KPAD, RES>), HM_LDS_RES));
+    auto *kern = ADAPT ? &pf_hmc_warm_kernel<KPAD, RES> : &pf_hmc_step_kernel<KPAD, RES>;
+    if (RES) PF_TRY(pf_raise_lds_limit(c, reinterpret_cast<const void *>(kern), HM_LDS_RES));
     char name[32];
-    snprintf(name, sizeof name, "hmc:%d:%s", KPAD, RES ? "res" : "stream");
+    snprintf(name, sizeof name, "%s:%d:%s", ADAPT ? "hmc_adapt" : "hmc", KPAD, RES ? "res" : "stream");
     ++c->hmc_plans[name];
-    hipLaunchKernelGGL((pf_hmc_step_kernel<KPAD, RES>), dim3(A.K), dim3(HM_NT), lds, s, A);
+    hipLaunchKernelGGL(kern, dim3(A.K), dim3(HM_NT), lds, s, A);
     return PFMI_OK;
 }
 
@@ -283,7 +311,8 @@ int32_t pf_launch_hmc_step(pfmi_ctx *c, int64_t round, hipStream_t s) {
     const bool res = pf_hmc_resident(A.d, c->kpad);
     int32_t rc = PFMI_OK;
     const bool ok = pf_dispatch_kpad<4, 8, 12, 16, 20, 32, 64>(c->kpad, [&](auto KP) {
-        rc = res ? hm_launch<KP(), true>(c, A, s) : hm_launch<KP(), false>(c, A, s);
+        if (c->hmc.adapting) rc = res ? hm_launch<KP(), true, true>(c, A, s) : hm_launch<KP(), false, true>(c, A, s);
+        else rc = res ? hm_launch<KP(), true, false>(c, A, s) : hm_launch<KP(), false, false>(c, A, s);
     });
     PF_CHECK(ok, PFMI_ERR_UNSUPPORTED, "unsupported kpad %d", c->kpad);
     PF_TRY(rc);

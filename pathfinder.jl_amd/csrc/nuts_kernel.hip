@@ -33,6 +33,7 @@
 // the two progress counters.  A chain's output depends on nothing but its own inputs.
 #include "pfmi_common.h"
 #include "hmc_rows.h"
+#include "adapt.h"
 #include <float.h>
 
 #define NT_NT 256                      // threads per chain (4 waves)
@@ -57,12 +58,13 @@ struct NtArgs {
     int64_t round, prow;               // number of this launch (progress word); row of the recorded path
     const int32_t *pts;
     const uint64_t *seeds;
-    const double *eps;
+    double *eps;                       // [K]; a warm-up launch that ends a transition writes the chain's next step size
     const double *x0;
     double *X;                         // closure input: d x K column-major
     const double *out;                 // closure output: logp [K], then grad [K][d]
     double *blk;                       // [K][NT_VECS + 2 max_depth][d]: the chain's vectors (the slots below), then its checkpoints
     NtChain *st;
+    PfAdapt *ad;                       // adaptive runs: [K] adaptation states, then the warm-up traces PfWarmRow [K][t0] (read by thread 0 only)
     double *draws, *rlp, *racc, *rde;  // records [K][T][d], [K][T] (shared with static HMC)
     int32_t *rdiv, *rdepth, *rnleap;   // [K][T]
     double *pX, *pout, *pv;            // PFMI_NUTS_RECORD_PATH
@@ -102,15 +104,22 @@ __global__ __launch_bounds__(NT_NT) void pf_nuts_init_kernel(NtArgs A) {
     }
 }
 
-template <int KPAD, bool RES>
-__global__ __launch_bounds__(NT_NT) void pf_nuts_step_kernel(NtArgs A_) {
-    // The arguments are read where they are used, through the kernel-argument segment itself (A_ is its first and only entry): as a
-    // by-value parameter all 78 dwords are loaded on entry and stay in scalar registers until their one use.
+// ADAPT (pf_nuts_warm_kernel): transitions t < t0 are the warm-up.  They write no row but a PfWarmRow, and thread 0 applies pf_adapt_update
+// between recording transition t and opening transition t + 1, whose first half kick and drift already use the new step size.
+template <int KPAD, bool RES, bool ADAPT>
+__device__ __forceinline__ void nt_step_body(const NtArgs &A_) {
+    // The arguments are read where they are used, through the kernel-argument segment itself (A_ is the kernel's first and only entry): as a
+    // by-value parameter all 80 dwords are loaded on entry and stay in scalar registers until their one use.
 #if defined(__HIP_DEVICE_COMPILE__)
     const NtArgs &A = *(const NtArgs *)__builtin_amdgcn_kernarg_segment_ptr();
 #else
     const NtArgs &A = A_;
 #endif
+    // an adaptive run records no path (its flags are 0): the warm kernel carries none of that code and none of its addresses
+    auto rec = [&]() -> int {
+        if constexpr (ADAPT) return 0;
+        else return A.record;
+    };
     extern __shared__ __attribute__((aligned(32))) double sVh[];      // RES: the chain's factor rows [d][KPAD]
     constexpr int NVM = KPAD + 4;                        // KPAD sums + one rider (pf_block_sum_mv takes multiples of 4)
     constexpr int NRED = NVM > NT_NDOT ? NVM : NT_NDOT;
@@ -131,13 +140,26 @@ __global__ __launch_bounds__(NT_NT) void pf_nuts_step_kernel(NtArgs A_) {
     if (!(idle_in && !A.reopen)) {
         const int p = sPt;
         const size_t kd = (size_t)k * d;
-        const double *gVh = A.vh + (size_t)p * d * KPAD, *T = A.tmat + (size_t)p * KPAD * KPAD, *Vc = A.vchol + (size_t)p * KPAD * KPAD;
-        const double *sqa = A.sqa + (size_t)p * d;
+        // In the warm kernel the base addresses that live through the whole launch pass through an empty asm, which makes each an opaque
+        // value in scalar registers.  Left as the result of the merged eight-dword argument load they are a tuple the register allocator
+        // splits around the update and REMATERIALISES, and the spill slot it leaves behind (never read, never written) would still make
+        // every wave reserve scratch; an opaque value is moved into a lane of a vector register instead, as in the plain kernel, which
+        // keeps its loads as they are.
+        auto karg = [&](auto *const &f) {
+            using P = std::remove_cv_t<std::remove_reference_t<decltype(f)>>;
+            if constexpr (ADAPT) {
+                uint64_t u = (uint64_t)f;
+                asm volatile("" : "+s"(u));
+                return (P)u;
+            } else return f;
+        };
+        const double *gVh = karg(A.vh) + (size_t)p * d * KPAD, *T = karg(A.tmat) + (size_t)p * KPAD * KPAD, *Vc = karg(A.vchol) + (size_t)p * KPAD * KPAD;
+        const double *sqa = karg(A.sqa) + (size_t)p * d;
         double *X = A.X + kd;
         double *B = A.blk + (size_t)k * A.nslot * d;
         const int ckv = NT_VECS, ckr = NT_VECS + (A.nslot - NT_VECS) / 2;        // first checkpoint slots
 #define V_(slot, i) B[(size_t)(slot) * d + (i)]
-        const double eps = sEps;
+        double eps = sEps;
         const uint64_t seed = sSeed;
         bool staged = false;
         auto vrow = [&](int i) -> const double * {
@@ -145,13 +167,14 @@ __global__ __launch_bounds__(NT_NT) void pf_nuts_step_kernel(NtArgs A_) {
             else return gVh + (size_t)i * KPAD;
         };
         bool open = idle_in, drift = false;
+        int wend = 0;                                        // ADAPT: this launch ended a warm-up transition (2: a divergent one)
         int bslot = -1;                                      // the drift's base: a slot, or (-1) the trial point itself
         int ndir = S.dir;                                    // direction of the leapfrog step this launch starts
         if (!idle_in) {
             const double lpt = A.out[k];
             const double *g = A.out + K + kd;
             const size_t pr = ((size_t)A.prow * K + k);
-            if (A.record) {                                  // what the closure saw and what it answered, before X is rewritten
+            if (rec()) {                                  // what the closure saw and what it answered, before X is rewritten
                 double *pX = A.pX + pr * d, *pout = A.pout + (size_t)A.prow * ((size_t)K * (d + 1));
                 for (int i = tid; i < d; i += NT_NT) { pX[i] = X[i]; pout[K + kd + i] = g[i]; }
                 if (tid == 0) pout[k] = lpt;
@@ -197,7 +220,7 @@ __global__ __launch_bounds__(NT_NT) void pf_nuts_step_kernel(NtArgs A_) {
                 S.lp = badg ? -DBL_MAX : lpt;
                 S.dead = badg ? 1 : 0;
                 open = true;
-                if (A.record) {
+                if (rec()) {
                     double *pv = A.pv + pr * d;
                     for (int i = tid; i < d; i += NT_NT) pv[i] = 0.0;
                     if (tid == 0) {
@@ -213,7 +236,7 @@ __global__ __launch_bounds__(NT_NT) void pf_nuts_step_kernel(NtArgs A_) {
                 const bool last = n == (1 << j) - 1, store = (n & 1) == 0;
                 const double hk = (dir > 0 ? 0.5 : -0.5) * eps;
                 const int vo = NT_VE + (dir > 0 ? 0 : 1);                 // the momentum at the tree's other end
-                double *pv = A.record ? A.pv + pr * d : nullptr;
+                double *pv = rec() ? A.pv + pr * d : nullptr;
                 double w[NT_NDOT];
 #pragma unroll
                 for (int q = 0; q < NT_NDOT; ++q) w[q] = 0.0;
@@ -268,7 +291,7 @@ __global__ __launch_bounds__(NT_NT) void pf_nuts_step_kernel(NtArgs A_) {
                     }
                 }
                 const bool end = div || turn || (complete && (fturn || mstop));
-                if (A.record && tid == 0) {
+                if (rec() && tid == 0) {
                     pfmi_nuts_event E;
                     E.t = (int32_t)S.t; E.j = j; E.n = n; E.dir = dir; E.leaf = leaf;
                     E.flags = (div ? PFMI_NUTS_EV_DIVERGENT : 0) | (turn ? PFMI_NUTS_EV_SUBTREE_TURN : 0) | (sel ? PFMI_NUTS_EV_LEAF_TAKEN : 0) |
@@ -279,7 +302,9 @@ __global__ __launch_bounds__(NT_NT) void pf_nuts_step_kernel(NtArgs A_) {
                 }
                 // ---- update the states
                 const int64_t row = S.t - A.t0;
-                double *dr = A.draws + ((size_t)k * A.T + row) * d;
+                bool warm = false;                               // (a scalar: S comes through LDS, so row < 0 alone is a lane mask)
+                if constexpr (ADAPT) warm = __builtin_amdgcn_readfirstlane(row < 0 ? 1 : 0) != 0;
+                double *dr = karg(A.draws) + ((size_t)k * A.T + (warm ? 0 : row)) * d;
                 const int en = dir > 0 ? 1 : 0;
                 for (int i = tid; i < d; i += NT_NT) {
                     double xsi = V_(NT_XS, i), wsi = V_(NT_WS, i);
@@ -290,11 +315,12 @@ __global__ __launch_bounds__(NT_NT) void pf_nuts_step_kernel(NtArgs A_) {
                         V_(NT_XE + en, i) = X[i]; V_(NT_VE + en, i) = V_(NT_V, i); V_(NT_WE + en, i) = V_(NT_WT, i);
                         if (tsel) { xci = xsi; wci = wsi; V_(NT_XC, i) = xci; V_(NT_WC, i) = wci; }
                     }
-                    if (end) { V_(NT_X, i) = xci; V_(NT_WG, i) = wci; dr[i] = xci; }
+                    if (end) { V_(NT_X, i) = xci; V_(NT_WG, i) = wci; if (!warm) dr[i] = xci; }
                 }
                 if (end) {
                     S.lp = S.lpc;
-                    if (tid == 0) {
+                    if (warm) wend = div ? 2 : 1;
+                    if (tid == 0 && !warm) {
                         const size_t r = (size_t)k * A.T + row;
                         const double de = S.Hc - S.H0;
                         A.rlp[r] = S.lp; A.racc[r] = S.sacc / (double)S.nleaf; A.rde[r] = isfinite(de) ? de : DBL_MAX; A.rdiv[r] = div ? 1 : 0;
@@ -322,6 +348,23 @@ __global__ __launch_bounds__(NT_NT) void pf_nuts_step_kernel(NtArgs A_) {
                     for (int i = tid; i < d; i += NT_NT) V_(NT_V, i) = fma(hk, V_(NT_WT, i), V_(NT_V, i));
                     drift = true;
                 }
+            }
+        }
+        if constexpr (ADAPT) {
+            // ---- the warm-up transition S.t - 1 has ended: its trace, the update, the step size of the transition that opens below
+            // (here and not in the branch above: fewer uniform values are live beside the constants of sqrt and exp)
+            if (wend) {
+                if (tid == 0) {
+                    const double a = S.sacc / (double)S.nleaf;
+                    PfWarmRow *tr = reinterpret_cast<PfWarmRow *>(A.ad + K) + (size_t)k * A.t0 + (S.t - 1);
+                    tr->eps = eps; tr->acc = a; tr->div = wend - 1; tr->nleap = S.nleaf;
+                    PfAdapt Ad = A.ad[k];
+                    const double le = pf_adapt_update(Ad, a);
+                    const double en = pf_adapt_pick(Ad, S.t < A.t0 ? le : Ad.leb, eps);
+                    A.ad[k] = Ad; A.eps[k] = en; sEps = en;
+                }
+                __syncthreads();
+                eps = sEps;
             }
         }
         double vv0 = 0.0;
@@ -396,6 +439,12 @@ __global__ __launch_bounds__(NT_NT) void pf_nuts_step_kernel(NtArgs A_) {
     }
 }
 
+template <int KPAD, bool RES>
+__global__ __launch_bounds__(NT_NT) void pf_nuts_step_kernel(NtArgs A_) { nt_step_body<KPAD, RES, false>(A_); }
+
+template <int KPAD, bool RES>
+__global__ __launch_bounds__(NT_NT) void pf_nuts_warm_kernel(NtArgs A_) { nt_step_body<KPAD, RES, true>(A_); }
+
 // ---------------------------------------------------------------------------------------------------
 static NtArgs nt_args(pfmi_ctx *c, int64_t round, int64_t prow, bool reopen) {
     const HmcState &H = c->hmc;
@@ -411,6 +460,7 @@ static NtArgs nt_args(pfmi_ctx *c, int64_t round, int64_t prow, bool reopen) {
     A.pX = c->hm_pX.as<double>(); A.pout = c->hm_pout.as<double>(); A.pv = c->hm_pv.as<double>(); A.pev = c->nt_pev.as<pfmi_nuts_event>();
     A.ctr = c->nt_ctr.as<int32_t>(); A.h_status = c->nt_status;
     A.vh = c->vh.as<double>(); A.tmat = c->tmat.as<double>(); A.vchol = c->vchol.as<double>(); A.sqa = c->sqrt_alpha.as<double>();
+    A.ad = c->hm_adapt.as<PfAdapt>();
     return A;
 }
 
@@ -423,14 +473,15 @@ int32_t pf_launch_nuts_init(pfmi_ctx *c, hipStream_t s) {
     return PFMI_OK;
 }
 
-template <int KPAD, bool RES>
+template <int KPAD, bool RES, bool ADAPT>
 static int32_t nt_launch(pfmi_ctx *c, const NtArgs &A, hipStream_t s) {
     const size_t lds = RES ? (size_t)A.d * KPAD * sizeof(double) : 0;
-    if (RES) PF_TRY(pf_raise_lds_limit(c, reinterpret_cast<const void *>(&pf_nuts_step_kernel<KPAD, RES>), NT_LDS_RES));
+    auto *kern = ADAPT ? &pf_nuts_warm_kernel<KPAD, RES> : &pf_nuts_step_kernel<KPAD, RES>;
+    if (RES) PF_TRY(pf_raise_lds_limit(c, reinterpret_cast<const void *>(kern), NT_LDS_RES));
     char name[32];
-    snprintf(name, sizeof name, "nuts:%d:%s", KPAD, RES ? "res" : "stream");
+    snprintf(name, sizeof name, "%s:%d:%s", ADAPT ? "nuts_adapt" : "nuts", KPAD, RES ? "res" : "stream");
     ++c->hmc_plans[name];
-    hipLaunchKernelGGL((pf_nuts_step_kernel<KPAD, RES>), dim3(A.K), dim3(NT_NT), lds, s, A);
+    hipLaunchKernelGGL(kern, dim3(A.K), dim3(NT_NT), lds, s, A);
     return PFMI_OK;
 }
 
@@ -457,7 +508,8 @@ int32_t pf_launch_nuts_step(pfmi_ctx *c, int64_t round, int64_t prow, bool reope
     const bool res = pf_hmc_resident(A.d, c->kpad);
     int32_t rc = PFMI_OK;
     const bool ok = pf_dispatch_kpad<4, 8, 12, 16, 20, 32, 64>(c->kpad, [&](auto KP) {
-        rc = res ? nt_launch<KP(), true>(c, A, s) : nt_launch<KP(), false>(c, A, s);
+        if (c->hmc.adapting) rc = res ? nt_launch<KP(), true, true>(c, A, s) : nt_launch<KP(), false, true>(c, A, s);
+        else rc = res ? nt_launch<KP(), true, false>(c, A, s) : nt_launch<KP(), false, false>(c, A, s);
     });
     PF_CHECK(ok, PFMI_ERR_UNSUPPORTED, "unsupported kpad %d", c->kpad);
     PF_TRY(rc);

@@ -119,6 +119,10 @@ struct HmcState {
     int max_depth = 0, md_alloc = 0;                  // the stop rule of the last call; the depth the chains' checkpoints were made for
     int64_t issued = 0, seen = 0, max_rounds = 0;     // rounds launched / last round whose progress word the host has read / hard cap
     bool finished = true;         // every chain has made its transitions (or the cap is reached and seen)
+    // pfmi_hmc_adapt_enqueue / pfmi_nuts_adapt_enqueue (api_adapt.hip): transitions 0 .. W - 1 were the warm-up, t0 = W
+    bool adapting = false;        // the call in flight launches the warm kernels (a later plain CONTINUE does not)
+    int64_t W = 0;                // > 0: the adaptation states and the warm-up traces [K][W] are resident (pfmi_adapt_get)
+    bool eps_kept = false;        // a plain CONTINUE has replaced hm_eps: the adaptive run's final step sizes are the copy in hm_adapt
 };
 
 struct pfmi_ctx {
@@ -283,6 +287,7 @@ struct pfmi_ctx {
     DevBuf hm_X, hm_out, hm_x0, hm_x, hm_wg, hm_wt, hm_v, hm_st, hm_pts, hm_seeds, hm_eps;
     DevBuf hm_draws, hm_lp, hm_acc, hm_de, hm_div;      // the last call's records [K][T][d], [K][T]
     DevBuf hm_pX, hm_pout, hm_pv;                       // PFMI_HMC_RECORD_PATH: every round's X, closure output and v
+    DevBuf hm_adapt;                                    // adaptive runs: PfAdapt [K], PfWarmRow [K][W], then [K] final step sizes (adapt.h, api_adapt.hip)
     DevBuf nt_vec, nt_st, nt_depth, nt_nleap, nt_pev, nt_ctr;   // NUTS: the chains' vectors and checkpoints, their scalars, statistics, events
     int64_t *nt_status = nullptr; // page-locked: round << 32 | chains still running, written by the last workgroup of each NUTS round
     std::map<std::string, int64_t> hmc_plans;           // step launches per plan "hmc:<KPAD>:<res|stream>" (pfmi_kernel_time)

@@ -1396,6 +1396,64 @@ function nuts_stats(b::Batch)
     return (rounds = r[], closure_columns = n[])
 end
 
+# ---- device-resident warm-up: `nwarmup` transitions whose step sizes the device adapts after every transition (dual averaging, as
+# AdvancedHMC's StepSizeAdaptor and DynamicHMC do), then `ntransitions` sampling transitions, in ONE enqueue (include/pfmi.h).
+function _adapt_get(b::Batch, K::Integer, W::Integer)
+    ϵ = Vector{Float64}(undef, K); et = Matrix{Float64}(undef, W, K); at = similar(et)
+    dv = Matrix{Int32}(undef, W, K); nl = similar(dv); st = Vector{Int32}(undef, K)
+    check(ccall((:pfmi_adapt_get, libpfmi), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}),
+                b.eng.ptr, ϵ, et, at, dv, nl, st))
+    return (step_size = ϵ, eps_trace = et, accept_trace = at, divergent = dv, n_leapfrog = nl, status = st)
+end
+"""
+    hmc_adapt(b::Batch, points, x0, seeds, step_size0; nleapfrog = 8, nwarmup, ntransitions, target_accept = 0.8)
+
+`hmc` with `nwarmup` adaptive warm-up transitions in front.  Returns `hmc`'s rows of the `ntransitions` sampling transitions and `warmup`:
+the final `step_size` (K), `eps_trace`, `accept_trace`, `divergent`, `n_leapfrog` `(nwarmup, K)` and `status` (K).
+"""
+function hmc_adapt(b::Batch, points::AbstractVector{<:Integer}, x0::AbstractMatrix{Float64}, seeds::AbstractVector{UInt64},
+                   step_size0::AbstractVector{Float64}; nleapfrog::Integer = 8, nwarmup::Integer, ntransitions::Integer,
+                   target_accept::Real = 0.8)
+    _live(b.eng, b.gen)
+    K = length(points); d = b.dim; T = Int(ntransitions); W = Int(nwarmup)
+    (length(seeds) == K && length(step_size0) == K && size(x0) == (d, K)) || throw(ArgumentError("hmc_adapt: K values per argument"))
+    pts = Vector{Int64}(points); X0 = Matrix{Float64}(x0); sd = Vector{UInt64}(seeds); ϵ = Vector{Float64}(step_size0)
+    check(ccall((:pfmi_hmc_adapt_enqueue, libpfmi), Int32,
+                (Ptr{Cvoid}, Int32, Ptr{Int64}, Ptr{Float64}, Ptr{UInt64}, Ptr{Float64}, Int32, Int64, Int64, Float64, Int32),
+                b.eng.ptr, K, pts, X0, sd, ϵ, nleapfrog, W, T, Float64(target_accept), Int32(0)))
+    check(ccall((:pfmi_hmc_wait, libpfmi), Int32, (Ptr{Cvoid},), b.eng.ptr))
+    draws = Array{Float64}(undef, d, T, K)
+    lp = Matrix{Float64}(undef, T, K); acc = similar(lp); de = similar(lp); dv = Matrix{Int32}(undef, T, K)
+    check(ccall((:pfmi_hmc_get, libpfmi), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+                b.eng.ptr, draws, lp, acc, de, dv))
+    return (draws = draws, logp = lp, accept_prob = acc, energy_error = de, divergent = dv, warmup = _adapt_get(b, K, W))
+end
+"""
+    nuts_adapt(b::Batch, points, x0, seeds, step_size0; max_depth = 10, nwarmup, ntransitions, target_accept = 0.8)
+
+`nuts` with `nwarmup` adaptive warm-up transitions in front: `nuts`'s rows of the sampling transitions and `warmup` as `hmc_adapt` gives it.
+"""
+function nuts_adapt(b::Batch, points::AbstractVector{<:Integer}, x0::AbstractMatrix{Float64}, seeds::AbstractVector{UInt64},
+                    step_size0::AbstractVector{Float64}; max_depth::Integer = 10, nwarmup::Integer, ntransitions::Integer,
+                    target_accept::Real = 0.8)
+    _live(b.eng, b.gen)
+    K = length(points); d = b.dim; T = Int(ntransitions); W = Int(nwarmup)
+    (length(seeds) == K && length(step_size0) == K && size(x0) == (d, K)) || throw(ArgumentError("nuts_adapt: K values per argument"))
+    pts = Vector{Int64}(points); X0 = Matrix{Float64}(x0); sd = Vector{UInt64}(seeds); ϵ = Vector{Float64}(step_size0)
+    check(ccall((:pfmi_nuts_adapt_enqueue, libpfmi), Int32,
+                (Ptr{Cvoid}, Int32, Ptr{Int64}, Ptr{Float64}, Ptr{UInt64}, Ptr{Float64}, Int32, Int64, Int64, Float64, Int32),
+                b.eng.ptr, K, pts, X0, sd, ϵ, max_depth, W, T, Float64(target_accept), Int32(0)))
+    check(ccall((:pfmi_nuts_wait, libpfmi), Int32, (Ptr{Cvoid},), b.eng.ptr))
+    draws = Array{Float64}(undef, d, T, K)
+    lp = Matrix{Float64}(undef, T, K); acc = similar(lp); de = similar(lp); dv = Matrix{Int32}(undef, T, K)
+    check(ccall((:pfmi_hmc_get, libpfmi), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+                b.eng.ptr, draws, lp, acc, de, dv))
+    depth = Matrix{Int32}(undef, T, K); nleap = Matrix{Int32}(undef, T, K)
+    check(ccall((:pfmi_nuts_get_stats, libpfmi), Int32, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}), b.eng.ptr, depth, nleap))
+    return (draws = draws, logp = lp, accept_prob = acc, energy_error = de, divergent = dv, tree_depth = depth, n_leapfrog = nleap,
+            warmup = _adapt_get(b, K, W))
+end
+
 # ---- chain diagnostics on the device: what summarystats(chns) reports in docs/src/examples/turing.md and initializing-hmc.md
 function _chain_diagnostics(eng::Engine, source::Integer, draws, d::Integer, T::Integer, K::Integer, flags::Integer, len::Integer)
     out = [Vector{Float64}(undef, len) for _ in 1:7]

@@ -55,6 +55,7 @@ SYMBOLS = [
     "pfmi_hmc_enqueue", "pfmi_hmc_wait", "pfmi_hmc_get", "pfmi_hmc_draws_dev", "pfmi_hmc_get_path", "pfmi_hmc_stats",
     "pfmi_chain_diagnostics",
     "pfmi_nuts_enqueue", "pfmi_nuts_pump", "pfmi_nuts_wait", "pfmi_nuts_get_stats", "pfmi_nuts_get_path", "pfmi_nuts_stats",
+    "pfmi_hmc_adapt_enqueue", "pfmi_nuts_adapt_enqueue", "pfmi_adapt_get", "pfmi_host_dual_averaging",
 ]
 
 # declared argument types (entry points not listed here take what the caller wraps by hand)
@@ -81,6 +82,12 @@ ARGTYPES = {
     "pfmi_nuts_get_path": [C.c_void_p, C.c_int64, C.c_int64, _dp, _dp, _dp, C.c_void_p],
     "pfmi_nuts_stats": [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
     "pfmi_chain_diagnostics": [C.c_void_p, C.c_int32, _dp, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp, _dp],
+    "pfmi_hmc_adapt_enqueue": [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), _dp, C.POINTER(C.c_uint64), _dp, C.c_int32, C.c_int64, C.c_int64,
+                               C.c_double, C.c_int32],
+    "pfmi_nuts_adapt_enqueue": [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), _dp, C.POINTER(C.c_uint64), _dp, C.c_int32, C.c_int64, C.c_int64,
+                                C.c_double, C.c_int32],
+    "pfmi_adapt_get": [C.c_void_p, _dp, _dp, _dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
+    "pfmi_host_dual_averaging": [C.c_int64, C.c_double, C.c_double, _dp, _dp, _dp],
 }
 
 

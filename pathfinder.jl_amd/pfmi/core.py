@@ -105,6 +105,7 @@ class Engine:
         self.npoints = None
         self.J = 0
         self._hmc = None                          # (K, T) of the last hmc_enqueue that succeeded
+        self._adapt = None                        # (K, W) of the adaptive run whose traces are resident (adapt_get)
         self.hmc_runs = 0                         # hmc_enqueue calls that succeeded (HMCResult.summary: is a result still the resident run?)
 
     def close(self):
@@ -507,6 +508,8 @@ class Engine:
             self._raise_target_error()
         check(rc)
         self._hmc = (K, int(ntransitions))
+        if not cont:
+            self._adapt = None
         self.hmc_runs += 1
 
     # ---- chain diagnostics (include/pfmi.h: pfmi_chain_diagnostics) ---------------------------------------------------------------
@@ -599,7 +602,54 @@ class Engine:
             self._raise_target_error()
         check(rc)
         self._hmc = (K, int(ntransitions))
+        if not cont:
+            self._adapt = None
         self.hmc_runs += 1
+
+    # ---- device-resident warm-up (include/pfmi.h: pfmi_hmc_adapt_enqueue, pfmi_nuts_adapt_enqueue) -----------------------------------
+    ADAPT_KEPT_STEP = 1
+
+    def _adapt_enqueue(self, fn, points, x0, seeds, step_size0, param, nwarmup, ntransitions, target_accept, flags):
+        points = np.ascontiguousarray(points, dtype=np.int64)
+        K = len(points)
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
+        eps = np.ascontiguousarray(np.broadcast_to(np.asarray(step_size0, dtype=np.float64), (K,)))
+        assert seeds.shape == (K,)
+        x0 = np.asfortranarray(x0, dtype=np.float64)
+        assert x0.shape == (self.d, K), (x0.shape, self.d, K)
+        rc = fn(self.ctx, K, points.ctypes.data_as(_i64p), _d(x0), seeds.ctypes.data_as(C.POINTER(C.c_uint64)), _d(eps), int(param),
+                int(nwarmup), int(ntransitions), float(target_accept), int(flags))
+        if getattr(self.target, "pending_error", None) is not None:
+            self.sync()
+            self._raise_target_error()
+        check(rc)
+        self._hmc = (K, int(ntransitions))
+        self._adapt = (K, int(nwarmup))
+        self.hmc_runs += 1
+
+    def hmc_adapt_enqueue(self, points, x0, seeds, step_size0, nleapfrog, nwarmup, ntransitions, target_accept=0.8, flags=0):
+        """hmc_enqueue with `nwarmup` warm-up transitions in front whose step sizes are adapted on the device after every transition (dual
+        averaging towards target_accept, from step_size0); the rows of hmc_get are the `ntransitions` sampling transitions.  One enqueue;
+        does not wait.  flags must be 0."""
+        self._adapt_enqueue(self.L.pfmi_hmc_adapt_enqueue, points, x0, seeds, step_size0, nleapfrog, nwarmup, ntransitions, target_accept, flags)
+
+    def nuts_adapt_enqueue(self, points, x0, seeds, step_size0, max_depth, nwarmup, ntransitions, target_accept=0.8, flags=0):
+        """nuts_enqueue with `nwarmup` adaptive warm-up transitions in front (hmc_adapt_enqueue); nuts_pump / nuts_wait issue the rounds"""
+        self._adapt_enqueue(self.L.pfmi_nuts_adapt_enqueue, points, x0, seeds, step_size0, max_depth, nwarmup, ntransitions, target_accept, flags)
+
+    def adapt_get(self):
+        """the last adaptive run's warm-up: dict of step_size (K,) the sampling transitions' step sizes, eps_trace, accept_trace (K, W),
+        divergent, n_leapfrog int32 (K, W) and status int32 (K,) (ADAPT_KEPT_STEP)"""
+        if self._adapt is None:
+            check(self.L.pfmi_adapt_get(self.ctx, None, None, None, None, None, None))       # (PFMI_ERR_STATE: the library's message)
+            raise _lib.PfmiError("adapt_get: no adaptive run was enqueued through this engine")
+        K, W = self._adapt
+        i32p = C.POINTER(C.c_int32)
+        out = {"step_size": np.empty(K), "eps_trace": np.empty((K, W)), "accept_trace": np.empty((K, W)),
+               "divergent": np.empty((K, W), dtype=np.int32), "n_leapfrog": np.empty((K, W), dtype=np.int32), "status": np.empty(K, dtype=np.int32)}
+        check(self.L.pfmi_adapt_get(self.ctx, _d(out["step_size"]), _d(out["eps_trace"]), _d(out["accept_trace"]),
+                                    out["divergent"].ctypes.data_as(i32p), out["n_leapfrog"].ctypes.data_as(i32p), out["status"].ctypes.data_as(i32p)))
+        return out
 
     def nuts_pump(self):
         """one scheduling pass; True once every chain has made its transitions"""

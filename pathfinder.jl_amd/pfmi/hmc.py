@@ -101,6 +101,8 @@ class HMCResult:
     nwarmup: int = 0
     engine: Any = field(repr=False, default=None)
     run: int = 0                      # engine.hmc_runs after this result's last hmc_enqueue (0: unknown)
+    # adapt="device": the warm-up's traces (Engine.adapt_get: eps_trace, accept_trace, divergent, n_leapfrog (nchains, nwarmup), status)
+    warmup: Any = field(default=None, kw_only=True)
 
     def summary(self):
         """ChainSummary of the draws and of logp.  While this result is still the engine's latest run the resident records are used; after
@@ -146,13 +148,23 @@ def _starts_and_points(result):
     return dist.engine, draws, np.full(draws.shape[1], dist.point, dtype=np.int64), dist.token
 
 
-def hmc(result, ndraws, *, nchains=None, nwarmup=0, step_size="auto", nleapfrog=8, rng=None, target_accept=0.8, window=10):
+def _check_adapt(adapt, auto, nwarmup):
+    if adapt not in ("windows", "device"):
+        raise ValueError('adapt must be "windows" or "device"')
+    if adapt == "device" and not (auto and nwarmup >= 1):
+        raise ValueError('adapt="device" adapts the step size during the warm-up: it needs step_size="auto" and nwarmup >= 1')
+    return adapt == "device"
+
+
+def hmc(result, ndraws, *, nchains=None, nwarmup=0, step_size="auto", nleapfrog=8, rng=None, target_accept=0.8, window=10, adapt="windows"):
     """`ndraws` transitions of `nchains` chains of static HMC from a PathfinderResult / MultiPathfinderResult.
 
     Chain c starts at result.draws[:, c] (resample(result, nchains, replace=False) first gives distinct starts) and uses the best fit of
     the run that draw came from as its metric.  step_size: a number, one per chain, or "auto": d^(-1/4), adapted per chain during the
     `nwarmup` warm-up transitions between windows of `window` transitions by dual averaging on the window's mean acceptance
-    (dual_averaging_update); the warm-up draws are discarded and sampling uses the averaged step size."""
+    (dual_averaging_update); the warm-up draws are discarded and sampling uses the averaged step size.  adapt="device" (step_size="auto"
+    only): the device updates every chain's step size after every warm-up transition (include/pfmi.h: pfmi_hmc_adapt_enqueue); warm-up and
+    sampling are ONE enqueue, and the result's `warmup` holds the traces."""
     eng, starts, pts, token = _starts_and_points(result)
     if eng is None:
         raise ValueError("pfmi.hmc needs a result whose fits are still on an engine")
@@ -172,6 +184,12 @@ def hmc(result, ndraws, *, nchains=None, nwarmup=0, step_size="auto", nleapfrog=
     if auto and step_size != "auto":
         raise ValueError('step_size must be a number, an array of nchains numbers or "auto"')
     eps = np.full(nchains, d ** -0.25) if auto else np.broadcast_to(np.asarray(step_size, dtype=np.float64), (nchains,)).copy()
+    if _check_adapt(adapt, auto, int(nwarmup)):
+        eng.hmc_adapt_enqueue(pts, x0, seeds, eps, nleapfrog, int(nwarmup), int(ndraws), target_accept)
+        eng.hmc_wait()
+        got, warm = eng.hmc_get(), eng.adapt_get()
+        return HMCResult(got["draws"], got["logp"], got["accept_prob"], got["energy_error"], got["divergent"], warm.pop("step_size"),
+                         np.array(pts), int(nleapfrog), int(nwarmup), eng, eng.hmc_runs, warmup=warm)
     done, first = 0, True
     if nwarmup > 0:
         state = dual_averaging_init(eps)
@@ -211,10 +229,11 @@ class NUTSResult(HMCResult):
         return "\n".join(lines)
 
 
-def nuts(result, ndraws, *, nchains=None, nwarmup=0, step_size="auto", max_depth=10, rng=None, target_accept=0.8, window=10):
+def nuts(result, ndraws, *, nchains=None, nwarmup=0, step_size="auto", max_depth=10, rng=None, target_accept=0.8, window=10, adapt="windows"):
     """`ndraws` transitions of `nchains` chains of multinomial NUTS from a PathfinderResult / MultiPathfinderResult: the starts, metrics,
     seeds and step-size rule of `hmc` (dual averaging between windows of `window` warm-up transitions on the windows' mean accept_prob,
-    the mean over a tree's leaves of min(1, exp(H0 - H))), with trees of at most 2^max_depth - 1 leapfrog steps instead of a fixed count."""
+    the mean over a tree's leaves of min(1, exp(H0 - H))), with trees of at most 2^max_depth - 1 leapfrog steps instead of a fixed count.
+    adapt="device": as for `hmc`, one enqueue whose warm-up adapts on the device after every transition (pfmi_nuts_adapt_enqueue)."""
     eng, starts, pts, token = _starts_and_points(result)
     if eng is None:
         raise ValueError("pfmi.nuts needs a result whose fits are still on an engine")
@@ -236,6 +255,13 @@ def nuts(result, ndraws, *, nchains=None, nwarmup=0, step_size="auto", max_depth
     if auto and step_size != "auto":
         raise ValueError('step_size must be a number, an array of nchains numbers or "auto"')
     eps = np.full(nchains, d ** -0.25) if auto else np.broadcast_to(np.asarray(step_size, dtype=np.float64), (nchains,)).copy()
+    if _check_adapt(adapt, auto, int(nwarmup)):
+        eng.nuts_adapt_enqueue(pts, x0, seeds, eps, max_depth, int(nwarmup), int(ndraws), target_accept)
+        eng.nuts_wait()
+        got, warm = eng.hmc_get(), eng.adapt_get()
+        depth, nleap = eng.nuts_get_stats()
+        return NUTSResult(got["draws"], got["logp"], got["accept_prob"], got["energy_error"], got["divergent"], warm.pop("step_size"),
+                          np.array(pts), 0, int(nwarmup), eng, eng.hmc_runs, depth, nleap, int(max_depth), warmup=warm)
     done, first = 0, True
     if nwarmup > 0:
         state = dual_averaging_init(eps)
