@@ -20,24 +20,13 @@ int32_t adapt_keep_step_sizes(pfmi_ctx *c) {
     return PFMI_OK;
 }
 
-// the adaptation states of K chains that start at step_size[k], and their empty traces
-int32_t adapt_reserve(pfmi_ctx *c, int32_t K, int64_t W, const double *step_size, double delta) {
-    PF_TRY(c->hm_adapt.ensure(adapt_bytes(K, W)));
+// the adaptation states of K chains that start at step_size[k], and their empty traces (hm_adapt holds adapt_bytes(K, W): chain_begin)
+int32_t adapt_reset(pfmi_ctx *c, int32_t K, int64_t W, const double *step_size, double delta) {
     std::vector<PfAdapt> st((size_t)K);
     for (int k = 0; k < K; ++k) st[(size_t)k] = pf_adapt_init(step_size[k], delta);
     PF_TRY(pf_upload(c, c->hm_adapt.p, st.data(), sizeof(PfAdapt) * (size_t)K));
     PF_HIP(hipMemsetAsync(c->hm_adapt.as<PfAdapt>() + K, 0, sizeof(PfWarmRow) * (size_t)K * (size_t)W, c->stream));
     return PFMI_OK;
-}
-
-// (as every other error of the two enqueues, a refused argument drains the stream and leaves no chains and no traces behind)
-static int32_t adapt_refused(pfmi_ctx *c, int32_t rc) {
-    if (rc != PFMI_OK) {
-        (void)hipStreamSynchronize(c->stream);
-        c->hmc.finished = true;
-        hmc_forget(c);
-    }
-    return rc;
 }
 
 static int32_t adapt_args(const char *who, int64_t W, double delta, int32_t flags) {
@@ -54,7 +43,7 @@ int32_t pfmi_hmc_adapt_enqueue(pfmi_ctx *c, int32_t K, const int64_t *points, co
     PF_CTX_MUT(c);
     int32_t rc = adapt_args("hmc_adapt_enqueue", nwarmup, target_accept, flags);
     if (rc == PFMI_OK) rc = hmc_enqueue(c, K, points, x0, seeds, step_size0, nleapfrog, ntransitions, 0, nwarmup, target_accept);
-    return adapt_refused(c, rc);
+    return chain_refused(c, rc);        // (as every other error of the enqueues, a refused argument leaves no chains and no traces behind)
 }
 
 int32_t pfmi_nuts_adapt_enqueue(pfmi_ctx *c, int32_t K, const int64_t *points, const double *x0, const uint64_t *seeds, const double *step_size0,
@@ -62,7 +51,7 @@ int32_t pfmi_nuts_adapt_enqueue(pfmi_ctx *c, int32_t K, const int64_t *points, c
     PF_CTX_MUT(c);
     int32_t rc = adapt_args("nuts_adapt_enqueue", nwarmup, target_accept, flags);
     if (rc == PFMI_OK) rc = nuts_enqueue(c, K, points, x0, seeds, step_size0, max_depth, ntransitions, 0, nwarmup, target_accept);
-    return adapt_refused(c, rc);
+    return chain_refused(c, rc);
 }
 
 int32_t pfmi_adapt_get(pfmi_ctx *c, double *step_size, double *eps_trace, double *accept_trace, int32_t *divergent, int32_t *n_leapfrog,

@@ -1,9 +1,13 @@
 // api_hmc.hip -- static HMC on a fitted metric for gradient closures: the entry points of include/pfmi.h over hmc_kernel.hip, and the
-// diagnostics of its chains (or of any uploaded ones), pfmi_chain_diagnostics over chain_diag_kernels.hip.
+// diagnostics of its chains (or of any uploaded ones), pfmi_chain_diagnostics over chain_diag_kernels.hip.  Also the ONE enqueue path of
+// both samplers (chain_check_target, chain_check_chains, chain_begin: checks, the buffer list, uploads, bookkeeping) and their shared epilogues; api_nuts.hip and api_adapt.hip
+// call them.
 #include "api_internal.h"
 
 #include <math.h>
 #include <vector>
+
+static_assert(PFMI_HMC_CONTINUE == PFMI_NUTS_CONTINUE && PFMI_HMC_RECORD_PATH == PFMI_NUTS_RECORD_PATH, "the samplers share their flags");
 
 // an HMC call that was never waited for still writes the chains and the records on the ctx stream: drain THIS ctx's stream (never the
 // device) and forget the chains.  Called by whatever replaces the target, the traces or the fit the chains were made for.
@@ -16,93 +20,155 @@ void hmc_forget(pfmi_ctx *c) {
     c->hmc.eps_kept = false;
 }
 
-int32_t hmc_enqueue(pfmi_ctx *c, int32_t K, const int64_t *points, const double *x0, const uint64_t *seeds, const double *step_size,
-                    int32_t nleapfrog, int64_t T, int32_t flags, int64_t W, double delta) {
-    HmcState &H = c->hmc;
-    const TargetDev &Tg = c->target;
-    const bool cont = (flags & PFMI_HMC_CONTINUE) != 0, rec = (flags & PFMI_HMC_RECORD_PATH) != 0;
-    PF_CHECK(c->fitted, PFMI_ERR_STATE, "hmc_enqueue: call pfmi_fit_batch first");
-    PF_CHECK(Tg.kind == PFMI_TARGET_DEVICE_CALLBACK && Tg.grad_fn != nullptr, PFMI_ERR_UNSUPPORTED,
-             "hmc_enqueue: needs a DEVICE_CALLBACK target with a gradient closure (pfmi_set_target_gradient)");
-    PF_CHECK(Tg.d == c->d, PFMI_ERR_STATE, "hmc_enqueue: the target's dimension %d is not the fit's %d", Tg.d, c->d);
-    PF_CHECK(K >= 1 && points && seeds && step_size && (cont || x0), PFMI_ERR_ARG, "hmc_enqueue: K < 1 or a null argument");
-    PF_CHECK(nleapfrog >= 1 && T >= 1, PFMI_ERR_ARG, "hmc_enqueue: nleapfrog %d and ntransitions %lld must be >= 1", nleapfrog, (long long)T);
-    PF_CHECK((flags & ~(PFMI_HMC_CONTINUE | PFMI_HMC_RECORD_PATH)) == 0, PFMI_ERR_ARG, "hmc_enqueue: unknown flags %d", flags);
-    for (int k = 0; k < K; ++k) {
-        PF_CHECK(points[k] >= 0 && points[k] < c->P, PFMI_ERR_ARG, "hmc_enqueue: point %lld of chain %d outside [0, %lld)", (long long)points[k], k,
-                 (long long)c->P);
-        PF_CHECK(isfinite(step_size[k]) && step_size[k] > 0.0, PFMI_ERR_ARG, "hmc_enqueue: step size of chain %d is not positive and finite", k);
+// The one refusal epilogue of the enqueues, the pump and the wait: an error exit drains this ctx's stream and leaves no chains, no traces
+// and no run behind.  (Every reader of HmcState tests `have` -- cleared here -- before any other field.)
+int32_t chain_refused(pfmi_ctx *c, int32_t rc) {
+    if (rc != PFMI_OK) {
+        (void)hipStreamSynchronize(c->stream);
+        c->hmc.finished = true;
+        hmc_forget(c);
     }
-    PF_CHECK(!cont || (H.have && H.K == K), PFMI_ERR_STATE, "hmc_enqueue: PFMI_HMC_CONTINUE without %d resident chains", K);
-    PF_CHECK(!cont || H.kind == 0, PFMI_ERR_STATE, "hmc_enqueue: PFMI_HMC_CONTINUE on the chains of pfmi_nuts_enqueue");
+    return rc;
+}
+
+// the one wait epilogue: a chain whose start point had a non-finite log density or gradient cannot leave it
+int32_t chain_dead_check(pfmi_ctx *c, const char *name, const std::vector<int32_t> &dead) {
+    for (int k = 0; k < c->hmc.K; ++k)
+        if (dead[(size_t)k]) {
+            c->hmc.have = false;
+            PF_CHECK(false, PFMI_ERR_NUMERIC, "%s: the start point of chain %d has a non-finite log density or gradient", name, k);
+        }
+    return PFMI_OK;
+}
+
+// rounds [round0, round0 + nrounds) of the recorded path: X, v and the closure's output (queued; the caller waits)
+int32_t chain_path_download(pfmi_ctx *c, int64_t round0, int64_t nrounds, double *X, double *closure_out, double *v) {
+    const size_t vec = (size_t)c->hmc.K * c->d, ovec = (size_t)c->hmc.K * (c->d + 1);
+    if (X) PF_TRY(pf_download(c, X, c->hm_pX.as<double>() + (size_t)round0 * vec, sizeof(double) * vec * (size_t)nrounds));
+    if (v) PF_TRY(pf_download(c, v, c->hm_pv.as<double>() + (size_t)round0 * vec, sizeof(double) * vec * (size_t)nrounds));
+    if (closure_out) PF_TRY(pf_download(c, closure_out, c->hm_pout.as<double>() + (size_t)round0 * ovec, sizeof(double) * ovec * (size_t)nrounds));
+    return PFMI_OK;
+}
+
+int32_t chain_check_target(pfmi_ctx *c, const ChainKind &S, const ChainCall &A) {
+    const TargetDev &Tg = c->target;
+    const bool cont = (A.flags & PFMI_HMC_CONTINUE) != 0;
+    PF_CHECK(c->fitted, PFMI_ERR_STATE, "%s_enqueue: call pfmi_fit_batch first", S.name);
+    PF_CHECK(Tg.kind == PFMI_TARGET_DEVICE_CALLBACK && Tg.grad_fn != nullptr, PFMI_ERR_UNSUPPORTED,
+             "%s_enqueue: needs a DEVICE_CALLBACK target with a gradient closure (pfmi_set_target_gradient)", S.name);
+    PF_CHECK(Tg.d == c->d, PFMI_ERR_STATE, "%s_enqueue: the target's dimension %d is not the fit's %d", S.name, Tg.d, c->d);
+    PF_CHECK(A.K >= 1 && A.points && A.seeds && A.step_size && (cont || A.x0), PFMI_ERR_ARG, "%s_enqueue: K < 1 or a null argument", S.name);
+    return PFMI_OK;
+}
+
+int32_t chain_check_chains(pfmi_ctx *c, const ChainKind &S, const ChainCall &A) {
+    const HmcState &H = c->hmc;
+    const int32_t K = A.K, flags = A.flags;
+    const int64_t *points = A.points;
+    const double *step_size = A.step_size;
+    const bool cont = (flags & PFMI_HMC_CONTINUE) != 0;
+    PF_CHECK((flags & ~(PFMI_HMC_CONTINUE | PFMI_HMC_RECORD_PATH)) == 0, PFMI_ERR_ARG, "%s_enqueue: unknown flags %d", S.name, flags);
+    for (int k = 0; k < K; ++k) {
+        PF_CHECK(points[k] >= 0 && points[k] < c->P, PFMI_ERR_ARG, "%s_enqueue: point %lld of chain %d outside [0, %lld)", S.name, (long long)points[k],
+                 k, (long long)c->P);
+        PF_CHECK(isfinite(step_size[k]) && step_size[k] > 0.0, PFMI_ERR_ARG, "%s_enqueue: step size of chain %d is not positive and finite", S.name, k);
+    }
+    PF_CHECK(!cont || (H.have && H.K == K), PFMI_ERR_STATE, "%s_enqueue: PFMI_%s_CONTINUE without %d resident chains", S.name, S.NAME, K);
+    PF_CHECK(!cont || H.kind == S.kind, PFMI_ERR_STATE, "%s_enqueue: PFMI_%s_CONTINUE on the chains of pfmi_%s_enqueue", S.name, S.NAME, S.other);
+    return PFMI_OK;
+}
+
+int32_t chain_begin(pfmi_ctx *c, const ChainKind &S, const ChainCall &A, int64_t per_transition, const char *need_detail,
+                    std::vector<ChainBuf> bufs, int32_t (*drain)(pfmi_ctx *), int64_t *rounds_out) {
+    HmcState &H = c->hmc;
+    const int32_t K = A.K;
+    const int64_t *points = A.points, T = A.T, W = A.W;
+    const double *step_size = A.step_size;
+    const bool cont = (A.flags & PFMI_HMC_CONTINUE) != 0, rec = (A.flags & PFMI_HMC_RECORD_PATH) != 0;
     const int d = c->d;
-    const int64_t rounds = (cont ? 0 : 1) + (W + T) * (int64_t)nleapfrog;
-    const char *stage = W ? "hmc_adapt" : "hmc", *cstage = W ? "hmc_adapt_closure" : "hmc_closure";
+    const int64_t rounds = (cont ? 0 : 1) + (W + T) * per_transition;
     {   // the fits the chains ask for are successes
         std::vector<int32_t> st((size_t)c->P);
         PF_TRY(d2h(c, st.data(), c->status.p, sizeof(int32_t) * (size_t)c->P));
         for (int k = 0; k < K; ++k)
-            PF_CHECK(st[(size_t)points[k]] == PFMI_FIT_OK, PFMI_ERR_NUMERIC, "hmc_enqueue: the fit of point %lld (chain %d) has status %d",
+            PF_CHECK(st[(size_t)points[k]] == PFMI_FIT_OK, PFMI_ERR_NUMERIC, "%s_enqueue: the fit of point %lld (chain %d) has status %d", S.name,
                      (long long)points[k], k, st[(size_t)points[k]]);
     }
-    const size_t vec = sizeof(double) * (size_t)K * d, rows = (size_t)K * (size_t)T;
-    const size_t out_bytes = sizeof(double) * (size_t)K * (d + 1);
-    {   // what the call's `ensure`s below will grow (a buffer that is large enough already -- the chains of a CONTINUE, the records of an
-        // equal call before -- costs nothing: hipMemGetInfo's free figure excludes it)
+    // The buffers of the call, each size stated ONCE: the samplers' common ones here, `bufs` holds the caller's own.  The estimate and the
+    // `ensure`s both walk this list.  (est = false: the small per-chain arrays the estimate has always left out.)
+    const size_t vec = sizeof(double) * (size_t)K * d, rows = (size_t)K * (size_t)T, out_bytes = sizeof(double) * (size_t)K * (d + 1);
+    for (DevBuf *b : {&c->hm_X, &c->hm_x0}) bufs.push_back({b, vec, CHAIN_BUF});
+    bufs.push_back({&c->hm_out, out_bytes, CHAIN_BUF});
+    bufs.push_back({&c->hm_pts, sizeof(int32_t) * (size_t)K, CHAIN_BUF, false});
+    bufs.push_back({&c->hm_seeds, sizeof(uint64_t) * (size_t)K, CHAIN_BUF, false});
+    bufs.push_back({&c->hm_eps, sizeof(double) * (size_t)K, CHAIN_BUF, false});
+    bufs.push_back({&c->hm_draws, sizeof(double) * rows * d, CALL_BUF});
+    for (DevBuf *b : {&c->hm_lp, &c->hm_acc, &c->hm_de}) bufs.push_back({b, sizeof(double) * rows, CALL_BUF});
+    bufs.push_back({&c->hm_div, sizeof(int32_t) * rows, CALL_BUF});
+    if (W) bufs.push_back({&c->hm_adapt, adapt_bytes(K, W), CALL_BUF});
+    for (DevBuf *b : {&c->hm_pX, &c->hm_pv}) bufs.push_back({b, vec, PATH_BUF});
+    bufs.push_back({&c->hm_pout, out_bytes, PATH_BUF});
+    // what this call grows: a CONTINUE keeps the chains' buffers, only RECORD_PATH has path rows (one per round, of the cap for NUTS)
+    std::vector<ChainBuf> grown;
+    for (ChainBuf b : bufs) {
+        if ((b.scope == CHAIN_BUF && cont) || (b.scope == PATH_BUF && !rec)) continue;
+        if (b.scope == PATH_BUF) b.bytes *= (size_t)rounds;
+        grown.push_back(b);
+    }
+    {   // against what is free (a buffer that is large enough already -- the records of an equal call before -- costs nothing:
+        // hipMemGetInfo's free figure excludes it)
         size_t fr = 0, tot = 0;
         PF_HIP(hipMemGetInfo(&fr, &tot));
         double need = 0.0;
-        auto grow = [&](const DevBuf &b, size_t bytes) { if (bytes > b.cap) need += (double)bytes; };
-        if (!cont) {
-            for (const DevBuf *b : {&c->hm_X, &c->hm_x0, &c->hm_x, &c->hm_wg, &c->hm_wt, &c->hm_v}) grow(*b, vec);
-            grow(c->hm_out, out_bytes);
-        }
-        grow(c->hm_draws, sizeof(double) * rows * d);
-        for (const DevBuf *b : {&c->hm_lp, &c->hm_acc, &c->hm_de}) grow(*b, sizeof(double) * rows);
-        grow(c->hm_div, sizeof(int32_t) * rows);
-        if (W) grow(c->hm_adapt, adapt_bytes(K, W));
-        if (rec) {
-            grow(c->hm_pX, vec * (size_t)rounds);
-            grow(c->hm_pv, vec * (size_t)rounds);
-            grow(c->hm_pout, out_bytes * (size_t)rounds);
-        }
-        PF_CHECK(need < 0.8 * (double)fr, PFMI_ERR_UNSUPPORTED, "hmc_enqueue: %.3g GB more needed for K = %d, d = %d, %lld transitions; %.3g GB free",
-                 need / 1e9, K, d, (long long)T, (double)fr / 1e9);
+        for (const ChainBuf &b : grown) if (b.est && b.bytes > b.buf->cap) need += (double)b.bytes;
+        PF_CHECK(need < 0.8 * (double)fr, PFMI_ERR_UNSUPPORTED, "%s_enqueue: %.3g GB more needed for K = %d, d = %d, %lld transitions%s; %.3g GB free",
+                 S.name, need / 1e9, K, d, (long long)T, need_detail, (double)fr / 1e9);
     }
-    if (!cont) {
-        hmc_forget(c);
-        for (DevBuf *b : {&c->hm_X, &c->hm_x0, &c->hm_x, &c->hm_wg, &c->hm_wt, &c->hm_v}) PF_TRY(b->ensure(vec));
-        PF_TRY(c->hm_out.ensure(out_bytes));
-        PF_TRY(c->hm_st.ensure(pf_hmc_chain_bytes() * (size_t)K));
-        PF_TRY(c->hm_pts.ensure(sizeof(int32_t) * (size_t)K));
-        PF_TRY(c->hm_seeds.ensure(sizeof(uint64_t) * (size_t)K));
-        PF_TRY(c->hm_eps.ensure(sizeof(double) * (size_t)K));
-    } else if (H.active) {
-        PF_HIP(hipStreamSynchronize(c->stream));          // the records of the call before are rewritten (and may be reallocated)
+    if (!cont) hmc_forget(c);
+    else {
+        if (drain) PF_TRY(drain(c));                      // NUTS: the rounds of the call before that were not issued yet
+        if (drain || H.active) PF_HIP(hipStreamSynchronize(c->stream));     // its records are rewritten (and may be reallocated)
         H.active = false;
     }
-    PF_TRY(c->hm_draws.ensure(sizeof(double) * rows * d));
-    for (DevBuf *b : {&c->hm_lp, &c->hm_acc, &c->hm_de}) PF_TRY(b->ensure(sizeof(double) * rows));
-    PF_TRY(c->hm_div.ensure(sizeof(int32_t) * rows));
-    if (rec) {
-        PF_TRY(c->hm_pX.ensure(vec * (size_t)rounds));
-        PF_TRY(c->hm_pv.ensure(vec * (size_t)rounds));
-        PF_TRY(c->hm_pout.ensure(out_bytes * (size_t)rounds));
-    }
+    for (const ChainBuf &b : grown) PF_TRY(b.buf->ensure(b.bytes));
     std::vector<int32_t> p32((size_t)K);
     for (int k = 0; k < K; ++k) p32[(size_t)k] = (int32_t)points[k];
     PF_TRY(pf_upload(c, c->hm_pts.p, p32.data(), sizeof(int32_t) * (size_t)K));
-    PF_TRY(pf_upload(c, c->hm_seeds.p, seeds, sizeof(uint64_t) * (size_t)K));
+    PF_TRY(pf_upload(c, c->hm_seeds.p, A.seeds, sizeof(uint64_t) * (size_t)K));
     if (cont) PF_TRY(adapt_keep_step_sizes(c));
     PF_TRY(pf_upload(c, c->hm_eps.p, step_size, sizeof(double) * (size_t)K));
-    if (!cont) PF_TRY(pf_upload(c, c->hm_x0.p, x0, vec));
-    if (W) PF_TRY(adapt_reserve(c, K, W, step_size, delta));
-    H.K = K; H.nleap = nleapfrog; H.record = rec; H.kind = 0; H.finished = true;
+    if (!cont) PF_TRY(pf_upload(c, c->hm_x0.p, A.x0, vec));
+    if (W) PF_TRY(adapt_reset(c, K, W, step_size, A.delta));
+    H.K = K; H.record = rec; H.kind = S.kind;
     H.t0 = cont ? H.t0 + H.T : W; H.T = T;
     H.adapting = W > 0;
     if (W) H.W = W;
     H.rounds = 0; H.columns = 0; H.path_rounds = rec ? rounds : 0;
-    H.have = true; H.active = true;                       // from here on, failure paths drain (pfmi_hmc_enqueue)
+    H.have = true; H.active = true;                       // from here on, failure paths drain (chain_refused)
+    *rounds_out = rounds;
+    return PFMI_OK;
+}
+
+static const ChainKind HMC_KIND = {"hmc", "HMC", "nuts", 0};
+
+int32_t hmc_enqueue(pfmi_ctx *c, int32_t K, const int64_t *points, const double *x0, const uint64_t *seeds, const double *step_size,
+                    int32_t nleapfrog, int64_t T, int32_t flags, int64_t W, double delta) {
+    HmcState &H = c->hmc;
+    const TargetDev &Tg = c->target;
+    const int d = c->d;
+    const size_t vec = sizeof(double) * (size_t)K * d;
+    const ChainCall A = {K, points, x0, seeds, step_size, T, flags, W, delta};
+    PF_TRY(chain_check_target(c, HMC_KIND, A));
+    PF_CHECK(nleapfrog >= 1 && T >= 1, PFMI_ERR_ARG, "hmc_enqueue: nleapfrog %d and ntransitions %lld must be >= 1", nleapfrog, (long long)T);
+    PF_TRY(chain_check_chains(c, HMC_KIND, A));
+    std::vector<ChainBuf> own;
+    for (DevBuf *b : {&c->hm_x, &c->hm_wg, &c->hm_wt, &c->hm_v}) own.push_back({b, vec, CHAIN_BUF});
+    own.push_back({&c->hm_st, pf_hmc_chain_bytes() * (size_t)K, CHAIN_BUF, false});
+    int64_t rounds = 0;
+    PF_TRY(chain_begin(c, HMC_KIND, A, nleapfrog, "", own, nullptr, &rounds));
+    const bool cont = (flags & PFMI_HMC_CONTINUE) != 0;
+    const char *stage = W ? "hmc_adapt" : "hmc", *cstage = W ? "hmc_adapt_closure" : "hmc_closure";
+    H.nleap = nleapfrog; H.finished = true;
     if (!cont) PF_TRY(pf_launch_hmc_init(c, c->stream));
     else {
         pf_kernel_begin(c);
@@ -128,12 +194,7 @@ extern "C" {
 int32_t pfmi_hmc_enqueue(pfmi_ctx *c, int32_t K, const int64_t *points, const double *x0, const uint64_t *seeds, const double *step_size,
                          int32_t nleapfrog, int64_t ntransitions, int32_t flags) {
     PF_CTX_MUT(c);
-    const int32_t rc = hmc_enqueue(c, K, points, x0, seeds, step_size, nleapfrog, ntransitions, flags, 0, 0.0);
-    if (rc != PFMI_OK) {                                  // an error exit drains this ctx's stream and leaves no chains behind
-        (void)hipStreamSynchronize(c->stream);
-        c->hmc.active = false; c->hmc.have = false;
-    }
-    return rc;
+    return chain_refused(c, hmc_enqueue(c, K, points, x0, seeds, step_size, nleapfrog, ntransitions, flags, 0, 0.0));
 }
 
 int32_t pfmi_hmc_wait(pfmi_ctx *c) {
@@ -144,12 +205,7 @@ int32_t pfmi_hmc_wait(pfmi_ctx *c) {
     c->hmc.active = false;
     std::vector<int32_t> dead;
     PF_TRY(pf_hmc_dead_flags(c, dead));
-    for (int k = 0; k < c->hmc.K; ++k)
-        if (dead[(size_t)k]) {
-            c->hmc.have = false;
-            PF_CHECK(false, PFMI_ERR_NUMERIC, "hmc: the start point of chain %d has a non-finite log density or gradient", k);
-        }
-    return PFMI_OK;
+    return chain_dead_check(c, "hmc", dead);
 }
 
 int32_t pfmi_hmc_get(pfmi_ctx *c, double *draws, double *logp, double *accept_prob, double *energy_error, int32_t *divergent) {
@@ -182,10 +238,7 @@ int32_t pfmi_hmc_get_path(pfmi_ctx *c, int64_t round0, int64_t nrounds, double *
     PF_CHECK(H.have && H.record && H.kind == 0, PFMI_ERR_STATE, "hmc_get_path: the last pfmi_hmc_enqueue did not run with PFMI_HMC_RECORD_PATH");
     PF_CHECK(round0 >= 0 && nrounds >= 0 && round0 + nrounds <= H.path_rounds, PFMI_ERR_ARG, "hmc_get_path: rounds [%lld, %lld) outside [0, %lld)",
              (long long)round0, (long long)(round0 + nrounds), (long long)H.path_rounds);
-    const size_t vec = (size_t)H.K * c->d, ovec = (size_t)H.K * (c->d + 1);
-    if (X) PF_TRY(pf_download(c, X, c->hm_pX.as<double>() + (size_t)round0 * vec, sizeof(double) * vec * (size_t)nrounds));
-    if (v) PF_TRY(pf_download(c, v, c->hm_pv.as<double>() + (size_t)round0 * vec, sizeof(double) * vec * (size_t)nrounds));
-    if (closure_out) PF_TRY(pf_download(c, closure_out, c->hm_pout.as<double>() + (size_t)round0 * ovec, sizeof(double) * ovec * (size_t)nrounds));
+    PF_TRY(chain_path_download(c, round0, nrounds, X, closure_out, v));
     PF_TRY(pf_stream_sync(c));
     c->hmc.active = false;
     return PFMI_OK;

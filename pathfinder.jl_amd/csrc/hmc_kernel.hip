@@ -12,11 +12,12 @@
 //
 // A launch of chain k
 //   * reads its column of the closure's output (logp, grad at the trial point it wrote in the previous launch),
-//   * forms wt = R grad:  z = s . grad, w = Vh'z (block reduction 1), tv = T'w, y = z - Vh tv, head <- V head,
+//   * forms wt = R grad:  z = s . grad, w = Vh'z (block reduction 1), tv = T'w, y = z - Vh tv, head <- V head (hm_apply_R, hmc_rows.h),
 //   * finishes the pending kick with it (a full one inside a trajectory, a half one at its end),
 //   * at a trajectory's end sums |v|^2 (one more reduction), decides, records row t, draws the next momentum, gives it its first half
 //     kick and takes |v|^2 of the fresh normals along in the reduction of the drift,
 //   * applies L to v:  z = [V'v_head; v_tail], w = Vh'z (block reduction 2), tv = T w, and writes x~ + e s . (z - Vh tv) into column k of X.
+//     (hm_apply_L, hmc_rows.h: both passes, the thread count, the LDS budget and the launch helper are shared with nuts_kernel.hip)
 // The chain's rows of Vh are kept in LDS once per launch when they fit (RES): the first pass reads them from HBM and leaves each thread's
 // rows in its own LDS slots, so that the other three passes (the second half of R, both halves of L) do not read HBM again.
 //
@@ -25,12 +26,7 @@
 // chain's output depends on nothing but its own inputs.
 #include "pfmi_common.h"
 #include "hmc_rows.h"
-#include "adapt.h"
 #include <float.h>
-
-#define HM_NT 256                      // threads per chain (4 waves)
-#define HM_NW (HM_NT / 64)
-#define HM_LDS_RES (150 * 1024)        // most dynamic LDS the staged factor rows may take (of 160 KB, beside the static buffers below)
 
 enum { HM_OPEN = -1, HM_START = 0 };   // HmChain::i: open a trajectory without reading the closure; the start point is being evaluated;
                                        // 1 .. Lf: the leapfrog evaluation the next launch consumes
@@ -62,9 +58,7 @@ struct HmArgs {
 
 __global__ __launch_bounds__(HM_NT) void pf_hmc_init_kernel(HmArgs A) {
     const int k = blockIdx.x, d = A.d;
-    const double *x0 = A.x0 + (size_t)k * d;
-    double *X = A.X + (size_t)k * d, *x = A.x + (size_t)k * d;
-    for (int i = threadIdx.x; i < d; i += HM_NT) { const double v = x0[i]; X[i] = v; x[i] = v; }
+    hm_copy_start(A.x0 + (size_t)k * d, A.X + (size_t)k * d, A.x + (size_t)k * d, d);
     if (threadIdx.x == 0) {
         HmChain S = {};
         S.i = HM_START;
@@ -76,10 +70,8 @@ __global__ __launch_bounds__(HM_NT) void pf_hmc_init_kernel(HmArgs A) {
 // between recording transition t and opening transition t + 1, whose first half kick and drift already use the new step size.
 template <int KPAD, bool RES, bool ADAPT>
 __device__ __forceinline__ void hm_step_body(const HmArgs &A) {
-    extern __shared__ __attribute__((aligned(32))) double sVh[];      // RES: the chain's factor rows [d][KPAD]
     constexpr int NVM = KPAD + 4;                        // KPAD sums + one rider, padded to the multiple of 4 pf_block_sum_mv takes
-    __shared__ double red[2 * HM_NW * NVM];
-    __shared__ double sHead[KPAD], sZ[KPAD], sTv[KPAD];
+    __shared__ HmLds<KPAD, NVM> L;
     const int k = blockIdx.x, tid = threadIdx.x, d = A.d, K = A.K;
     int flip = 0;
     HmChain S = A.st[k];
@@ -90,13 +82,8 @@ __device__ __forceinline__ void hm_step_body(const HmArgs &A) {
     double *X = A.X + kd, *x = A.x + kd, *wg = A.wg + kd, *wt = A.wt + kd, *v = A.v + kd;
     double eps = A.eps[k];
     const uint64_t seed = A.seeds[k];
-    // RES: a thread reads only the rows it owns (i = tid, tid + 256, ...), in every pass.  The first pass over the factor reads them from
-    // HBM and leaves them in LDS; the later ones (three more per launch) read the thread's own copy: no staging pass, no barrier.
-    bool staged = false;
-    auto vrow = [&](int i) -> const double * {
-        if constexpr (RES) return sVh + (size_t)i * KPAD;
-        else return gVh + (size_t)i * KPAD;
-    };
+    const HmFactor F = {gVh, T, Vc, sqa};
+    bool staged = false;                                 // an R pass came before the L pass (hmc_rows.h)
     bool open = S.i == HM_OPEN, drift = false;
     if (S.i != HM_OPEN) {
         const double lpt = A.out[k];
@@ -106,38 +93,8 @@ __device__ __forceinline__ void hm_step_body(const HmArgs &A) {
             for (int i = tid; i < d; i += HM_NT) { pX[i] = X[i]; pout[K + kd + i] = g[i]; }
             if (tid == 0) pout[k] = lpt;
         }
-        // ---- wt = R g: z = s . g, w = Vh'z, tv = T'w, y = z - Vh tv, head <- V head
-        double w[NVM];
-#pragma unroll
-        for (int j = 0; j < NVM; ++j) w[j] = 0.0;
-        for (int i = tid; i < d; i += HM_NT) {
-            const double gi = g[i], zi = sqa[i] * gi;
-            if (RES) hm_row_axpy<KPAD, NVM, true>(gVh + (size_t)i * KPAD, sVh + (size_t)i * KPAD, zi, w);
-            else hm_row_axpy<KPAD, NVM, false>(gVh + (size_t)i * KPAD, nullptr, zi, w);
-            w[KPAD] += isfinite(gi) ? 0.0 : 1.0;
-        }
+        const double nbad = hm_apply_R<KPAD, RES, HM_NT, NVM>(F, L, g, d, flip, [&](int i) -> double & { return wt[i]; });
         staged = true;
-        pf_block_sum_mv<NVM, NVM>(w, red, flip);
-        const double nbad = w[KPAD];
-        if (tid < KPAD) {
-            double s = 0.0;
-#pragma unroll
-            for (int b = 0; b < KPAD; ++b) if (b <= tid) s = fma(T[b * KPAD + tid], w[b], s);
-            sTv[tid] = s;
-        }
-        __syncthreads();
-        for (int i = tid; i < d; i += HM_NT) {
-            const double y = hm_row_sub<KPAD>(vrow(i), sTv, sqa[i] * g[i]);
-            if (i < KPAD) sHead[i] = y; else wt[i] = y;
-        }
-        if (tid < KPAD && tid >= d) sHead[tid] = 0.0;
-        __syncthreads();
-        if (tid < KPAD && tid < d) {
-            double s = 0.0;
-#pragma unroll
-            for (int b = 0; b < KPAD; ++b) if (b >= tid) s = fma(Vc[tid * KPAD + b], sHead[b], s);
-            wt[tid] = s;                                 // (row tid is thread tid's own: every thread reads back only rows it wrote)
-        }
         // ---- the pending kick
         if (S.i == HM_START) {
             const bool bad = nbad > 0.0 || !isfinite(lpt);       // a start point the chain cannot leave: reported by pfmi_hmc_wait
@@ -154,7 +111,7 @@ __device__ __forceinline__ void hm_step_body(const HmArgs &A) {
             // ---- the trajectory's end: last half kick, H1, the decision, row t
             double e = 0.0;
             for (int i = tid; i < d; i += HM_NT) { const double vi = fma(0.5 * eps, wt[i], v[i]); e = fma(vi, vi, e); }
-            e = pf_block_sum1_pp<NVM>(e, red, flip);
+            e = pf_block_sum1_pp<NVM>(e, L.red, flip);
             const double H1 = -lpt + 0.5 * e, dH = H1 - S.H0;
             const bool div = S.bad || nbad > 0.0 || !isfinite(lpt) || !isfinite(H1) || dH > 1000.0;
             const double a = div ? 0.0 : fmin(1.0, exp(-dH));
@@ -177,14 +134,7 @@ __device__ __forceinline__ void hm_step_body(const HmArgs &A) {
             if constexpr (ADAPT) {
                 if (warm) {
                     __shared__ double sNext;
-                    if (tid == 0) {
-                        PfWarmRow *tr = reinterpret_cast<PfWarmRow *>(A.ad + K) + (size_t)k * A.t0 + (S.t - 1);
-                        tr->eps = eps; tr->acc = a; tr->div = div ? 1 : 0; tr->nleap = A.nleap;
-                        PfAdapt Ad = A.ad[k];
-                        const double le = pf_adapt_update(Ad, a);
-                        const double en = pf_adapt_pick(Ad, S.t < A.t0 ? le : Ad.leb, eps);
-                        A.ad[k] = Ad; A.eps[k] = en; sNext = en;
-                    }
+                    if (tid == 0) sNext = hm_warm_end(A.ad, A.eps, K, k, S.t, A.t0, eps, a, div ? 1 : 0, A.nleap);
                     __syncthreads();
                     eps = sNext;
                 }
@@ -205,41 +155,9 @@ __device__ __forceinline__ void hm_step_body(const HmArgs &A) {
         drift = true;
     }
     if (drift) {
-        // ---- x~ <- base + e L v: z = [V'v_head; v_tail], w = Vh'z, tv = T w, y = s . (z - Vh tv)
         const double *base = open ? x : X;
-        __syncthreads();                                 // the head product above has read sHead
-        if (tid < KPAD) sHead[tid] = tid < d ? v[tid] : 0.0;
-        __syncthreads();
-        if (tid < KPAD) {
-            double s = 0.0;
-#pragma unroll
-            for (int b = 0; b < KPAD; ++b) if (b <= tid) s = fma(Vc[b * KPAD + tid], sHead[b], s);
-            sZ[tid] = s;
-        }
-        __syncthreads();
-        double w[NVM];
-#pragma unroll
-        for (int j = 0; j < NVM; ++j) w[j] = 0.0;
-        if (RES && !staged) {                            // (the opening launch of PFMI_HMC_CONTINUE: no R-apply came before)
-            for (int i = tid; i < d; i += HM_NT)
-                hm_row_axpy<KPAD, NVM, true>(gVh + (size_t)i * KPAD, sVh + (size_t)i * KPAD, i < KPAD ? sZ[i] : v[i], w);
-        } else {
-            for (int i = tid; i < d; i += HM_NT) hm_row_axpy<KPAD, NVM, false>(vrow(i), nullptr, i < KPAD ? sZ[i] : v[i], w);
-        }
-        w[KPAD] = vv0;
-        pf_block_sum_mv<NVM, NVM>(w, red, flip);
-        if (open) S.H0 = -S.lp + 0.5 * w[KPAD];
-        if (tid < KPAD) {
-            double s = 0.0;
-#pragma unroll
-            for (int b = 0; b < KPAD; ++b) if (b >= tid) s = fma(T[tid * KPAD + b], w[b], s);
-            sTv[tid] = s;
-        }
-        __syncthreads();
-        for (int i = tid; i < d; i += HM_NT) {
-            const double y = hm_row_sub<KPAD>(vrow(i), sTv, i < KPAD ? sZ[i] : v[i]);
-            X[i] = fma(eps, sqa[i] * y, base[i]);
-        }
+        hm_apply_L<KPAD, RES, HM_NT, NVM>(F, L, X, eps, vv0, staged, d, flip, [&](int i) -> const double & { return v[i]; }, [&](int i) { return base[i]; },
+                                          [&](double vv) { if (open) S.H0 = -S.lp + 0.5 * vv; });
     }
     if (A.record && A.round >= 0) {
         double *pv = A.pv + ((size_t)A.round * K + k) * d;
@@ -274,8 +192,6 @@ static HmArgs hm_args(pfmi_ctx *c, int64_t round) {
 }
 
 size_t pf_hmc_chain_bytes() { return sizeof(HmChain); }
-// the staged factor rows of one chain fit in LDS beside the reduction buffers
-bool pf_hmc_resident(int d, int kpad) { return (size_t)d * kpad * sizeof(double) <= (size_t)HM_LDS_RES; }
 
 int32_t pf_launch_hmc_init(pfmi_ctx *c, hipStream_t s) {
     hipLaunchKernelGGL(pf_hmc_init_kernel, dim3(c->hmc.K), dim3(HM_NT), 0, s, hm_args(c, 0));
@@ -283,17 +199,10 @@ int32_t pf_launch_hmc_init(pfmi_ctx *c, hipStream_t s) {
     return PFMI_OK;
 }
 
-template <int KPAD, bool RES, bool ADAPT>
-static int32_t hm_launch(pfmi_ctx *c, const HmArgs &A, hipStream_t s) {
-    const size_t lds = RES ? (size_t)A.d * KPAD * sizeof(double) : 0;
-    auto *kern = ADAPT ? &pf_hmc_warm_kernel<KPAD, RES> : &pf_hmc_step_kernel<KPAD, RES>;
-    if (RES) PF_TRY(pf_raise_lds_limit(c, reinterpret_cast<const void *>(kern), HM_LDS_RES));
-    char name[32];
-    snprintf(name, sizeof name, "%s:%d:%s", ADAPT ? "hmc_adapt" : "hmc", KPAD, RES ? "res" : "stream");
-    ++c->hmc_plans[name];
-    hipLaunchKernelGGL(kern, dim3(A.K), dim3(HM_NT), lds, s, A);
-    return PFMI_OK;
-}
+struct HmFamily {
+    template <int KPAD, bool RES, bool ADAPT>
+    static auto kernel() { return ADAPT ? &pf_hmc_warm_kernel<KPAD, RES> : &pf_hmc_step_kernel<KPAD, RES>; }
+};
 
 // the dying chains' start flags: dead[k] != 0 when chain k's start point had a non-finite log density or gradient
 int32_t pf_hmc_dead_flags(pfmi_ctx *c, std::vector<int32_t> &dead) {
@@ -306,16 +215,4 @@ int32_t pf_hmc_dead_flags(pfmi_ctx *c, std::vector<int32_t> &dead) {
     return PFMI_OK;
 }
 
-int32_t pf_launch_hmc_step(pfmi_ctx *c, int64_t round, hipStream_t s) {
-    const HmArgs A = hm_args(c, round);
-    const bool res = pf_hmc_resident(A.d, c->kpad);
-    int32_t rc = PFMI_OK;
-    const bool ok = pf_dispatch_kpad<4, 8, 12, 16, 20, 32, 64>(c->kpad, [&](auto KP) {
-        if (c->hmc.adapting) rc = res ? hm_launch<KP(), true, true>(c, A, s) : hm_launch<KP(), false, true>(c, A, s);
-        else rc = res ? hm_launch<KP(), true, false>(c, A, s) : hm_launch<KP(), false, false>(c, A, s);
-    });
-    PF_CHECK(ok, PFMI_ERR_UNSUPPORTED, "unsupported kpad %d", c->kpad);
-    PF_TRY(rc);
-    PF_HIP(hipGetLastError());
-    return PFMI_OK;
-}
+int32_t pf_launch_hmc_step(pfmi_ctx *c, int64_t round, hipStream_t s) { return hm_launch_step<HmFamily>(c, "hmc", hm_args(c, round), s); }

@@ -1,9 +1,45 @@
-// hmc_rows.h -- what the chain kernels (hmc_kernel.hip: static HMC, nuts_kernel.hip: NUTS) share: the momentum normals and the two
-// per-row products of the Woodbury passes.
+// hmc_rows.h -- what the chain kernels (hmc_kernel.hip: static HMC, nuts_kernel.hip: NUTS) share, each stated ONCE here: the launch
+// geometry and the LDS budget (HM_NT, HM_LDS_RES, pf_hmc_resident), the launch of a kernel family (hm_launch_step), the momentum normals,
+// the two Woodbury passes of a step (hm_apply_R: wt = R g, both kernels; hm_apply_L: X <- base + e L v, static HMC -- NUTS keeps its copy
+// written out, nuts_kernel.hip says why), the start-point copy of the init kernels and the end of a warm-up transition (hm_warm_end).
 #pragma once
 #include "pfmi_common.h"
+#include "adapt.h"
+
+#define HM_NT 256                      // threads per chain (4 waves)
+#define HM_NW (HM_NT / 64)
+#define HM_LDS_RES (150 * 1024)        // most dynamic LDS the staged factor rows may take (of 160 KB, beside the kernels' static buffers)
+
+// the staged factor rows of one chain fit in LDS beside the reduction buffers
+inline bool pf_hmc_resident(int d, int kpad) { return (size_t)d * kpad * sizeof(double) <= (size_t)HM_LDS_RES; }
 
 #ifdef __HIPCC__
+// One step launch of a kernel family (Family::kernel<KPAD, RES, ADAPT>() is its step or warm kernel; Args carries d and K): one workgroup
+// per chain, the factor rows in dynamic LDS when they fit, counted under the plan name "<plan>[_adapt]:<KPAD>:<res|stream>".
+template <class Family, class Args>
+static int32_t hm_launch_step(pfmi_ctx *c, const char *plan, const Args &A, hipStream_t s) {
+    const bool res = pf_hmc_resident(A.d, c->kpad), adapt = c->hmc.adapting;
+    auto go = [&](auto KP, auto RES, auto AD) -> int32_t {
+        auto *kern = Family::template kernel<KP(), RES(), AD()>();
+        if (RES()) PF_TRY(pf_raise_lds_limit(c, reinterpret_cast<const void *>(kern), HM_LDS_RES));
+        char name[32];
+        snprintf(name, sizeof name, "%s%s:%d:%s", plan, AD() ? "_adapt" : "", KP(), RES() ? "res" : "stream");
+        ++c->hmc_plans[name];
+        hipLaunchKernelGGL(kern, dim3(A.K), dim3(HM_NT), RES() ? (size_t)A.d * KP() * sizeof(double) : 0, s, A);
+        return PFMI_OK;
+    };
+    int32_t rc = PFMI_OK;
+    const bool ok = pf_dispatch_kpad<4, 8, 12, 16, 20, 32, 64>(c->kpad, [&](auto KP) {
+        const std::true_type Y;
+        const std::false_type N;
+        rc = res ? (adapt ? go(KP, Y, Y) : go(KP, Y, N)) : (adapt ? go(KP, N, Y) : go(KP, N, N));
+    });
+    PF_CHECK(ok, PFMI_ERR_UNSUPPORTED, "unsupported kpad %d", c->kpad);
+    PF_TRY(rc);
+    PF_HIP(hipGetLastError());
+    return PFMI_OK;
+}
+
 // the standard normal of row i of draw n under `seed`: the value pf_randn4(seed, i / 4, n, stream 0) gives row i (full table in global
 // memory: the same values as the LDS copy's)
 __device__ __forceinline__ double hm_normal(uint64_t seed, uint32_t n, int i) {
@@ -38,5 +74,129 @@ __device__ __forceinline__ double hm_row_sub(const double *row, const double *tv
         y = fma(-r.x, tv[c], y); y = fma(-r.y, tv[c + 1], y); y = fma(-r.z, tv[c + 2], y); y = fma(-r.w, tv[c + 3], y);
     }
     return y;
+}
+
+// What the two passes read of a chain: its fit point's factor (rows gVh [d][KPAD] in HBM, T, V's Cholesky factor Vc, the scaling sqa) ...
+struct HmFactor {
+    const double *gVh, *T, *Vc, *sqa;
+};
+// ... and the static LDS the kernel declares for them: the ping-pong buffers of the block reductions (NRED: the widest reduction of the
+// kernel) and three KPAD-long vectors.  The passes name the members of the kernel's one object: an LDS array handed on as a plain pointer
+// loses its address space, and a store to it is merged with the store to HBM in the other branch into one flat store of a selected address.
+// (Lds of the passes: this struct, or a kernel's own with the same members -- the NUTS kernel orders them differently)
+template <int KPAD, int NRED>
+struct HmLds {
+    alignas(16) double red[2 * HM_NW * NRED];
+    alignas(16) double sHead[KPAD], sZ[KPAD], sTv[KPAD];       // (16 bytes: two doubles per LDS access, as for separate arrays)
+};
+// RES: the chain's factor rows [d][KPAD] in dynamic LDS.  A thread reads only the rows it owns (i = tid, tid + NT, ...), in every pass.  The
+// first pass over the factor reads them from HBM and leaves them in LDS; the later ones read the thread's own copy: no staging pass, no
+// barrier.
+#define HM_STAGED_ROWS extern __shared__ __attribute__((aligned(32))) double sVh[]
+
+// wt = R g: z = s . g, w = Vh'z (one block reduction), tv = T'w, y = z - Vh tv, head <- V head.  wt(i) is the caller's element i of the
+// result (double &).  Returns the number of non-finite entries of g.  With RES this pass stages the rows.
+template <int KPAD, bool RES, int NT, int NRED, class Lds, class Wt>
+__device__ __forceinline__ double hm_apply_R(const HmFactor &F, Lds &L, const double *g, int d, int &flip, Wt wt) {
+    HM_STAGED_ROWS;
+    constexpr int NVM = KPAD + 4;                        // KPAD sums + one rider, padded to the multiple of 4 pf_block_sum_mv takes
+    const int tid = threadIdx.x;
+    double w[NVM];
+#pragma unroll
+    for (int j = 0; j < NVM; ++j) w[j] = 0.0;
+    for (int i = tid; i < d; i += NT) {
+        const double gi = g[i], zi = F.sqa[i] * gi;
+        if (RES) hm_row_axpy<KPAD, NVM, true>(F.gVh + (size_t)i * KPAD, sVh + (size_t)i * KPAD, zi, w);
+        else hm_row_axpy<KPAD, NVM, false>(F.gVh + (size_t)i * KPAD, nullptr, zi, w);
+        w[KPAD] += isfinite(gi) ? 0.0 : 1.0;
+    }
+    pf_block_sum_mv<NVM, NRED>(w, L.red, flip);
+    const double nbad = w[KPAD];
+    if (tid < KPAD) {
+        double s = 0.0;
+#pragma unroll
+        for (int b = 0; b < KPAD; ++b) if (b <= tid) s = fma(F.T[b * KPAD + tid], w[b], s);
+        L.sTv[tid] = s;
+    }
+    __syncthreads();
+    const double *rows = RES ? sVh : F.gVh;
+    for (int i = tid; i < d; i += NT) {
+        const double y = hm_row_sub<KPAD>(rows + (size_t)i * KPAD, L.sTv, F.sqa[i] * g[i]);
+        if (i < KPAD) L.sHead[i] = y; else wt(i) = y;
+    }
+    if (tid < KPAD && tid >= d) L.sHead[tid] = 0.0;
+    __syncthreads();
+    if (tid < KPAD && tid < d) {
+        double s = 0.0;
+#pragma unroll
+        for (int b = 0; b < KPAD; ++b) if (b >= tid) s = fma(F.Vc[tid * KPAD + b], L.sHead[b], s);
+        wt(tid) = s;                                     // (row tid is thread tid's own: every thread reads back only rows it wrote)
+    }
+    return nbad;
+}
+
+// X <- base + e L v: z = [V'v_head; v_tail], w = Vh'z (one block reduction), tv = T w, y = s . (z - Vh tv).  v(i) and base(i) are the
+// caller's elements i (v: const double &).  `rider` is summed over the block along with w; summed(total) is called once the sums are
+// there.  staged: an R pass came before in this launch (it did not in the opening launch of a CONTINUE, where this pass stages the rows).
+template <int KPAD, bool RES, int NT, int NRED, class Lds, class Vv, class Base, class Summed>
+__device__ __forceinline__ void hm_apply_L(const HmFactor &F, Lds &L, double *X, double e, double rider, bool staged, int d,
+                                            int &flip, Vv v, Base base, Summed summed) {
+    HM_STAGED_ROWS;
+    constexpr int NVM = KPAD + 4;
+    const int tid = threadIdx.x;
+    const double *rows = RES ? sVh : F.gVh;
+    const auto &sZ = L.sZ;                               // (const: z[i] below is ONE load from a selected address, not two in two branches)
+    __syncthreads();                                     // the head product of the R pass has read sHead
+    if (tid < KPAD) L.sHead[tid] = tid < d ? v(tid) : 0.0;
+    __syncthreads();
+    if (tid < KPAD) {
+        double s = 0.0;
+#pragma unroll
+        for (int b = 0; b < KPAD; ++b) if (b <= tid) s = fma(F.Vc[b * KPAD + tid], L.sHead[b], s);
+        L.sZ[tid] = s;
+    }
+    __syncthreads();
+    double w[NVM];
+#pragma unroll
+    for (int j = 0; j < NVM; ++j) w[j] = 0.0;
+    if (RES && !staged) {
+        for (int i = tid; i < d; i += NT)
+            hm_row_axpy<KPAD, NVM, true>(F.gVh + (size_t)i * KPAD, sVh + (size_t)i * KPAD, i < KPAD ? sZ[i] : v(i), w);
+    } else {
+        for (int i = tid; i < d; i += NT) hm_row_axpy<KPAD, NVM, false>(rows + (size_t)i * KPAD, nullptr, i < KPAD ? sZ[i] : v(i), w);
+    }
+    w[KPAD] = rider;
+    pf_block_sum_mv<NVM, NRED>(w, L.red, flip);
+    summed(w[KPAD]);
+    if (tid < KPAD) {
+        double s = 0.0;
+#pragma unroll
+        for (int b = 0; b < KPAD; ++b) if (b >= tid) s = fma(F.T[tid * KPAD + b], w[b], s);
+        L.sTv[tid] = s;
+    }
+    __syncthreads();
+    for (int i = tid; i < d; i += NT) {
+        const double y = hm_row_sub<KPAD>(rows + (size_t)i * KPAD, L.sTv, i < KPAD ? sZ[i] : v(i));
+        X[i] = fma(e, F.sqa[i] * y, base(i));
+    }
+}
+
+// the init kernels: the start point becomes the chain's state and the closure's first input
+__device__ __forceinline__ void hm_copy_start(const double *x0, double *X, double *x, int d) {
+    for (int i = threadIdx.x; i < d; i += HM_NT) { const double v = x0[i]; X[i] = v; x[i] = v; }
+}
+
+// The end of warm-up transition t - 1 (t transitions made, t0 of them warm-up), by thread 0 of the chain: its PfWarmRow (ad: [K] adaptation
+// states, then the traces [K][t0]), the update on the statistic a, the state and the step size of transition t stored -- exp(le) while t
+// is a warm-up transition, exp(leb) after the last one.  Returns that step size.
+__device__ __forceinline__ double hm_warm_end(PfAdapt *ad, double *eps_out, int K, int k, int64_t t, int64_t t0, double eps, double a, int div,
+                                              int nleap) {
+    PfWarmRow *tr = reinterpret_cast<PfWarmRow *>(ad + K) + (size_t)k * t0 + (t - 1);
+    tr->eps = eps; tr->acc = a; tr->div = div; tr->nleap = nleap;
+    PfAdapt Ad = ad[k];
+    const double le = pf_adapt_update(Ad, a);
+    const double en = pf_adapt_pick(Ad, t < t0 ? le : Ad.leb, eps);
+    ad[k] = Ad; eps_out[k] = en;
+    return en;
 }
 #endif

@@ -4,6 +4,10 @@
 // checkpoints instead of recursion (Phan, Pradhan & Jankowiak 2019, "Composable effects for flexible and accelerated probabilistic
 // programming in NumPyro"; Lao & Dillon 2019, "Unrolled implementation of No-U-Turn Sampler").
 //
+// What a step shares with static HMC is hmc_rows.h: the R pass (hm_apply_R), the thread count, the LDS budget, the launch helper and the end
+// of a warm-up transition.  The L pass is static HMC's statement for statement but stays written out here (see the rule for the base
+// addresses in nt_step_body).
+//
 // As in hmc_kernel.hip the run is cut into ROUNDS: one call of the closure on all K columns of X, then one launch of pf_nuts_step_kernel (one
 // workgroup per chain), which consumes the evaluation -- exactly ONE leapfrog step of every running chain -- and writes the next trial
 // point.  The round count is not known up front, so the rounds are scheduled as the closure L-BFGS's are (lbfgs_closure_kernel.hip): a few
@@ -33,12 +37,8 @@
 // the two progress counters.  A chain's output depends on nothing but its own inputs.
 #include "pfmi_common.h"
 #include "hmc_rows.h"
-#include "adapt.h"
 #include <float.h>
 
-#define NT_NT 256                      // threads per chain (4 waves)
-#define NT_NW (NT_NT / 64)
-#define NT_LDS_RES (150 * 1024)        // most dynamic LDS the staged factor rows may take (pf_hmc_resident's rule)
 #define NT_MAXD 10                     // deepest tree: 2^10 - 1 leaves per transition
 #define NT_NDOT 24                     // |v|^2, two dot products per checkpoint, two of the full tree, padded to a multiple of 4
 
@@ -92,11 +92,9 @@ __device__ __forceinline__ double nt_logaddexp(double a, double b) {
     return fmax(a, b) + log1p(exp(-fabs(a - b)));
 }
 
-__global__ __launch_bounds__(NT_NT) void pf_nuts_init_kernel(NtArgs A) {
+__global__ __launch_bounds__(HM_NT) void pf_nuts_init_kernel(NtArgs A) {
     const int k = blockIdx.x, d = A.d;
-    const double *x0 = A.x0 + (size_t)k * d;
-    double *X = A.X + (size_t)k * d, *x = A.blk + (size_t)k * A.nslot * d + (size_t)NT_X * d;
-    for (int i = threadIdx.x; i < d; i += NT_NT) { const double v = x0[i]; X[i] = v; x[i] = v; }
+    hm_copy_start(A.x0 + (size_t)k * d, A.X + (size_t)k * d, A.blk + (size_t)k * A.nslot * d + (size_t)NT_X * d, d);
     if (threadIdx.x == 0) {
         NtChain S = {};
         S.phase = NT_START;
@@ -120,11 +118,15 @@ __device__ __forceinline__ void nt_step_body(const NtArgs &A_) {
         if constexpr (ADAPT) return 0;
         else return A.record;
     };
-    extern __shared__ __attribute__((aligned(32))) double sVh[];      // RES: the chain's factor rows [d][KPAD]
     constexpr int NVM = KPAD + 4;                        // KPAD sums + one rider (pf_block_sum_mv takes multiples of 4)
     constexpr int NRED = NVM > NT_NDOT ? NVM : NT_NDOT;
-    __shared__ double red[2 * NT_NW * NRED];
-    __shared__ double sHead[KPAD], sZ[KPAD], sTv[KPAD];
+    // (HmLds of hmc_rows.h with the vectors first: with the reduction buffers first pf_nuts_warm_kernel<12, true> moves a seventh scalar
+    // register into a lane)
+    struct NtLds {
+        alignas(16) double sTv[KPAD], sZ[KPAD], sHead[KPAD];
+        alignas(16) double red[2 * HM_NW * NRED];
+    };
+    __shared__ NtLds L;
     const int k = blockIdx.x, tid = threadIdx.x, d = A.d, K = A.K;
     int flip = 0;
     // the chain's scalars, its step size, seed and fit point go through LDS: the values (and the factor's addresses, which depend on the
@@ -140,11 +142,12 @@ __device__ __forceinline__ void nt_step_body(const NtArgs &A_) {
     if (!(idle_in && !A.reopen)) {
         const int p = sPt;
         const size_t kd = (size_t)k * d;
-        // In the warm kernel the base addresses that live through the whole launch pass through an empty asm, which makes each an opaque
-        // value in scalar registers.  Left as the result of the merged eight-dword argument load they are a tuple the register allocator
-        // splits around the update and REMATERIALISES, and the spill slot it leaves behind (never read, never written) would still make
-        // every wave reserve scratch; an opaque value is moved into a lane of a vector register instead, as in the plain kernel, which
-        // keeps its loads as they are.
+        // The rule for the base addresses: in the warm kernel, and only there, the argument addresses that live through the whole launch pass
+        // through an empty asm, which makes each an opaque value in scalar registers.  Left as the result of the merged eight-dword argument
+        // load they are a tuple the register allocator splits around the update and REMATERIALISES, and the spill slot it leaves behind
+        // (never read, never written) makes every wave reserve scratch; an opaque value is moved into a lane of a vector register instead.
+        // The plain kernel keeps its loads as they are and has no such slot as long as the L pass below is written out: through
+        // hm_apply_L no rule tried held both its registers and its time (profiles/chain_kernels.md).
         auto karg = [&](auto *const &f) {
             using P = std::remove_cv_t<std::remove_reference_t<decltype(f)>>;
             if constexpr (ADAPT) {
@@ -161,11 +164,13 @@ __device__ __forceinline__ void nt_step_body(const NtArgs &A_) {
 #define V_(slot, i) B[(size_t)(slot) * d + (i)]
         double eps = sEps;
         const uint64_t seed = sSeed;
-        bool staged = false;
+        const HmFactor F = {gVh, T, Vc, sqa};
+        HM_STAGED_ROWS;                                      // (the L pass below reads the rows the R pass staged)
         auto vrow = [&](int i) -> const double * {
             if constexpr (RES) return sVh + (size_t)i * KPAD;
             else return gVh + (size_t)i * KPAD;
         };
+        bool staged = false;                                 // an R pass came before the L pass (hmc_rows.h)
         bool open = idle_in, drift = false;
         int wend = 0;                                        // ADAPT: this launch ended a warm-up transition (2: a divergent one)
         int bslot = -1;                                      // the drift's base: a slot, or (-1) the trial point itself
@@ -176,53 +181,20 @@ __device__ __forceinline__ void nt_step_body(const NtArgs &A_) {
             const size_t pr = ((size_t)A.prow * K + k);
             if (rec()) {                                  // what the closure saw and what it answered, before X is rewritten
                 double *pX = A.pX + pr * d, *pout = A.pout + (size_t)A.prow * ((size_t)K * (d + 1));
-                for (int i = tid; i < d; i += NT_NT) { pX[i] = X[i]; pout[K + kd + i] = g[i]; }
+                for (int i = tid; i < d; i += HM_NT) { pX[i] = X[i]; pout[K + kd + i] = g[i]; }
                 if (tid == 0) pout[k] = lpt;
             }
-            // ---- wt = R g: z = s . g, w = Vh'z, tv = T'w, y = z - Vh tv, head <- V head                       (reduction 1)
-            double nbad;
-            {
-                double w[NVM];
-#pragma unroll
-                for (int q = 0; q < NVM; ++q) w[q] = 0.0;
-                for (int i = tid; i < d; i += NT_NT) {
-                    const double gi = g[i], zi = sqa[i] * gi;
-                    if (RES) hm_row_axpy<KPAD, NVM, true>(gVh + (size_t)i * KPAD, sVh + (size_t)i * KPAD, zi, w);
-                    else hm_row_axpy<KPAD, NVM, false>(gVh + (size_t)i * KPAD, nullptr, zi, w);
-                    w[KPAD] += isfinite(gi) ? 0.0 : 1.0;
-                }
-                staged = true;
-                pf_block_sum_mv<NVM, NRED>(w, red, flip);
-                nbad = w[KPAD];
-                if (tid < KPAD) {
-                    double s = 0.0;
-#pragma unroll
-                    for (int b = 0; b < KPAD; ++b) if (b <= tid) s = fma(T[b * KPAD + tid], w[b], s);
-                    sTv[tid] = s;
-                }
-            }
-            __syncthreads();
-            for (int i = tid; i < d; i += NT_NT) {
-                const double y = hm_row_sub<KPAD>(vrow(i), sTv, sqa[i] * g[i]);
-                if (i < KPAD) sHead[i] = y; else V_(NT_WT, i) = y;
-            }
-            if (tid < KPAD && tid >= d) sHead[tid] = 0.0;
-            __syncthreads();
-            if (tid < KPAD && tid < d) {
-                double s = 0.0;
-#pragma unroll
-                for (int b = 0; b < KPAD; ++b) if (b >= tid) s = fma(Vc[tid * KPAD + b], sHead[b], s);
-                V_(NT_WT, tid) = s;                                 // (row tid is thread tid's own: every thread reads back only rows it wrote)
-            }
+            const double nbad = hm_apply_R<KPAD, RES, HM_NT, NRED>(F, L, g, d, flip, [&](int i) -> double & { return V_(NT_WT, i); });     // (reduction 1)
+            staged = true;
             const bool badg = nbad > 0.0 || !isfinite(lpt);
             if (S.phase == NT_START) {
-                for (int i = tid; i < d; i += NT_NT) V_(NT_WG, i) = badg ? 0.0 : V_(NT_WT, i);
+                for (int i = tid; i < d; i += HM_NT) V_(NT_WG, i) = badg ? 0.0 : V_(NT_WT, i);
                 S.lp = badg ? -DBL_MAX : lpt;
                 S.dead = badg ? 1 : 0;
                 open = true;
                 if (rec()) {
                     double *pv = A.pv + pr * d;
-                    for (int i = tid; i < d; i += NT_NT) pv[i] = 0.0;
+                    for (int i = tid; i < d; i += HM_NT) pv[i] = 0.0;
                     if (tid == 0) {
                         pfmi_nuts_event E = {};
                         E.t = -1; E.j = -1; E.n = -1; E.flags = badg ? PFMI_NUTS_EV_DIVERGENT : 0;
@@ -240,7 +212,7 @@ __device__ __forceinline__ void nt_step_body(const NtArgs &A_) {
                 double w[NT_NDOT];
 #pragma unroll
                 for (int q = 0; q < NT_NDOT; ++q) w[q] = 0.0;
-                for (int i = tid; i < d; i += NT_NT) {
+                for (int i = tid; i < d; i += HM_NT) {
                     const double vl = fma(hk, V_(NT_WT, i), V_(NT_V, i)), rs = V_(NT_RHOS, i) + vl;
                     V_(NT_V, i) = vl; V_(NT_RHOS, i) = rs;
                     if (pv) pv[i] = vl;
@@ -259,14 +231,14 @@ __device__ __forceinline__ void nt_step_body(const NtArgs &A_) {
                     if (c < nchk) {
                         const int sv = ckv + imax - c, sr = ckr + imax - c;
                         double a0 = 0.0, a1 = 0.0;
-                        for (int i = tid; i < d; i += NT_NT) {
+                        for (int i = tid; i < d; i += HM_NT) {
                             const double vc = V_(sv, i), rsub = (V_(NT_RHOS, i) - V_(sr, i)) + vc;
                             a0 = fma(rsub, vc, a0);
                             a1 = fma(rsub, V_(NT_V, i), a1);
                         }
                         w[1 + 2 * c] = a0; w[2 + 2 * c] = a1;
                     }
-                pf_block_sum_mv<NT_NDOT, NRED>(w, red, flip);
+                pf_block_sum_mv<NT_NDOT, NRED>(w, L.red, flip);
                 // ---- decide (every thread, on the same values)
                 const double Hl = -lpt + 0.5 * w[0], dH = Hl - S.H0, lw = -dH;
                 const bool div = badg || !isfinite(Hl) || dH > 1000.0;
@@ -306,7 +278,7 @@ __device__ __forceinline__ void nt_step_body(const NtArgs &A_) {
                 if constexpr (ADAPT) warm = __builtin_amdgcn_readfirstlane(row < 0 ? 1 : 0) != 0;
                 double *dr = karg(A.draws) + ((size_t)k * A.T + (warm ? 0 : row)) * d;
                 const int en = dir > 0 ? 1 : 0;
-                for (int i = tid; i < d; i += NT_NT) {
+                for (int i = tid; i < d; i += HM_NT) {
                     double xsi = V_(NT_XS, i), wsi = V_(NT_WS, i);
                     if (sel) { xsi = X[i]; wsi = V_(NT_WT, i); V_(NT_XS, i) = xsi; V_(NT_WS, i) = wsi; }
                     double xci = V_(NT_XC, i), wci = V_(NT_WC, i);
@@ -329,7 +301,7 @@ __device__ __forceinline__ void nt_step_body(const NtArgs &A_) {
                     ++S.t;
                     if (S.t < A.t_end) open = true;
                     else {
-                        for (int i = tid; i < d; i += NT_NT) X[i] = V_(NT_X, i);      // an idle chain's column stays a valid point
+                        for (int i = tid; i < d; i += HM_NT) X[i] = V_(NT_X, i);      // an idle chain's column stays a valid point
                         S.phase = NT_IDLE; S.fin_round = A.round;
                     }
                 } else if (complete) {
@@ -339,13 +311,13 @@ __device__ __forceinline__ void nt_step_body(const NtArgs &A_) {
                     S.dir = ndir;
                     const int e = ndir > 0 ? 1 : 0;
                     const double hk2 = (ndir > 0 ? 0.5 : -0.5) * eps;
-                    for (int i = tid; i < d; i += NT_NT) { V_(NT_RHOS, i) = 0.0; V_(NT_V, i) = fma(hk2, V_(NT_WE + e, i), V_(NT_VE + e, i)); }
+                    for (int i = tid; i < d; i += HM_NT) { V_(NT_RHOS, i) = 0.0; V_(NT_V, i) = fma(hk2, V_(NT_WE + e, i), V_(NT_VE + e, i)); }
                     bslot = NT_XE + e;
                     drift = true;
                 } else {
                     // ---- the next leaf of the sub-tree
                     S.n = n + 1;
-                    for (int i = tid; i < d; i += NT_NT) V_(NT_V, i) = fma(hk, V_(NT_WT, i), V_(NT_V, i));
+                    for (int i = tid; i < d; i += HM_NT) V_(NT_V, i) = fma(hk, V_(NT_WT, i), V_(NT_V, i));
                     drift = true;
                 }
             }
@@ -354,15 +326,7 @@ __device__ __forceinline__ void nt_step_body(const NtArgs &A_) {
             // ---- the warm-up transition S.t - 1 has ended: its trace, the update, the step size of the transition that opens below
             // (here and not in the branch above: fewer uniform values are live beside the constants of sqrt and exp)
             if (wend) {
-                if (tid == 0) {
-                    const double a = S.sacc / (double)S.nleaf;
-                    PfWarmRow *tr = reinterpret_cast<PfWarmRow *>(A.ad + K) + (size_t)k * A.t0 + (S.t - 1);
-                    tr->eps = eps; tr->acc = a; tr->div = wend - 1; tr->nleap = S.nleaf;
-                    PfAdapt Ad = A.ad[k];
-                    const double le = pf_adapt_update(Ad, a);
-                    const double en = pf_adapt_pick(Ad, S.t < A.t0 ? le : Ad.leb, eps);
-                    A.ad[k] = Ad; A.eps[k] = en; sEps = en;
-                }
+                if (tid == 0) sEps = hm_warm_end(A.ad, A.eps, K, k, S.t, A.t0, eps, S.sacc / (double)S.nleaf, wend - 1, S.nleaf);
                 __syncthreads();
                 eps = sEps;
             }
@@ -373,7 +337,7 @@ __device__ __forceinline__ void nt_step_body(const NtArgs &A_) {
             const uint32_t nd = (uint32_t)S.t;
             ndir = nt_direction(seed, S.t, 0);
             const double hk = (ndir > 0 ? 0.5 : -0.5) * eps;
-            for (int i = tid; i < d; i += NT_NT) {
+            for (int i = tid; i < d; i += HM_NT) {
                 const double z = hm_normal(seed, nd, i), xi = V_(NT_X, i), wi = V_(NT_WG, i);
                 vv0 = fma(z, z, vv0);
                 V_(NT_XE, i) = xi; V_(NT_XE + 1, i) = xi; V_(NT_VE, i) = z; V_(NT_VE + 1, i) = z; V_(NT_WE, i) = wi; V_(NT_WE + 1, i) = wi;
@@ -387,38 +351,39 @@ __device__ __forceinline__ void nt_step_body(const NtArgs &A_) {
         }
         if (drift) {
             // ---- X <- base + dir e L v: z = [V'v_head; v_tail], w = Vh'z, tv = T w, y = s . (z - Vh tv)          (reduction 3)
+            // (hm_apply_L of hmc_rows.h, written out: see the rule for the base addresses above)
             const double se = ndir > 0 ? eps : -eps;
             __syncthreads();                                 // the head product above has read sHead
-            if (tid < KPAD) sHead[tid] = tid < d ? V_(NT_V, tid) : 0.0;
+            if (tid < KPAD) L.sHead[tid] = tid < d ? V_(NT_V, tid) : 0.0;
             __syncthreads();
             if (tid < KPAD) {
                 double s = 0.0;
 #pragma unroll
-                for (int b = 0; b < KPAD; ++b) if (b <= tid) s = fma(Vc[b * KPAD + tid], sHead[b], s);
-                sZ[tid] = s;
+                for (int b = 0; b < KPAD; ++b) if (b <= tid) s = fma(Vc[b * KPAD + tid], L.sHead[b], s);
+                L.sZ[tid] = s;
             }
             __syncthreads();
             double w[NVM];
 #pragma unroll
             for (int q = 0; q < NVM; ++q) w[q] = 0.0;
             if (RES && !staged) {                            // (the opening launch of PFMI_NUTS_CONTINUE: no R-apply came before)
-                for (int i = tid; i < d; i += NT_NT)
-                    hm_row_axpy<KPAD, NVM, true>(gVh + (size_t)i * KPAD, sVh + (size_t)i * KPAD, i < KPAD ? sZ[i] : V_(NT_V, i), w);
+                for (int i = tid; i < d; i += HM_NT)
+                    hm_row_axpy<KPAD, NVM, true>(gVh + (size_t)i * KPAD, sVh + (size_t)i * KPAD, i < KPAD ? L.sZ[i] : V_(NT_V, i), w);
             } else {
-                for (int i = tid; i < d; i += NT_NT) hm_row_axpy<KPAD, NVM, false>(vrow(i), nullptr, i < KPAD ? sZ[i] : V_(NT_V, i), w);
+                for (int i = tid; i < d; i += HM_NT) hm_row_axpy<KPAD, NVM, false>(vrow(i), nullptr, i < KPAD ? L.sZ[i] : V_(NT_V, i), w);
             }
             w[KPAD] = vv0;
-            pf_block_sum_mv<NVM, NRED>(w, red, flip);
+            pf_block_sum_mv<NVM, NRED>(w, L.red, flip);
             if (open) { S.H0 = -S.lp + 0.5 * w[KPAD]; S.Hc = S.H0; }
             if (tid < KPAD) {
                 double s = 0.0;
 #pragma unroll
                 for (int b = 0; b < KPAD; ++b) if (b >= tid) s = fma(T[tid * KPAD + b], w[b], s);
-                sTv[tid] = s;
+                L.sTv[tid] = s;
             }
             __syncthreads();
-            for (int i = tid; i < d; i += NT_NT) {
-                const double y = hm_row_sub<KPAD>(vrow(i), sTv, i < KPAD ? sZ[i] : V_(NT_V, i));
+            for (int i = tid; i < d; i += HM_NT) {
+                const double y = hm_row_sub<KPAD>(vrow(i), L.sTv, i < KPAD ? L.sZ[i] : V_(NT_V, i));
                 X[i] = fma(se, sqa[i] * y, bslot < 0 ? X[i] : V_(bslot, i));
             }
         }
@@ -440,10 +405,10 @@ __device__ __forceinline__ void nt_step_body(const NtArgs &A_) {
 }
 
 template <int KPAD, bool RES>
-__global__ __launch_bounds__(NT_NT) void pf_nuts_step_kernel(NtArgs A_) { nt_step_body<KPAD, RES, false>(A_); }
+__global__ __launch_bounds__(HM_NT) void pf_nuts_step_kernel(NtArgs A_) { nt_step_body<KPAD, RES, false>(A_); }
 
 template <int KPAD, bool RES>
-__global__ __launch_bounds__(NT_NT) void pf_nuts_warm_kernel(NtArgs A_) { nt_step_body<KPAD, RES, true>(A_); }
+__global__ __launch_bounds__(HM_NT) void pf_nuts_warm_kernel(NtArgs A_) { nt_step_body<KPAD, RES, true>(A_); }
 
 // ---------------------------------------------------------------------------------------------------
 static NtArgs nt_args(pfmi_ctx *c, int64_t round, int64_t prow, bool reopen) {
@@ -468,22 +433,15 @@ size_t pf_nuts_chain_bytes() { return sizeof(NtChain); }
 int pf_nuts_vec_slots(int max_depth) { return NT_VECS + 2 * max_depth; }
 
 int32_t pf_launch_nuts_init(pfmi_ctx *c, hipStream_t s) {
-    hipLaunchKernelGGL(pf_nuts_init_kernel, dim3(c->hmc.K), dim3(NT_NT), 0, s, nt_args(c, 0, 0, false));
+    hipLaunchKernelGGL(pf_nuts_init_kernel, dim3(c->hmc.K), dim3(HM_NT), 0, s, nt_args(c, 0, 0, false));
     PF_HIP(hipGetLastError());
     return PFMI_OK;
 }
 
-template <int KPAD, bool RES, bool ADAPT>
-static int32_t nt_launch(pfmi_ctx *c, const NtArgs &A, hipStream_t s) {
-    const size_t lds = RES ? (size_t)A.d * KPAD * sizeof(double) : 0;
-    auto *kern = ADAPT ? &pf_nuts_warm_kernel<KPAD, RES> : &pf_nuts_step_kernel<KPAD, RES>;
-    if (RES) PF_TRY(pf_raise_lds_limit(c, reinterpret_cast<const void *>(kern), NT_LDS_RES));
-    char name[32];
-    snprintf(name, sizeof name, "%s:%d:%s", ADAPT ? "nuts_adapt" : "nuts", KPAD, RES ? "res" : "stream");
-    ++c->hmc_plans[name];
-    hipLaunchKernelGGL(kern, dim3(A.K), dim3(NT_NT), lds, s, A);
-    return PFMI_OK;
-}
+struct NtFamily {
+    template <int KPAD, bool RES, bool ADAPT>
+    static auto kernel() { return ADAPT ? &pf_nuts_warm_kernel<KPAD, RES> : &pf_nuts_step_kernel<KPAD, RES>; }
+};
 
 // the chains' start flags and the last round in which a chain was still running
 int32_t pf_nuts_chain_flags(pfmi_ctx *c, std::vector<int32_t> &dead, int64_t *last_round) {
@@ -504,15 +462,5 @@ int32_t pf_nuts_chain_flags(pfmi_ctx *c, std::vector<int32_t> &dead, int64_t *la
 // round: the number the launch publishes with its progress word; prow: its row of the recorded path; reopen: the opening launch of
 // PFMI_NUTS_CONTINUE (no closure output is read, every idle chain opens its next transition)
 int32_t pf_launch_nuts_step(pfmi_ctx *c, int64_t round, int64_t prow, bool reopen, hipStream_t s) {
-    const NtArgs A = nt_args(c, round, prow, reopen);
-    const bool res = pf_hmc_resident(A.d, c->kpad);
-    int32_t rc = PFMI_OK;
-    const bool ok = pf_dispatch_kpad<4, 8, 12, 16, 20, 32, 64>(c->kpad, [&](auto KP) {
-        if (c->hmc.adapting) rc = res ? nt_launch<KP(), true, true>(c, A, s) : nt_launch<KP(), false, true>(c, A, s);
-        else rc = res ? nt_launch<KP(), true, false>(c, A, s) : nt_launch<KP(), false, false>(c, A, s);
-    });
-    PF_CHECK(ok, PFMI_ERR_UNSUPPORTED, "unsupported kpad %d", c->kpad);
-    PF_TRY(rc);
-    PF_HIP(hipGetLastError());
-    return PFMI_OK;
+    return hm_launch_step<NtFamily>(c, "nuts", nt_args(c, round, prow, reopen), s);
 }

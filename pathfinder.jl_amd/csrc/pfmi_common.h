@@ -410,8 +410,8 @@ size_t pf_lbc_path_state_bytes(int J);
 int32_t pf_lbc_alloc(pfmi_ctx *c, int K, int J, int d);
 int32_t pf_launch_lbc_init(pfmi_ctx *c, hipStream_t s);
 int32_t pf_launch_lbc_step(pfmi_ctx *c, int64_t round, hipStream_t s);
+// hmc_kernel.hip (what it shares with nuts_kernel.hip -- passes, launch geometry, LDS budget -- is hmc_rows.h)
 size_t pf_hmc_chain_bytes();
-bool pf_hmc_resident(int d, int kpad);
 int32_t pf_launch_hmc_init(pfmi_ctx *c, hipStream_t s);
 int32_t pf_launch_hmc_step(pfmi_ctx *c, int64_t round, hipStream_t s);      // round < 0: open the next trajectory only (no closure output is read)
 int32_t pf_hmc_dead_flags(pfmi_ctx *c, std::vector<int32_t> &dead);

@@ -486,31 +486,52 @@ class Engine:
     # ---- static HMC with a fitted metric (include/pfmi.h: pfmi_hmc_enqueue) ---------------------------------------------------
     HMC_CONTINUE, HMC_RECORD_PATH = 1, 2
 
-    def hmc_enqueue(self, points, x0, seeds, step_size, nleapfrog, ntransitions, cont=False, record_path=False):
-        """K chains of static HMC: chain k uses the metric of fit points[k], starts at x0[:, k] (d, K; ignored with cont=True, may be None),
-        draws its momenta and accept uniforms from seeds[k] and steps by step_size[k].  Enqueues every round; does not wait.  A Python
-        closure that raised is re-raised here."""
+    def _chain_enqueue(self, name, points, x0, seeds, step_size, param, ntransitions, flags, nwarmup=None, target_accept=None):
+        """the one enqueue of both samplers: pfmi_<name>_enqueue, or (nwarmup given) pfmi_<name>_adapt_enqueue, which takes no x0 = None"""
         points = np.ascontiguousarray(points, dtype=np.int64)
         K = len(points)
         seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
         eps = np.ascontiguousarray(np.broadcast_to(np.asarray(step_size, dtype=np.float64), (K,)))
         assert seeds.shape == (K,)
         x0p = None
-        if x0 is not None:
+        if x0 is not None or nwarmup is not None:
             x0 = np.asfortranarray(x0, dtype=np.float64)
             assert x0.shape == (self.d, K), (x0.shape, self.d, K)
             x0p = _d(x0)
-        flags = (self.HMC_CONTINUE if cont else 0) | (self.HMC_RECORD_PATH if record_path else 0)
-        rc = self.L.pfmi_hmc_enqueue(self.ctx, K, points.ctypes.data_as(_i64p), x0p, seeds.ctypes.data_as(C.POINTER(C.c_uint64)), _d(eps),
-                                     int(nleapfrog), int(ntransitions), flags)
+        head = (self.ctx, K, points.ctypes.data_as(_i64p), x0p, seeds.ctypes.data_as(C.POINTER(C.c_uint64)), _d(eps), int(param))
+        if nwarmup is None:
+            rc = getattr(self.L, f"pfmi_{name}_enqueue")(*head, int(ntransitions), int(flags))
+        else:
+            rc = getattr(self.L, f"pfmi_{name}_adapt_enqueue")(*head, int(nwarmup), int(ntransitions), float(target_accept), int(flags))
         if getattr(self.target, "pending_error", None) is not None:
             self.sync()
             self._raise_target_error()
         check(rc)
         self._hmc = (K, int(ntransitions))
-        if not cont:
+        if nwarmup is not None:
+            self._adapt = (K, int(nwarmup))
+        elif not flags & self.HMC_CONTINUE:
             self._adapt = None
         self.hmc_runs += 1
+
+    def _chain_path(self, who, stats, get_path, round0, nrounds, events):
+        """the recorded rounds round0 .. round0 + n - 1 of either sampler"""
+        K, T = self._hmc_run(who)
+        r, _ = stats()
+        n = r - round0 if nrounds is None else nrounds
+        X = np.empty((self.d, K, n), order="F")
+        v = np.empty((self.d, K, n), order="F")
+        o = np.empty((K * (self.d + 1), n), order="F")
+        ev = (np.empty((n, K), dtype=self.NUTS_EVENT),) if events else ()
+        check(get_path(self.ctx, round0, n, _d(X), _d(o), _d(v), *[e.ctypes.data_as(C.c_void_p) for e in ev]))
+        return (X, o[:K].copy(), o[K:].reshape(self.d, K, n, order="F").copy(), v) + ev
+
+    def hmc_enqueue(self, points, x0, seeds, step_size, nleapfrog, ntransitions, cont=False, record_path=False):
+        """K chains of static HMC: chain k uses the metric of fit points[k], starts at x0[:, k] (d, K; ignored with cont=True, may be None),
+        draws its momenta and accept uniforms from seeds[k] and steps by step_size[k].  Enqueues every round; does not wait.  A Python
+        closure that raised is re-raised here."""
+        flags = (self.HMC_CONTINUE if cont else 0) | (self.HMC_RECORD_PATH if record_path else 0)
+        self._chain_enqueue("hmc", points, x0, seeds, step_size, nleapfrog, ntransitions, flags)
 
     # ---- chain diagnostics (include/pfmi.h: pfmi_chain_diagnostics) ---------------------------------------------------------------
     CHAIN_SRC_HMC, CHAIN_SRC_HOST, CHAIN_WITH_LP = 0, 1, 1
@@ -560,14 +581,7 @@ class Engine:
 
     def hmc_path(self, round0=0, nrounds=None):
         """PFMI_HMC_RECORD_PATH: (X (d, K, n), logp (K, n), grad (d, K, n), v (d, K, n)) of rounds round0 .. round0 + n - 1"""
-        K, T = self._hmc_run("hmc_path")
-        r, _ = self.hmc_stats()
-        n = r - round0 if nrounds is None else nrounds
-        X = np.empty((self.d, K, n), order="F")
-        v = np.empty((self.d, K, n), order="F")
-        o = np.empty((K * (self.d + 1), n), order="F")
-        check(self.L.pfmi_hmc_get_path(self.ctx, round0, n, _d(X), _d(o), _d(v)))
-        return X, o[:K].copy(), o[K:].reshape(self.d, K, n, order="F").copy(), v
+        return self._chain_path("hmc_path", self.hmc_stats, self.L.pfmi_hmc_get_path, round0, nrounds, False)
 
     def hmc_stats(self):
         """(rounds, closure columns) of the last hmc_enqueue"""
@@ -584,58 +598,21 @@ class Engine:
     def nuts_enqueue(self, points, x0, seeds, step_size, max_depth, ntransitions, cont=False, record_path=False):
         """K chains of multinomial NUTS: the arguments of hmc_enqueue with max_depth (1 .. 10) in place of the leapfrog count.  Issues the first
         window of rounds and returns; nuts_pump / nuts_wait issue the rest.  A Python closure that raised is re-raised here."""
-        points = np.ascontiguousarray(points, dtype=np.int64)
-        K = len(points)
-        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
-        eps = np.ascontiguousarray(np.broadcast_to(np.asarray(step_size, dtype=np.float64), (K,)))
-        assert seeds.shape == (K,)
-        x0p = None
-        if x0 is not None:
-            x0 = np.asfortranarray(x0, dtype=np.float64)
-            assert x0.shape == (self.d, K), (x0.shape, self.d, K)
-            x0p = _d(x0)
         flags = (self.NUTS_CONTINUE if cont else 0) | (self.NUTS_RECORD_PATH if record_path else 0)
-        rc = self.L.pfmi_nuts_enqueue(self.ctx, K, points.ctypes.data_as(_i64p), x0p, seeds.ctypes.data_as(C.POINTER(C.c_uint64)), _d(eps),
-                                      int(max_depth), int(ntransitions), flags)
-        if getattr(self.target, "pending_error", None) is not None:
-            self.sync()
-            self._raise_target_error()
-        check(rc)
-        self._hmc = (K, int(ntransitions))
-        if not cont:
-            self._adapt = None
-        self.hmc_runs += 1
+        self._chain_enqueue("nuts", points, x0, seeds, step_size, max_depth, ntransitions, flags)
 
     # ---- device-resident warm-up (include/pfmi.h: pfmi_hmc_adapt_enqueue, pfmi_nuts_adapt_enqueue) -----------------------------------
     ADAPT_KEPT_STEP = 1
-
-    def _adapt_enqueue(self, fn, points, x0, seeds, step_size0, param, nwarmup, ntransitions, target_accept, flags):
-        points = np.ascontiguousarray(points, dtype=np.int64)
-        K = len(points)
-        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
-        eps = np.ascontiguousarray(np.broadcast_to(np.asarray(step_size0, dtype=np.float64), (K,)))
-        assert seeds.shape == (K,)
-        x0 = np.asfortranarray(x0, dtype=np.float64)
-        assert x0.shape == (self.d, K), (x0.shape, self.d, K)
-        rc = fn(self.ctx, K, points.ctypes.data_as(_i64p), _d(x0), seeds.ctypes.data_as(C.POINTER(C.c_uint64)), _d(eps), int(param),
-                int(nwarmup), int(ntransitions), float(target_accept), int(flags))
-        if getattr(self.target, "pending_error", None) is not None:
-            self.sync()
-            self._raise_target_error()
-        check(rc)
-        self._hmc = (K, int(ntransitions))
-        self._adapt = (K, int(nwarmup))
-        self.hmc_runs += 1
 
     def hmc_adapt_enqueue(self, points, x0, seeds, step_size0, nleapfrog, nwarmup, ntransitions, target_accept=0.8, flags=0):
         """hmc_enqueue with `nwarmup` warm-up transitions in front whose step sizes are adapted on the device after every transition (dual
         averaging towards target_accept, from step_size0); the rows of hmc_get are the `ntransitions` sampling transitions.  One enqueue;
         does not wait.  flags must be 0."""
-        self._adapt_enqueue(self.L.pfmi_hmc_adapt_enqueue, points, x0, seeds, step_size0, nleapfrog, nwarmup, ntransitions, target_accept, flags)
+        self._chain_enqueue("hmc", points, x0, seeds, step_size0, nleapfrog, ntransitions, flags, nwarmup, target_accept)
 
     def nuts_adapt_enqueue(self, points, x0, seeds, step_size0, max_depth, nwarmup, ntransitions, target_accept=0.8, flags=0):
         """nuts_enqueue with `nwarmup` adaptive warm-up transitions in front (hmc_adapt_enqueue); nuts_pump / nuts_wait issue the rounds"""
-        self._adapt_enqueue(self.L.pfmi_nuts_adapt_enqueue, points, x0, seeds, step_size0, max_depth, nwarmup, ntransitions, target_accept, flags)
+        self._chain_enqueue("nuts", points, x0, seeds, step_size0, max_depth, ntransitions, flags, nwarmup, target_accept)
 
     def adapt_get(self):
         """the last adaptive run's warm-up: dict of step_size (K,) the sampling transitions' step sizes, eps_trace, accept_trace (K, W),
@@ -678,15 +655,7 @@ class Engine:
     def nuts_path(self, round0=0, nrounds=None):
         """PFMI_NUTS_RECORD_PATH: (X (d, K, n), logp (K, n), grad (d, K, n), v (d, K, n), events (n, K) of NUTS_EVENT) of rounds
         round0 .. round0 + n - 1; v is the synchronised momentum of the leaf the round finished"""
-        K, T = self._hmc_run("nuts_path")
-        r, _ = self.nuts_stats()
-        n = r - round0 if nrounds is None else nrounds
-        X = np.empty((self.d, K, n), order="F")
-        v = np.empty((self.d, K, n), order="F")
-        o = np.empty((K * (self.d + 1), n), order="F")
-        ev = np.empty((n, K), dtype=self.NUTS_EVENT)
-        check(self.L.pfmi_nuts_get_path(self.ctx, round0, n, _d(X), _d(o), _d(v), ev.ctypes.data_as(C.c_void_p)))
-        return X, o[:K].copy(), o[K:].reshape(self.d, K, n, order="F").copy(), v, ev
+        return self._chain_path("nuts_path", self.nuts_stats, self.L.pfmi_nuts_get_path, round0, nrounds, True)
 
     # ---- pool / PSIS / resample -------------------------------------------------------------------------
     def pool_build(self, N_r, points, seeds):

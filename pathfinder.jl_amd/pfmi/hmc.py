@@ -3,9 +3,10 @@ pfmi_hmc_enqueue, pfmi_nuts_enqueue).
 
 The reference's worked example docs/src/examples/initializing-hmc.md, third way: "use Pathfinder's metric estimate for sampling"
 (AdvancedHMC.RankUpdateEuclideanMetric(result.fit_distribution.Sigma), ext/PathfinderAdvancedHMCExt.jl:17-23) -- here the chains run
-where the fits already are.  Scope: a fixed number of leapfrog steps per transition, Metropolis correction, full momentum refresh; no
-NUTS.  The target must be a device closure with a gradient (DeviceCallbackTarget(..., grad_fn=...), TorchDeviceTarget(..., grad=...));
-one engine only.  `nuts` below is the dynamic sampler with the same starts, metric and step-size adaptation."""
+where the fits already are.  `hmc`: a fixed number of leapfrog steps per transition, Metropolis correction, full momentum refresh.
+`nuts`: multinomial NUTS, trees of at most 2^max_depth - 1 leapfrog steps.  Both share one driver (`_run`): the same starts, metric,
+seeds and step-size adaptation.  The target must be a device closure with a gradient (DeviceCallbackTarget(..., grad_fn=...),
+TorchDeviceTarget(..., grad=...)); one engine only."""
 import sys
 import types
 from dataclasses import dataclass, field
@@ -156,62 +157,6 @@ def _check_adapt(adapt, auto, nwarmup):
     return adapt == "device"
 
 
-def hmc(result, ndraws, *, nchains=None, nwarmup=0, step_size="auto", nleapfrog=8, rng=None, target_accept=0.8, window=10, adapt="windows"):
-    """`ndraws` transitions of `nchains` chains of static HMC from a PathfinderResult / MultiPathfinderResult.
-
-    Chain c starts at result.draws[:, c] (resample(result, nchains, replace=False) first gives distinct starts) and uses the best fit of
-    the run that draw came from as its metric.  step_size: a number, one per chain, or "auto": d^(-1/4), adapted per chain during the
-    `nwarmup` warm-up transitions between windows of `window` transitions by dual averaging on the window's mean acceptance
-    (dual_averaging_update); the warm-up draws are discarded and sampling uses the averaged step size.  adapt="device" (step_size="auto"
-    only): the device updates every chain's step size after every warm-up transition (include/pfmi.h: pfmi_hmc_adapt_enqueue); warm-up and
-    sampling are ONE enqueue, and the result's `warmup` holds the traces."""
-    eng, starts, pts, token = _starts_and_points(result)
-    if eng is None:
-        raise ValueError("pfmi.hmc needs a result whose fits are still on an engine")
-    eng.check_token(token, "pfmi.hmc")
-    if not getattr(eng.target, "has_device_gradient", False):
-        raise ValueError("pfmi.hmc needs a device closure target with a gradient (built-in targets, host closures and device closures "
-                         "without a gradient are not supported)")
-    nchains = starts.shape[1] if nchains is None else int(nchains)
-    if not 1 <= nchains <= starts.shape[1]:
-        raise ValueError(f"nchains must be in 1 .. {starts.shape[1]} (the result's draws)")
-    d = starts.shape[0]
-    x0 = np.asfortranarray(starts[:, :nchains])
-    pts = pts[:nchains]
-    rng = rng if rng is not None else HostRNG(0)
-    seeds = rng.rand_u64(nchains)
-    auto = isinstance(step_size, str)
-    if auto and step_size != "auto":
-        raise ValueError('step_size must be a number, an array of nchains numbers or "auto"')
-    eps = np.full(nchains, d ** -0.25) if auto else np.broadcast_to(np.asarray(step_size, dtype=np.float64), (nchains,)).copy()
-    if _check_adapt(adapt, auto, int(nwarmup)):
-        eng.hmc_adapt_enqueue(pts, x0, seeds, eps, nleapfrog, int(nwarmup), int(ndraws), target_accept)
-        eng.hmc_wait()
-        got, warm = eng.hmc_get(), eng.adapt_get()
-        return HMCResult(got["draws"], got["logp"], got["accept_prob"], got["energy_error"], got["divergent"], warm.pop("step_size"),
-                         np.array(pts), int(nleapfrog), int(nwarmup), eng, eng.hmc_runs, warmup=warm)
-    done, first = 0, True
-    if nwarmup > 0:
-        state = dual_averaging_init(eps)
-        ebar = eps
-        while done < nwarmup:
-            n = min(int(window), nwarmup - done)
-            eng.hmc_enqueue(pts, x0, seeds, eps, nleapfrog, n, cont=not first)
-            eng.hmc_wait()
-            first = False
-            done += n
-            if auto:
-                acc = eng.hmc_get(draws=False)["accept_prob"].mean(axis=1)
-                state, eps, ebar = dual_averaging_update(state, acc, target_accept)
-        if auto:
-            eps = np.asarray(ebar, dtype=np.float64)
-    eng.hmc_enqueue(pts, x0, seeds, eps, nleapfrog, int(ndraws), cont=not first)
-    eng.hmc_wait()
-    got = eng.hmc_get()
-    return HMCResult(got["draws"], got["logp"], got["accept_prob"], got["energy_error"], got["divergent"], np.array(eps), np.array(pts),
-                     int(nleapfrog), int(nwarmup), eng, eng.hmc_runs)
-
-
 @dataclass
 class NUTSResult(HMCResult):
     """the fields of HMCResult (nleapfrog is 0: the trajectory length is dynamic) and the trees' statistics"""
@@ -229,19 +174,17 @@ class NUTSResult(HMCResult):
         return "\n".join(lines)
 
 
-def nuts(result, ndraws, *, nchains=None, nwarmup=0, step_size="auto", max_depth=10, rng=None, target_accept=0.8, window=10, adapt="windows"):
-    """`ndraws` transitions of `nchains` chains of multinomial NUTS from a PathfinderResult / MultiPathfinderResult: the starts, metrics,
-    seeds and step-size rule of `hmc` (dual averaging between windows of `window` warm-up transitions on the windows' mean accept_prob,
-    the mean over a tree's leaves of min(1, exp(H0 - H))), with trees of at most 2^max_depth - 1 leapfrog steps instead of a fixed count.
-    adapt="device": as for `hmc`, one enqueue whose warm-up adapts on the device after every transition (pfmi_nuts_adapt_enqueue)."""
+def _run(name, result, ndraws, nchains, nwarmup, step_size, param, rng, target_accept, window, adapt):
+    """the driver behind hmc() and nuts(): `name` is the sampler ("hmc" / "nuts"), `param` its nleapfrog / max_depth"""
+    is_nuts = name == "nuts"
     eng, starts, pts, token = _starts_and_points(result)
     if eng is None:
-        raise ValueError("pfmi.nuts needs a result whose fits are still on an engine")
-    eng.check_token(token, "pfmi.nuts")
+        raise ValueError(f"pfmi.{name} needs a result whose fits are still on an engine")
+    eng.check_token(token, f"pfmi.{name}")
     if not getattr(eng.target, "has_device_gradient", False):
-        raise ValueError("pfmi.nuts needs a device closure target with a gradient (built-in targets, host closures and device closures "
+        raise ValueError(f"pfmi.{name} needs a device closure target with a gradient (built-in targets, host closures and device closures "
                          "without a gradient are not supported)")
-    if not 1 <= int(max_depth) <= 10:
+    if is_nuts and not 1 <= int(param) <= 10:
         raise ValueError("max_depth must be in 1 .. 10")
     nchains = starts.shape[1] if nchains is None else int(nchains)
     if not 1 <= nchains <= starts.shape[1]:
@@ -255,34 +198,58 @@ def nuts(result, ndraws, *, nchains=None, nwarmup=0, step_size="auto", max_depth
     if auto and step_size != "auto":
         raise ValueError('step_size must be a number, an array of nchains numbers or "auto"')
     eps = np.full(nchains, d ** -0.25) if auto else np.broadcast_to(np.asarray(step_size, dtype=np.float64), (nchains,)).copy()
+    enqueue, wait = (eng.nuts_enqueue, eng.nuts_wait) if is_nuts else (eng.hmc_enqueue, eng.hmc_wait)
+    warm = None
     if _check_adapt(adapt, auto, int(nwarmup)):
-        eng.nuts_adapt_enqueue(pts, x0, seeds, eps, max_depth, int(nwarmup), int(ndraws), target_accept)
-        eng.nuts_wait()
+        (eng.nuts_adapt_enqueue if is_nuts else eng.hmc_adapt_enqueue)(pts, x0, seeds, eps, param, int(nwarmup), int(ndraws), target_accept)
+        wait()
         got, warm = eng.hmc_get(), eng.adapt_get()
-        depth, nleap = eng.nuts_get_stats()
-        return NUTSResult(got["draws"], got["logp"], got["accept_prob"], got["energy_error"], got["divergent"], warm.pop("step_size"),
-                          np.array(pts), 0, int(nwarmup), eng, eng.hmc_runs, depth, nleap, int(max_depth), warmup=warm)
-    done, first = 0, True
-    if nwarmup > 0:
-        state = dual_averaging_init(eps)
-        ebar = eps
-        while done < nwarmup:
-            n = min(int(window), nwarmup - done)
-            eng.nuts_enqueue(pts, x0, seeds, eps, max_depth, n, cont=not first)
-            eng.nuts_wait()
-            first = False
-            done += n
+        eps = warm.pop("step_size")
+    else:
+        done, first = 0, True
+        if nwarmup > 0:
+            state = dual_averaging_init(eps)
+            ebar = eps
+            while done < nwarmup:
+                n = min(int(window), nwarmup - done)
+                enqueue(pts, x0, seeds, eps, param, n, cont=not first)
+                wait()
+                first = False
+                done += n
+                if auto:
+                    acc = eng.hmc_get(draws=False)["accept_prob"].mean(axis=1)
+                    state, eps, ebar = dual_averaging_update(state, acc, target_accept)
             if auto:
-                acc = eng.hmc_get(draws=False)["accept_prob"].mean(axis=1)
-                state, eps, ebar = dual_averaging_update(state, acc, target_accept)
-        if auto:
-            eps = np.asarray(ebar, dtype=np.float64)
-    eng.nuts_enqueue(pts, x0, seeds, eps, max_depth, int(ndraws), cont=not first)
-    eng.nuts_wait()
-    got = eng.hmc_get()
-    depth, nleap = eng.nuts_get_stats()
-    return NUTSResult(got["draws"], got["logp"], got["accept_prob"], got["energy_error"], got["divergent"], np.array(eps), np.array(pts),
-                      0, int(nwarmup), eng, eng.hmc_runs, depth, nleap, int(max_depth))
+                eps = np.asarray(ebar, dtype=np.float64)
+        enqueue(pts, x0, seeds, eps, param, int(ndraws), cont=not first)
+        wait()
+        got = eng.hmc_get()
+        eps = np.array(eps)
+    rows = (got["draws"], got["logp"], got["accept_prob"], got["energy_error"], got["divergent"], eps, np.array(pts))
+    if is_nuts:
+        depth, nleap = eng.nuts_get_stats()
+        return NUTSResult(*rows, 0, int(nwarmup), eng, eng.hmc_runs, depth, nleap, int(param), warmup=warm)
+    return HMCResult(*rows, int(param), int(nwarmup), eng, eng.hmc_runs, warmup=warm)
+
+
+def hmc(result, ndraws, *, nchains=None, nwarmup=0, step_size="auto", nleapfrog=8, rng=None, target_accept=0.8, window=10, adapt="windows"):
+    """`ndraws` transitions of `nchains` chains of static HMC from a PathfinderResult / MultiPathfinderResult.
+
+    Chain c starts at result.draws[:, c] (resample(result, nchains, replace=False) first gives distinct starts) and uses the best fit of
+    the run that draw came from as its metric.  step_size: a number, one per chain, or "auto": d^(-1/4), adapted per chain during the
+    `nwarmup` warm-up transitions between windows of `window` transitions by dual averaging on the window's mean acceptance
+    (dual_averaging_update); the warm-up draws are discarded and sampling uses the averaged step size.  adapt="device" (step_size="auto"
+    only): the device updates every chain's step size after every warm-up transition (include/pfmi.h: pfmi_hmc_adapt_enqueue); warm-up and
+    sampling are ONE enqueue, and the result's `warmup` holds the traces."""
+    return _run("hmc", result, ndraws, nchains, nwarmup, step_size, nleapfrog, rng, target_accept, window, adapt)
+
+
+def nuts(result, ndraws, *, nchains=None, nwarmup=0, step_size="auto", max_depth=10, rng=None, target_accept=0.8, window=10, adapt="windows"):
+    """`ndraws` transitions of `nchains` chains of multinomial NUTS from a PathfinderResult / MultiPathfinderResult: the starts, metrics,
+    seeds and step-size rule of `hmc` (dual averaging between windows of `window` warm-up transitions on the windows' mean accept_prob,
+    the mean over a tree's leaves of min(1, exp(H0 - H))), with trees of at most 2^max_depth - 1 leapfrog steps instead of a fixed count.
+    adapt="device": as for `hmc`, one enqueue whose warm-up adapts on the device after every transition (pfmi_nuts_adapt_enqueue)."""
+    return _run("nuts", result, ndraws, nchains, nwarmup, step_size, max_depth, rng, target_accept, window, adapt)
 
 
 class _CallableModule(types.ModuleType):
