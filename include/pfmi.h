@@ -479,6 +479,64 @@ int32_t pfmi_adapt_get(pfmi_ctx *ctx, double *step_size, double *eps_trace, doub
  * NULL): exp(leb_m) at index m - 1.  Needs no GPU and no ctx. */
 int32_t pfmi_host_dual_averaging(int64_t n, double eps0, double target_accept, const double *accept, double *eps, double *eps_bar);
 
+/* ---- device-resident warm-up: windowed metric adaptation on the Woodbury factor ---------------------------------------------------- */
+/* The second way the reference's worked example hands a Pathfinder result to HMC (docs/src/examples/initializing-hmc.md: "initialise a
+ * metric adaptation" from the fitted covariance), as Stan's windowed adaptation, AdvancedHMC's StanHMCAdaptor and DynamicHMC's
+ * default_warmup_stages run it, carried out in the coordinates whitened by the fit's factor.  Chain k keeps the factor of its fit point,
+ * Sigma_p = L R, and in addition a per-coordinate SCALE c_k (d positive doubles):
+ *     Sigma_k = L diag(c_k)^2 L'            a kick is v += e c . (R g), a drift x += e L (c . v)
+ * The momentum stays whitened, v ~ N(0, I), and nothing else of a transition changes; c = 1 is the fitted metric.
+ * The windows of W = nwarmup warm-up transitions (one rule for host and device, csrc/adapt.h; pfmi_adapt_windows):
+ *     W < 20     no window: the run is pfmi_*_adapt_enqueue's and PFMI_ADAPT_NO_METRIC_WINDOW is set in every chain's status.
+ *     otherwise  init = 75, term = 50, base = 25; if init + base + term > W: init = floor(0.15 W), term = floor(0.10 W),
+ *                base = W - init - term.  end = W - term.  Windows are consecutive from init; one of nominal size s that starts at e ends at
+ *                e + s, or at `end` if e + s + 2 s - 1 >= end; the next nominal size is 2 s.  (Stan's rule, except that the first window
+ *                takes the stretch test of the others.)
+ * After every transition of a window, accepted or not, the chain forms u = L \ (x - x0) -- PFMI_OP_WHITEN with the FIT's factor, so that
+ * an estimate replaces the scale and does not compound it; x0 its start point -- and every coordinate takes one Welford update of its
+ * running mean and M2.  At the end of a window of n transitions
+ *     D_i = (n / (n + 5)) M2_i / (n - 1) + 5 / (n + 5),        c_i = sqrt(D_i)
+ * (shrinkage towards 1, the fitted metric).  If any D_i is not finite or not positive the chain keeps its scale and
+ * PFMI_ADAPT_KEPT_METRIC is set.  The Welford state is cleared and the dual averaging restarts: m = 0, Hbar = leb = 0, mu = log(10 eps),
+ * eps the step size the ordinary update after this transition proposes (which the next transition uses).  The `term` transitions after
+ * the last window adapt the step size alone; sampling uses exp(leb) as in pfmi_*_adapt_enqueue.
+ * Stage names: "hmc_metric", "hmc_metric_closure", "nuts_metric", "nuts_metric_closure"; "hmc_metric:<KPAD>:<res|stream>" and
+ * "nuts_metric:<KPAD>:<res|stream>" count the launches of one plan of the metric kernels, which step every chain that carries a scale, in
+ * a plain run or an adaptive one (the counters of the plain and the _adapt plans are untouched). */
+#define PFMI_ADAPT_NO_METRIC_WINDOW 2   /* status bit: nwarmup < 20, the warm-up adapted the step size alone */
+#define PFMI_ADAPT_KEPT_METRIC 4        /* status bit: a window gave a variance that was not positive and finite; the chain kept its scale */
+#define PFMI_ADAPT_RECORD_WHITENED 4    /* flag: keep the u of every window transition (tests / diagnostics, as PFMI_HMC_RECORD_PATH is) */
+#define PFMI_ADAPT_MAX_WINDOWS 32       /* no nwarmup below 2^31 has more windows */
+/* Stages scale [K][d] for the next pfmi_hmc_enqueue / pfmi_nuts_enqueue (or adaptive enqueue) with that K, a fresh run or a CONTINUE,
+ * where it becomes the chains' resident scale.  A CONTINUE without a staged scale keeps the resident one; a fresh run without one has
+ * none and launches the plain kernels.  scale NULL clears the staging.  PFMI_ERR_ARG: a value that is not positive and finite, K < 1
+ * (as a refused enqueue, this drains the ctx's stream and leaves no chains); an enqueue whose K is not the staged K returns PFMI_ERR_ARG.
+ * Whatever forgets the chains forgets the scale, staged or resident. */
+int32_t pfmi_chain_scale_set(pfmi_ctx *ctx, int32_t K, const double *scale);
+/* pfmi_hmc_adapt_enqueue / pfmi_nuts_adapt_enqueue with the metric windows above.  The chains start from a staged scale, or from c = 1.
+ * flags: 0 or PFMI_ADAPT_RECORD_WHITENED (PFMI_ERR_UNSUPPORTED when the rows do not fit).  Errors and the drain-on-error rule are those
+ * of pfmi_*_adapt_enqueue; nwarmup >= 2^31 is PFMI_ERR_UNSUPPORTED.  After the run the resident scale is the last window's: a later plain
+ * CONTINUE samples with the adapted metric.  pfmi_adapt_get serves the step-size traces over all W transitions (a restart shows as the
+ * step size the update before it proposed), the final step size and the status bits. */
+int32_t pfmi_hmc_adapt_metric_enqueue(pfmi_ctx *ctx, int32_t K, const int64_t *points, const double *x0, const uint64_t *seeds,
+                                      const double *step_size0, int32_t nleapfrog, int64_t nwarmup, int64_t ntransitions,
+                                      double target_accept, int32_t flags);
+int32_t pfmi_nuts_adapt_metric_enqueue(pfmi_ctx *ctx, int32_t K, const int64_t *points, const double *x0, const uint64_t *seeds,
+                                       const double *step_size0, int32_t max_depth, int64_t nwarmup, int64_t ntransitions,
+                                       double target_accept, int32_t flags);
+/* The last run of those two: *nwindows; ends [nwindows] (room for PFMI_ADAPT_MAX_WINDOWS, or for what pfmi_adapt_windows gives) the
+ * windows' exclusive ends; scale_trace [K][nwindows][d] the scale each window left (the kept one under PFMI_ADAPT_KEPT_METRIC); whitened
+ * [K][ends[nwindows - 1] - init][d] the u of every window transition (PFMI_ERR_STATE if the run did not record them).  Any may be NULL.
+ * Waits as pfmi_adapt_get does.  PFMI_ERR_STATE without such a run. */
+int32_t pfmi_adapt_metric_get(pfmi_ctx *ctx, int32_t *nwindows, int64_t *ends, double *scale_trace, double *whitened);
+/* Host builds of the device's sources (csrc/adapt.h), as pfmi_host_dual_averaging is; no GPU, no ctx.
+ * pfmi_adapt_windows: the windows of nwarmup transitions -- *init the first window's start, *term the transitions after the last,
+ * ends [*nwindows] (nwarmup < 20: no window, *init = nwarmup, *term = 0).  PFMI_ERR_ARG: nwarmup < 1, a NULL pointer, cap too small.
+ * pfmi_host_metric_update: the scale a window of n >= 2 rows u [n][d] leaves -- scale_out = sqrt(D), or scale_in with *status =
+ * PFMI_ADAPT_KEPT_METRIC when a D_i is not positive and finite. */
+int32_t pfmi_adapt_windows(int64_t nwarmup, int64_t *init, int64_t *term, int64_t *ends, int32_t cap, int32_t *nwindows);
+int32_t pfmi_host_metric_update(int64_t n, int32_t d, const double *u, const double *scale_in, double *scale_out, int32_t *status);
+
 /* ---- chain diagnostics: rank-normalised split R-hat and ESS ------------------------------------------------------------------- */
 /* The table the reference's worked examples end every chain run with (summarystats(chns), docs/src/examples/turing.md,
  * initializing-hmc.md): mean, sd, mcse, ess_bulk, ess_tail, rhat per coordinate, computed where the draws are.  Definitions: Vehtari,

@@ -18,6 +18,11 @@ void hmc_forget(pfmi_ctx *c) {
     c->hmc.adapting = false;
     c->hmc.W = 0;
     c->hmc.eps_kept = false;
+    c->hmc.scaled = false;
+    c->hmc.metric_run = false;
+    c->hmc.rec_u = false;
+    c->hmc.nwin = 0;
+    c->scale_staged.clear();                              // (an enqueue has taken the staged scale before it forgets the chains: metric_plan)
 }
 
 // The one refusal epilogue of the enqueues, the pump and the wait: an error exit drains this ctx's stream and leaves no chains, no traces
@@ -75,6 +80,8 @@ int32_t chain_check_chains(pfmi_ctx *c, const ChainKind &S, const ChainCall &A) 
     }
     PF_CHECK(!cont || (H.have && H.K == K), PFMI_ERR_STATE, "%s_enqueue: PFMI_%s_CONTINUE without %d resident chains", S.name, S.NAME, K);
     PF_CHECK(!cont || H.kind == S.kind, PFMI_ERR_STATE, "%s_enqueue: PFMI_%s_CONTINUE on the chains of pfmi_%s_enqueue", S.name, S.NAME, S.other);
+    PF_CHECK(c->scale_staged.empty() || c->scale_staged_K == K, PFMI_ERR_ARG, "%s_enqueue: the scale of pfmi_chain_scale_set is for %d chains, not %d",
+             S.name, c->scale_staged_K, K);
     return PFMI_OK;
 }
 
@@ -106,6 +113,8 @@ int32_t chain_begin(pfmi_ctx *c, const ChainKind &S, const ChainCall &A, int64_t
     for (DevBuf *b : {&c->hm_lp, &c->hm_acc, &c->hm_de}) bufs.push_back({b, sizeof(double) * rows, CALL_BUF});
     bufs.push_back({&c->hm_div, sizeof(int32_t) * rows, CALL_BUF});
     if (W) bufs.push_back({&c->hm_adapt, adapt_bytes(K, W), CALL_BUF});
+    MetricPlan MP;
+    PF_TRY(metric_plan(c, A, bufs, MP));
     for (DevBuf *b : {&c->hm_pX, &c->hm_pv}) bufs.push_back({b, vec, PATH_BUF});
     bufs.push_back({&c->hm_pout, out_bytes, PATH_BUF});
     // what this call grows: a CONTINUE keeps the chains' buffers, only RECORD_PATH has path rows (one per round, of the cap for NUTS)
@@ -138,8 +147,9 @@ int32_t chain_begin(pfmi_ctx *c, const ChainKind &S, const ChainCall &A, int64_t
     if (cont) PF_TRY(adapt_keep_step_sizes(c));
     PF_TRY(pf_upload(c, c->hm_eps.p, step_size, sizeof(double) * (size_t)K));
     if (!cont) PF_TRY(pf_upload(c, c->hm_x0.p, A.x0, vec));
-    if (W) PF_TRY(adapt_reset(c, K, W, step_size, A.delta));
+    if (W) PF_TRY(adapt_reset(c, K, W, step_size, A.delta, A.metric && MP.nwin == 0 ? PF_ADAPT_NO_METRIC_WINDOW : 0));
     H.K = K; H.record = rec; H.kind = S.kind;
+    PF_TRY(metric_begin(c, A, MP));
     H.t0 = cont ? H.t0 + H.T : W; H.T = T;
     H.adapting = W > 0;
     if (W) H.W = W;
@@ -152,12 +162,12 @@ int32_t chain_begin(pfmi_ctx *c, const ChainKind &S, const ChainCall &A, int64_t
 static const ChainKind HMC_KIND = {"hmc", "HMC", "nuts", 0};
 
 int32_t hmc_enqueue(pfmi_ctx *c, int32_t K, const int64_t *points, const double *x0, const uint64_t *seeds, const double *step_size,
-                    int32_t nleapfrog, int64_t T, int32_t flags, int64_t W, double delta) {
+                    int32_t nleapfrog, int64_t T, int32_t flags, int64_t W, double delta, int metric) {
     HmcState &H = c->hmc;
     const TargetDev &Tg = c->target;
     const int d = c->d;
     const size_t vec = sizeof(double) * (size_t)K * d;
-    const ChainCall A = {K, points, x0, seeds, step_size, T, flags, W, delta};
+    const ChainCall A = {K, points, x0, seeds, step_size, T, flags, W, delta, metric};
     PF_TRY(chain_check_target(c, HMC_KIND, A));
     PF_CHECK(nleapfrog >= 1 && T >= 1, PFMI_ERR_ARG, "hmc_enqueue: nleapfrog %d and ntransitions %lld must be >= 1", nleapfrog, (long long)T);
     PF_TRY(chain_check_chains(c, HMC_KIND, A));
@@ -167,12 +177,15 @@ int32_t hmc_enqueue(pfmi_ctx *c, int32_t K, const int64_t *points, const double 
     int64_t rounds = 0;
     PF_TRY(chain_begin(c, HMC_KIND, A, nleapfrog, "", own, nullptr, &rounds));
     const bool cont = (flags & PFMI_HMC_CONTINUE) != 0;
-    const char *stage = W ? "hmc_adapt" : "hmc", *cstage = W ? "hmc_adapt_closure" : "hmc_closure";
+    const bool scaled = H.scaled;                        // chains that carry a scale: the metric kernel, plain run or adaptive
+    const char *stage = scaled ? "hmc_metric" : W ? "hmc_adapt" : "hmc";
+    const char *cstage = scaled ? "hmc_metric_closure" : W ? "hmc_adapt_closure" : "hmc_closure";
+    const auto step = scaled ? pf_launch_hmc_metric_step : pf_launch_hmc_step;
     H.nleap = nleapfrog; H.finished = true;
     if (!cont) PF_TRY(pf_launch_hmc_init(c, c->stream));
     else {
         pf_kernel_begin(c);
-        PF_TRY(pf_launch_hmc_step(c, -1, c->stream));
+        PF_TRY(step(c, -1, c->stream));
         pf_kernel_end(c, stage);
     }
     for (int64_t r = 0; r < rounds; ++r) {
@@ -182,7 +195,7 @@ int32_t hmc_enqueue(pfmi_ctx *c, int32_t K, const int64_t *points, const double 
         pf_kernel_end(c, cstage);
         H.columns += K;
         pf_kernel_begin(c);
-        PF_TRY(pf_launch_hmc_step(c, r, c->stream));
+        PF_TRY(step(c, r, c->stream));
         pf_kernel_end(c, stage);
         ++H.rounds;
     }

@@ -3,6 +3,7 @@
 // point relies on.  Each function is defined in the component it belongs to (named behind its declaration).
 #pragma once
 #include "pfmi_common.h"
+#include "adapt.h"
 #include <stdlib.h>
 #include <string.h>
 #include <vector>
@@ -46,11 +47,13 @@ void stream_abandon(pfmi_ctx *c);          // drain and forget a streaming call 
 void lbc_abandon(pfmi_ctx *c);             // the same for a packed closure optimisation
 void hmc_forget(pfmi_ctx *c);              // drain an HMC call that was never waited for and forget the chains (api_hmc.hip)
 // ---- api_hmc.hip, api_nuts.hip: the enqueues behind the plain and the adaptive entry points (api_adapt.hip).  W = 0: a plain run.
-// W >= 1: a fresh run whose first W transitions adapt the step size towards the acceptance `delta` and record no rows.
+// W >= 1: a fresh run whose first W transitions adapt the step size towards the acceptance `delta` and record no rows.  metric (W >= 1):
+// CHAIN_METRIC_WINDOWS: the warm-up also adapts the per-coordinate scale in windows (adapt.h); CHAIN_METRIC_RECORD: and keeps every u.
+enum { CHAIN_METRIC_NONE = 0, CHAIN_METRIC_WINDOWS = 1, CHAIN_METRIC_RECORD = 2 };
 int32_t hmc_enqueue(pfmi_ctx *c, int32_t K, const int64_t *points, const double *x0, const uint64_t *seeds, const double *step_size,
-                    int32_t nleapfrog, int64_t T, int32_t flags, int64_t W, double delta);
+                    int32_t nleapfrog, int64_t T, int32_t flags, int64_t W, double delta, int metric = CHAIN_METRIC_NONE);
 int32_t nuts_enqueue(pfmi_ctx *c, int32_t K, const int64_t *points, const double *x0, const uint64_t *seeds, const double *step_size,
-                     int32_t max_depth, int64_t T, int32_t flags, int64_t W, double delta);
+                     int32_t max_depth, int64_t T, int32_t flags, int64_t W, double delta, int metric = CHAIN_METRIC_NONE);
 // ---- api_hmc.hip: the one enqueue path of both samplers.
 struct ChainKind { const char *name, *NAME, *other; int kind; };       // "hmc" / "HMC" / the other sampler's name / HmcState::kind
 // One buffer of a sampler call and its size, stated once; the memory estimate and the `ensure`s both walk the list of them.
@@ -59,6 +62,7 @@ enum { CHAIN_BUF, CALL_BUF, PATH_BUF };
 struct ChainBuf { DevBuf *buf; size_t bytes; int scope; bool est = true; };      // est: counted in the estimate
 struct ChainCall {                                       // what both enqueues are given
     int32_t K; const int64_t *points; const double *x0; const uint64_t *seeds; const double *step_size; int64_t T; int32_t flags; int64_t W; double delta;
+    int metric = CHAIN_METRIC_NONE;
 };
 // The shared checks in the order the entry points have always made them (messages under "<name>_enqueue:"): fit, target and null
 // arguments; then the sampler checks its own parameter; flags, points, step sizes and what a CONTINUE needs; then the sampler's own
@@ -67,13 +71,19 @@ int32_t chain_check_target(pfmi_ctx *c, const ChainKind &S, const ChainCall &A);
 int32_t chain_check_chains(pfmi_ctx *c, const ChainKind &S, const ChainCall &A);
 // Checks that every chain's fit succeeded, sizes `bufs` plus the common buffers for rounds = (fresh ? 1 : 0) + (W + T) per_transition
 // against the free memory and grows them, quiets the call before (drain: pumps a NUTS run to its end), uploads, and sets the HmcState
-// fields both samplers have.  The caller launches init / reopen and issues the rounds.
+// fields both samplers have.  A scale staged by pfmi_chain_scale_set becomes the chains' resident one (c->hmc.scaled: the caller launches
+// the metric kernels); a run with metric windows starts from it, or from ones.  The caller launches init / reopen and issues the rounds.
 int32_t chain_begin(pfmi_ctx *c, const ChainKind &S, const ChainCall &A, int64_t per_transition, const char *need_detail,
                     std::vector<ChainBuf> bufs, int32_t (*drain)(pfmi_ctx *), int64_t *rounds_out);
 int32_t chain_refused(pfmi_ctx *c, int32_t rc);           // rc != OK: drain, no run, no chains, no traces; returns rc
 int32_t chain_dead_check(pfmi_ctx *c, const char *name, const std::vector<int32_t> &dead);         // the waits: a dead start point is PFMI_ERR_NUMERIC
 int32_t chain_path_download(pfmi_ctx *c, int64_t round0, int64_t nrounds, double *X, double *closure_out, double *v);     // queued, not waited for
-int32_t adapt_reset(pfmi_ctx *c, int32_t K, int64_t W, const double *step_size, double delta);     // api_adapt.hip: states and traces of a fresh adaptive run
+int32_t adapt_reset(pfmi_ctx *c, int32_t K, int64_t W, const double *step_size, double delta, int32_t status0);     // api_adapt.hip: states and traces of a fresh adaptive run
+// api_adapt.hip: the windows of a run with A.metric set (H.metric_run, nwin, win_*, rec_u) and its hm_metric buffer in `bufs`; then, once the
+// buffers are there, the scale (staged, or ones in front of metric windows) and the window table, with the Welford state cleared
+struct MetricPlan { int nwin = 0; int64_t init = 0, ends[32] = {}; std::vector<double> scale; };      // scale: the staged one, taken
+int32_t metric_plan(pfmi_ctx *c, const ChainCall &A, std::vector<ChainBuf> &bufs, MetricPlan &P);
+int32_t metric_begin(pfmi_ctx *c, const ChainCall &A, const MetricPlan &P);
 size_t adapt_bytes(int32_t K, int64_t W);
 // a plain CONTINUE is about to replace hm_eps: keep the adaptive run's final step sizes for pfmi_adapt_get (stream-ordered copy, once)
 int32_t adapt_keep_step_sizes(pfmi_ctx *c);

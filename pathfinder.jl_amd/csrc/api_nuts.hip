@@ -21,12 +21,12 @@ static int32_t nuts_issue_rounds(pfmi_ctx *c) {
     while (!H.finished && H.issued < H.max_rounds && H.issued - H.seen < PF_NUTS_WINDOW) {
         pf_kernel_begin(c);
         Tg.grad_fn(c->hm_X.as<double>(), c->d, H.K, c->hm_out.as<double>(), (void *)c->stream, Tg.grad_user);
-        pf_kernel_end(c, H.adapting ? "nuts_adapt_closure" : "nuts_closure");
+        pf_kernel_end(c, H.scaled ? "nuts_metric_closure" : H.adapting ? "nuts_adapt_closure" : "nuts_closure");
         H.columns += H.K;
         const int64_t prow = H.issued++;
         pf_kernel_begin(c);
-        PF_TRY(pf_launch_nuts_step(c, H.issued, prow, false, c->stream));
-        pf_kernel_end(c, H.adapting ? "nuts_adapt" : "nuts");
+        PF_TRY((H.scaled ? pf_launch_nuts_metric_step : pf_launch_nuts_step)(c, H.issued, prow, false, c->stream));
+        pf_kernel_end(c, H.scaled ? "nuts_metric" : H.adapting ? "nuts_adapt" : "nuts");
     }
     if (!H.finished && H.issued >= H.max_rounds && H.seen >= H.issued) H.finished = true;      // the hard cap: a stuck flag cannot loop forever
     return PFMI_OK;
@@ -55,10 +55,10 @@ static int32_t nuts_drain(pfmi_ctx *c) {                  // pump to the end (ev
 static const ChainKind NUTS_KIND = {"nuts", "NUTS", "hmc", 1};
 
 int32_t nuts_enqueue(pfmi_ctx *c, int32_t K, const int64_t *points, const double *x0, const uint64_t *seeds, const double *step_size,
-                     int32_t max_depth, int64_t T, int32_t flags, int64_t W, double delta) {
+                     int32_t max_depth, int64_t T, int32_t flags, int64_t W, double delta, int metric) {
     HmcState &H = c->hmc;
     const bool cont = (flags & PFMI_NUTS_CONTINUE) != 0, rec = (flags & PFMI_NUTS_RECORD_PATH) != 0;
-    const ChainCall A = {K, points, x0, seeds, step_size, T, flags, W, delta};
+    const ChainCall A = {K, points, x0, seeds, step_size, T, flags, W, delta, metric};
     PF_TRY(chain_check_target(c, NUTS_KIND, A));
     PF_CHECK(max_depth >= 1 && max_depth <= 10 && T >= 1, PFMI_ERR_ARG, "nuts_enqueue: max_depth %d outside 1 .. 10 or ntransitions %lld < 1", max_depth,
              (long long)T);
@@ -89,8 +89,8 @@ int32_t nuts_enqueue(pfmi_ctx *c, int32_t K, const int64_t *points, const double
     if (!cont) PF_TRY(pf_launch_nuts_init(c, c->stream));
     else {
         pf_kernel_begin(c);
-        PF_TRY(pf_launch_nuts_step(c, 0, 0, true, c->stream));
-        pf_kernel_end(c, "nuts");
+        PF_TRY((H.scaled ? pf_launch_nuts_metric_step : pf_launch_nuts_step)(c, 0, 0, true, c->stream));
+        pf_kernel_end(c, H.scaled ? "nuts_metric" : "nuts");
     }
     return nuts_issue_rounds(c);
 }

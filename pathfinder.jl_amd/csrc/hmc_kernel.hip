@@ -56,6 +56,7 @@ struct HmArgs {
     PfAdapt *ad;                       // adaptive runs: [K] adaptation states, then the warm-up traces PfWarmRow [K][t0]
 };
 
+#ifndef PF_CHAIN_METRIC_TU
 __global__ __launch_bounds__(HM_NT) void pf_hmc_init_kernel(HmArgs A) {
     const int k = blockIdx.x, d = A.d;
     hm_copy_start(A.x0 + (size_t)k * d, A.X + (size_t)k * d, A.x + (size_t)k * d, d);
@@ -65,11 +66,19 @@ __global__ __launch_bounds__(HM_NT) void pf_hmc_init_kernel(HmArgs A) {
         A.st[k] = S;
     }
 }
+#endif
 
 // ADAPT (pf_hmc_warm_kernel): transitions t < t0 are the warm-up.  They write no row but a PfWarmRow, and thread 0 applies pf_adapt_update
 // between recording transition t and opening transition t + 1, whose first half kick and drift already use the new step size.
-template <int KPAD, bool RES, bool ADAPT>
-__device__ __forceinline__ void hm_step_body(const HmArgs &A) {
+//
+// MODE HM_METRIC (pf_hmc_metric_kernel, hmc_metric_kernel.hip): the chain carries a per-coordinate scale c (HmMetric, hmc_rows.h): a kick is
+// v += e c . (R g), a drift x += e L (c . v) -- wg, wt and v themselves stay what they are without a scale, so a new scale needs no
+// conversion of the state -- and a warm-up transition inside a metric window ends with hm_metric_end.  Plain and adaptive runs share it.
+enum { HM_PLAIN = 0, HM_WARM = 1, HM_METRIC = 2 };
+
+template <int KPAD, bool RES, int MODE, class Args>
+__device__ __forceinline__ void hm_step_body(const Args &A) {
+    constexpr bool ADAPT = MODE != HM_PLAIN, METRIC = MODE == HM_METRIC;
     constexpr int NVM = KPAD + 4;                        // KPAD sums + one rider, padded to the multiple of 4 pf_block_sum_mv takes
     __shared__ HmLds<KPAD, NVM> L;
     const int k = blockIdx.x, tid = threadIdx.x, d = A.d, K = A.K;
@@ -85,6 +94,9 @@ __device__ __forceinline__ void hm_step_body(const HmArgs &A) {
     const HmFactor F = {gVh, T, Vc, sqa};
     bool staged = false;                                 // an R pass came before the L pass (hmc_rows.h)
     bool open = S.i == HM_OPEN, drift = false;
+    // METRIC: the chain's scale; c_i w of a kick is hm_scaled's (row i is the calling thread's own)
+    const double *sc = nullptr;
+    if constexpr (METRIC) sc = A.M.scale + kd;
     if (S.i != HM_OPEN) {
         const double lpt = A.out[k];
         const double *g = A.out + K + kd;
@@ -103,14 +115,14 @@ __device__ __forceinline__ void hm_step_body(const HmArgs &A) {
             S.dead = bad ? 1 : 0;
             open = true;
         } else if (S.i < A.nleap) {
-            for (int i = tid; i < d; i += HM_NT) v[i] = fma(eps, wt[i], v[i]);
+            for (int i = tid; i < d; i += HM_NT) v[i] = fma(eps, hm_scaled<METRIC>(sc, i, wt[i]), v[i]);
             if (nbad > 0.0 || !isfinite(lpt)) S.bad = 1;
             ++S.i;
             drift = true;
         } else {
             // ---- the trajectory's end: last half kick, H1, the decision, row t
             double e = 0.0;
-            for (int i = tid; i < d; i += HM_NT) { const double vi = fma(0.5 * eps, wt[i], v[i]); e = fma(vi, vi, e); }
+            for (int i = tid; i < d; i += HM_NT) { const double vi = fma(0.5 * eps, hm_scaled<METRIC>(sc, i, wt[i]), v[i]); e = fma(vi, vi, e); }
             e = pf_block_sum1_pp<NVM>(e, L.red, flip);
             const double H1 = -lpt + 0.5 * e, dH = H1 - S.H0;
             const bool div = S.bad || nbad > 0.0 || !isfinite(lpt) || !isfinite(H1) || dH > 1000.0;
@@ -134,7 +146,13 @@ __device__ __forceinline__ void hm_step_body(const HmArgs &A) {
             if constexpr (ADAPT) {
                 if (warm) {
                     __shared__ double sNext;
-                    if (tid == 0) sNext = hm_warm_end(A.ad, A.eps, K, k, S.t, A.t0, eps, a, div ? 1 : 0, A.nleap);
+                    bool wnd = false;                    // METRIC: the transition ended a metric window
+                    if constexpr (METRIC)
+                        wnd = hm_metric_end<KPAD, RES, NVM>(F, L, A.M, A.ad, k, d, S.t - 1, A.x0 + kd, flip, [&](int i) { return x[i]; });
+                    if (tid == 0) {
+                        sNext = hm_warm_end(A.ad, A.eps, K, k, S.t, A.t0, eps, a, div ? 1 : 0, A.nleap);
+                        if constexpr (METRIC) if (wnd) pf_adapt_restart(A.ad[k], sNext);
+                    }
                     __syncthreads();
                     eps = sNext;
                 }
@@ -149,15 +167,20 @@ __device__ __forceinline__ void hm_step_body(const HmArgs &A) {
         for (int i = tid; i < d; i += HM_NT) {
             const double z = hm_normal(seed, n, i);
             vv0 = fma(z, z, vv0);
-            v[i] = fma(0.5 * eps, wg[i], z);
+            v[i] = fma(0.5 * eps, hm_scaled<METRIC>(sc, i, wg[i]), z);
         }
         S.i = 1;
         drift = true;
     }
     if (drift) {
         const double *base = open ? x : X;
-        hm_apply_L<KPAD, RES, HM_NT, NVM>(F, L, X, eps, vv0, staged, d, flip, [&](int i) -> const double & { return v[i]; }, [&](int i) { return base[i]; },
-                                          [&](double vv) { if (open) S.H0 = -S.lp + 0.5 * vv; });
+        if constexpr (METRIC) {
+            hm_apply_L<KPAD, RES, HM_NT, NVM>(F, L, X, eps, vv0, staged, d, flip, [&](int i) { return sc[i] * v[i]; }, [&](int i) { return base[i]; },
+                                              [&](double vv) { if (open) S.H0 = -S.lp + 0.5 * vv; });
+        } else {
+            hm_apply_L<KPAD, RES, HM_NT, NVM>(F, L, X, eps, vv0, staged, d, flip, [&](int i) -> const double & { return v[i]; }, [&](int i) { return base[i]; },
+                                              [&](double vv) { if (open) S.H0 = -S.lp + 0.5 * vv; });
+        }
     }
     if (A.record && A.round >= 0) {
         double *pv = A.pv + ((size_t)A.round * K + k) * d;
@@ -167,11 +190,13 @@ __device__ __forceinline__ void hm_step_body(const HmArgs &A) {
     if (tid == 0) A.st[k] = S;
 }
 
+#ifndef PF_CHAIN_METRIC_TU             // (hmc_metric_kernel.hip takes the body and hm_args from this file and defines its own kernels)
 template <int KPAD, bool RES>
-__global__ __launch_bounds__(HM_NT) void pf_hmc_step_kernel(HmArgs A) { hm_step_body<KPAD, RES, false>(A); }
+__global__ __launch_bounds__(HM_NT) void pf_hmc_step_kernel(HmArgs A) { hm_step_body<KPAD, RES, HM_PLAIN>(A); }
 
 template <int KPAD, bool RES>
-__global__ __launch_bounds__(HM_NT) void pf_hmc_warm_kernel(HmArgs A) { hm_step_body<KPAD, RES, true>(A); }
+__global__ __launch_bounds__(HM_NT) void pf_hmc_warm_kernel(HmArgs A) { hm_step_body<KPAD, RES, HM_WARM>(A); }
+#endif
 
 // ---------------------------------------------------------------------------------------------------
 static HmArgs hm_args(pfmi_ctx *c, int64_t round) {
@@ -191,6 +216,7 @@ static HmArgs hm_args(pfmi_ctx *c, int64_t round) {
     return A;
 }
 
+#ifndef PF_CHAIN_METRIC_TU
 size_t pf_hmc_chain_bytes() { return sizeof(HmChain); }
 
 int32_t pf_launch_hmc_init(pfmi_ctx *c, hipStream_t s) {
@@ -200,6 +226,7 @@ int32_t pf_launch_hmc_init(pfmi_ctx *c, hipStream_t s) {
 }
 
 struct HmFamily {
+    static constexpr bool has_warm = true;
     template <int KPAD, bool RES, bool ADAPT>
     static auto kernel() { return ADAPT ? &pf_hmc_warm_kernel<KPAD, RES> : &pf_hmc_step_kernel<KPAD, RES>; }
 };
@@ -216,3 +243,4 @@ int32_t pf_hmc_dead_flags(pfmi_ctx *c, std::vector<int32_t> &dead) {
 }
 
 int32_t pf_launch_hmc_step(pfmi_ctx *c, int64_t round, hipStream_t s) { return hm_launch_step<HmFamily>(c, "hmc", hm_args(c, round), s); }
+#endif

@@ -1,7 +1,8 @@
 // hmc_rows.h -- what the chain kernels (hmc_kernel.hip: static HMC, nuts_kernel.hip: NUTS) share, each stated ONCE here: the launch
 // geometry and the LDS budget (HM_NT, HM_LDS_RES, pf_hmc_resident), the launch of a kernel family (hm_launch_step), the momentum normals,
 // the two Woodbury passes of a step (hm_apply_R: wt = R g, both kernels; hm_apply_L: X <- base + e L v, static HMC -- NUTS keeps its copy
-// written out, nuts_kernel.hip says why), the start-point copy of the init kernels and the end of a warm-up transition (hm_warm_end).
+// written out, nuts_kernel.hip says why), the start-point copy of the init kernels and the end of a warm-up transition (hm_warm_end); for the
+// metric kernels the third pass (hm_whiten: u = L \ dx) and what a window transition does with it (hm_metric_end).
 #pragma once
 #include "pfmi_common.h"
 #include "adapt.h"
@@ -15,10 +16,11 @@ inline bool pf_hmc_resident(int d, int kpad) { return (size_t)d * kpad * sizeof(
 
 #ifdef __HIPCC__
 // One step launch of a kernel family (Family::kernel<KPAD, RES, ADAPT>() is its step or warm kernel; Args carries d and K): one workgroup
-// per chain, the factor rows in dynamic LDS when they fit, counted under the plan name "<plan>[_adapt]:<KPAD>:<res|stream>".
+// per chain, the factor rows in dynamic LDS when they fit, counted under the plan name "<plan>[_adapt]:<KPAD>:<res|stream>".  (A family
+// without a warm kernel of its own -- has_warm false: the metric kernels -- serves plain and adaptive runs under one plan name.)
 template <class Family, class Args>
 static int32_t hm_launch_step(pfmi_ctx *c, const char *plan, const Args &A, hipStream_t s) {
-    const bool res = pf_hmc_resident(A.d, c->kpad), adapt = c->hmc.adapting;
+    const bool res = pf_hmc_resident(A.d, c->kpad), adapt = Family::has_warm && c->hmc.adapting;
     auto go = [&](auto KP, auto RES, auto AD) -> int32_t {
         auto *kern = Family::template kernel<KP(), RES(), AD()>();
         if (RES()) PF_TRY(pf_raise_lds_limit(c, reinterpret_cast<const void *>(kern), HM_LDS_RES));
@@ -179,6 +181,132 @@ __device__ __forceinline__ void hm_apply_L(const HmFactor &F, Lds &L, double *X,
         const double y = hm_row_sub<KPAD>(rows + (size_t)i * KPAD, L.sTv, i < KPAD ? sZ[i] : v(i));
         X[i] = fma(e, F.sqa[i] * y, base(i));
     }
+}
+
+// u = L \ dx (PFMI_OP_WHITEN): z = dx / s, w = Vh'z (one block reduction), tv = T'w, y = z - Vh tv, head <- V'^-1 head.  dx(i) is the
+// caller's element i; use(i, u_i) is called once per element by the thread that owns row i (head row i: thread i).  An R pass came
+// before in the launch, so with RES the rows are staged.
+// The head solve is wave 0's, lane a holding y_a (V upper triangular, the identity beyond the fit's columns), for a = 0 .. KPAD - 1 in turn:
+//     u_a = y_a / V[a][a];      y_b <- fma(-V[a][b], u_a, y_b) for every b > a
+// i.e. u_a = ((..((y_a - V[0][a] u_0) - V[1][a] u_1) ..) - V[a-1][a] u_{a-1}) / V[a][a]: a fused multiply-adds in the order b = 0 .. a - 1,
+// then one division.
+template <int KPAD, bool RES, int NT, int NRED, class Lds, class Dx, class Use>
+__device__ __forceinline__ void hm_whiten(const HmFactor &F, Lds &L, int d, int &flip, Dx dx, Use use) {
+    HM_STAGED_ROWS;
+    static_assert(KPAD <= 64, "the head solve is one wave's");
+    constexpr int NVM = KPAD + 4;
+    const int tid = threadIdx.x;
+    const double *rows = RES ? sVh : F.gVh;
+    double w[NVM];
+#pragma unroll
+    for (int j = 0; j < NVM; ++j) w[j] = 0.0;
+    for (int i = tid; i < d; i += NT) hm_row_axpy<KPAD, NVM, false>(rows + (size_t)i * KPAD, nullptr, dx(i) / F.sqa[i], w);
+    pf_block_sum_mv<NVM, NRED>(w, L.red, flip);
+    if (tid < KPAD) {
+        double s = 0.0;
+#pragma unroll
+        for (int b = 0; b < KPAD; ++b) if (b <= tid) s = fma(F.T[b * KPAD + tid], w[b], s);
+        L.sTv[tid] = s;
+    }
+    __syncthreads();
+    for (int i = tid; i < d; i += NT) {
+        const double y = hm_row_sub<KPAD>(rows + (size_t)i * KPAD, L.sTv, dx(i) / F.sqa[i]);
+        if (i < KPAD) L.sHead[i] = y; else use(i, y);
+    }
+    if (tid < KPAD && tid >= d) L.sHead[tid] = 0.0;
+    __syncthreads();
+    if (tid < 64) {
+        const bool mine = tid < KPAD;
+        double y = mine ? L.sHead[tid] : 0.0;
+#pragma unroll
+        for (int a = 0; a < KPAD; ++a) {
+            const double ua = __shfl(y, a) / F.Vc[a * KPAD + a];
+            const double vab = (mine && tid > a) ? F.Vc[a * KPAD + tid] : 0.0;       // (no read beyond V's row)
+            y = tid == a ? ua : fma(-vab, ua, y);
+        }
+        if (mine && tid < d) use(tid, y);
+    }
+}
+
+// c_i w in a metric kernel (a chain with a per-coordinate scale c), w itself in every other
+template <bool METRIC>
+__device__ __forceinline__ double hm_scaled(const double *c, int i, double w) {
+    if constexpr (METRIC) return c[i] * w;
+    else return w;
+}
+
+// What a chain with a per-coordinate scale reads (the metric kernels: pf_hmc_metric_kernel, pf_nuts_metric_kernel): the scale itself and,
+// in a run with metric windows (adapt.h), the windows, the Welford state of the open window and the traces.
+struct HmMetric {
+    double *scale;                     // [K][d] the chains' resident scale c
+    const int32_t *win;                // {number of windows, start of the first, their ends (exclusive)}; null: a run without windows
+    double *mean, *m2;                 // [K][d] Welford's running mean and M2 of u over the open window
+    double *strace;                    // [K][windows][d] the scale each window left
+    double *urec;                      // PFMI_ADAPT_RECORD_WHITENED: [K][nwt][d], the u of every window transition; else null
+    int64_t nwt;                       // transitions in windows: the last window's end - the first's start
+};
+// c->hm_metric of a run with metric windows, stated ONCE: the window table (PF_METRIC_HEAD bytes), mean and M2 [K][d], the scale trace
+// [K][nwin][d], then with PFMI_ADAPT_RECORD_WHITENED the rows u [K][nwt][d]
+#define PF_METRIC_HEAD 256
+static_assert(sizeof(int32_t) * (2 + PF_ADAPT_MAX_WINDOWS) <= PF_METRIC_HEAD, "the window table fits its slot");
+inline size_t pf_metric_bytes(int K, int d, int nwin, int64_t nwt_recorded) {
+    return PF_METRIC_HEAD + sizeof(double) * (size_t)K * d * (size_t)(2 + nwin + nwt_recorded);
+}
+inline double *pf_metric_strace(pfmi_ctx *c) { return reinterpret_cast<double *>(c->hm_metric.as<char>() + PF_METRIC_HEAD) + 2 * (size_t)c->hmc.K * c->d; }
+inline HmMetric pf_chain_metric_args(pfmi_ctx *c) {
+    const HmcState &H = c->hmc;
+    HmMetric M = {};
+    M.scale = c->hm_scale.as<double>();
+    if (H.adapting && H.metric_run && H.nwin > 0) {
+        const size_t vec = (size_t)H.K * c->d;
+        M.win = reinterpret_cast<const int32_t *>(c->hm_metric.as<char>());
+        M.mean = pf_metric_strace(c) - 2 * vec;
+        M.m2 = M.mean + vec;
+        M.strace = pf_metric_strace(c);
+        M.nwt = H.win_ends[H.nwin - 1] - H.win_init;
+        M.urec = H.rec_u ? M.strace + vec * (size_t)H.nwin : nullptr;
+    }
+    return M;
+}
+
+// The end of warm-up transition tt of chain k in a metric kernel, before hm_warm_end: inside a window, u = L \ (x - x0) and the Welford
+// update of every coordinate; at the window's end the new scale (or the kept one), its trace, and the cleared Welford state.  xs(i):
+// element i of the chain's state.  Returns whether a window ended: thread 0 then restarts the dual averaging (pf_adapt_restart).
+template <int KPAD, bool RES, int NRED, class Lds, class Xs>
+__device__ __forceinline__ bool hm_metric_end(const HmFactor &F, Lds &L, const HmMetric &M, PfAdapt *ad, int k, int d, int64_t tt64,
+                                              const double *x0, int &flip, Xs xs) {
+    if (!M.win) return false;
+    const int tt = __builtin_amdgcn_readfirstlane((int)tt64), nwin = M.win[0], first = M.win[1];
+    int j = -1, ws = 0, we = 0;
+    for (int q = 0, start = first; q < nwin; ++q) {
+        const int e = M.win[2 + q];
+        if (tt >= start && tt < e) { j = q; ws = start; we = e; }
+        start = e;
+    }
+    if (j < 0) return false;
+    const int tid = threadIdx.x;
+    const size_t kd = (size_t)k * d;
+    const double n = (double)(tt - ws + 1);
+    double *mean = M.mean + kd, *m2 = M.m2 + kd, *c = M.scale + kd;
+    double *ur = M.urec ? M.urec + ((size_t)k * M.nwt + (size_t)(tt - first)) * d : nullptr;
+    hm_whiten<KPAD, RES, HM_NT, NRED>(F, L, d, flip, [&](int i) { return xs(i) - x0[i]; }, [&](int i, double u) {
+        double mi = mean[i], qi = m2[i];
+        pf_welford_update(n, u, mi, qi);
+        mean[i] = mi; m2[i] = qi;
+        if (ur) ur[i] = u;
+    });
+    if (tt + 1 < we) return false;
+    // ---- the window's end (every thread reads back only what it wrote: row i is thread i % HM_NT's in every pass)
+    double bad = 0.0;
+    for (int i = tid; i < d; i += HM_NT) bad += pf_metric_var_ok(pf_metric_var(n, m2[i])) ? 0.0 : 1.0;
+    bad = pf_block_sum1_pp<NRED>(bad, L.red, flip);
+    double *st = M.strace + ((size_t)k * nwin + j) * d;
+    for (int i = tid; i < d; i += HM_NT) {
+        const double ci = bad > 0.0 ? c[i] : sqrt(pf_metric_var(n, m2[i]));
+        c[i] = ci; st[i] = ci; mean[i] = 0.0; m2[i] = 0.0;
+    }
+    if (tid == 0 && bad > 0.0) ad[k].flags |= PF_ADAPT_KEPT_METRIC;
+    return true;
 }
 
 // the init kernels: the start point becomes the chain's state and the closure's first input

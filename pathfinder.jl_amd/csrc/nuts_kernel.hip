@@ -92,6 +92,7 @@ __device__ __forceinline__ double nt_logaddexp(double a, double b) {
     return fmax(a, b) + log1p(exp(-fabs(a - b)));
 }
 
+#ifndef PF_CHAIN_METRIC_TU
 __global__ __launch_bounds__(HM_NT) void pf_nuts_init_kernel(NtArgs A) {
     const int k = blockIdx.x, d = A.d;
     hm_copy_start(A.x0 + (size_t)k * d, A.X + (size_t)k * d, A.blk + (size_t)k * A.nslot * d + (size_t)NT_X * d, d);
@@ -101,21 +102,29 @@ __global__ __launch_bounds__(HM_NT) void pf_nuts_init_kernel(NtArgs A) {
         A.st[k] = S;
     }
 }
+#endif
 
 // ADAPT (pf_nuts_warm_kernel): transitions t < t0 are the warm-up.  They write no row but a PfWarmRow, and thread 0 applies pf_adapt_update
 // between recording transition t and opening transition t + 1, whose first half kick and drift already use the new step size.
-template <int KPAD, bool RES, bool ADAPT>
-__device__ __forceinline__ void nt_step_body(const NtArgs &A_) {
+//
+// MODE NT_METRIC (pf_nuts_metric_kernel, nuts_metric_kernel.hip): the chain carries a per-coordinate scale c (HmMetric, hmc_rows.h): a kick is
+// v += e c . (R g), a drift x += e L (c . v) -- every stored R g and v stays what it is without a scale -- and a warm-up transition inside a
+// metric window ends with hm_metric_end.  Plain runs (which may record their path) and adaptive runs share it.
+enum { NT_PLAIN = 0, NT_WARM = 1, NT_METRIC = 2 };
+
+template <int KPAD, bool RES, int MODE, class Args>
+__device__ __forceinline__ void nt_step_body(const Args &A_) {
+    constexpr bool ADAPT = MODE != NT_PLAIN, METRIC = MODE == NT_METRIC;
     // The arguments are read where they are used, through the kernel-argument segment itself (A_ is the kernel's first and only entry): as a
     // by-value parameter all 80 dwords are loaded on entry and stay in scalar registers until their one use.
 #if defined(__HIP_DEVICE_COMPILE__)
-    const NtArgs &A = *(const NtArgs *)__builtin_amdgcn_kernarg_segment_ptr();
+    const Args &A = *(const Args *)__builtin_amdgcn_kernarg_segment_ptr();
 #else
-    const NtArgs &A = A_;
+    const Args &A = A_;
 #endif
     // an adaptive run records no path (its flags are 0): the warm kernel carries none of that code and none of its addresses
     auto rec = [&]() -> int {
-        if constexpr (ADAPT) return 0;
+        if constexpr (MODE == NT_WARM) return 0;
         else return A.record;
     };
     constexpr int NVM = KPAD + 4;                        // KPAD sums + one rider (pf_block_sum_mv takes multiples of 4)
@@ -165,6 +174,13 @@ __device__ __forceinline__ void nt_step_body(const NtArgs &A_) {
         double eps = sEps;
         const uint64_t seed = sSeed;
         const HmFactor F = {gVh, T, Vc, sqa};
+        // METRIC: the chain's scale; c_i w of a kick and c_i v_i of a drift (row i is the calling thread's own; without METRIC the plain operand)
+        // (macros on the constant METRIC and not hm_scaled of hmc_rows.h: through the function the step and warm kernels with staged rows
+        // allocate their registers differently -- three step kernels then reserve scratch -- although it returns its operand)
+        const double *sc = nullptr;
+        if constexpr (METRIC) sc = A.M.scale + kd;
+#define KSC_(i, w) (METRIC ? sc[i] * (w) : (w))
+#define VSC_(i) (METRIC ? sc[i] * V_(NT_V, i) : V_(NT_V, i))
         HM_STAGED_ROWS;                                      // (the L pass below reads the rows the R pass staged)
         auto vrow = [&](int i) -> const double * {
             if constexpr (RES) return sVh + (size_t)i * KPAD;
@@ -213,7 +229,7 @@ __device__ __forceinline__ void nt_step_body(const NtArgs &A_) {
 #pragma unroll
                 for (int q = 0; q < NT_NDOT; ++q) w[q] = 0.0;
                 for (int i = tid; i < d; i += HM_NT) {
-                    const double vl = fma(hk, V_(NT_WT, i), V_(NT_V, i)), rs = V_(NT_RHOS, i) + vl;
+                    const double vl = fma(hk, KSC_(i, V_(NT_WT, i)), V_(NT_V, i)), rs = V_(NT_RHOS, i) + vl;
                     V_(NT_V, i) = vl; V_(NT_RHOS, i) = rs;
                     if (pv) pv[i] = vl;
                     w[0] = fma(vl, vl, w[0]);
@@ -311,13 +327,13 @@ __device__ __forceinline__ void nt_step_body(const NtArgs &A_) {
                     S.dir = ndir;
                     const int e = ndir > 0 ? 1 : 0;
                     const double hk2 = (ndir > 0 ? 0.5 : -0.5) * eps;
-                    for (int i = tid; i < d; i += HM_NT) { V_(NT_RHOS, i) = 0.0; V_(NT_V, i) = fma(hk2, V_(NT_WE + e, i), V_(NT_VE + e, i)); }
+                    for (int i = tid; i < d; i += HM_NT) { V_(NT_RHOS, i) = 0.0; V_(NT_V, i) = fma(hk2, KSC_(i, V_(NT_WE + e, i)), V_(NT_VE + e, i)); }
                     bslot = NT_XE + e;
                     drift = true;
                 } else {
                     // ---- the next leaf of the sub-tree
                     S.n = n + 1;
-                    for (int i = tid; i < d; i += HM_NT) V_(NT_V, i) = fma(hk, V_(NT_WT, i), V_(NT_V, i));
+                    for (int i = tid; i < d; i += HM_NT) V_(NT_V, i) = fma(hk, KSC_(i, V_(NT_WT, i)), V_(NT_V, i));
                     drift = true;
                 }
             }
@@ -326,7 +342,13 @@ __device__ __forceinline__ void nt_step_body(const NtArgs &A_) {
             // ---- the warm-up transition S.t - 1 has ended: its trace, the update, the step size of the transition that opens below
             // (here and not in the branch above: fewer uniform values are live beside the constants of sqrt and exp)
             if (wend) {
-                if (tid == 0) sEps = hm_warm_end(A.ad, A.eps, K, k, S.t, A.t0, eps, S.sacc / (double)S.nleaf, wend - 1, S.nleaf);
+                bool wnd = false;                        // METRIC: the transition ended a metric window
+                if constexpr (METRIC)
+                    wnd = hm_metric_end<KPAD, RES, NRED>(F, L, A.M, A.ad, k, d, S.t - 1, A.x0 + kd, flip, [&](int i) { return V_(NT_X, i); });
+                if (tid == 0) {
+                    sEps = hm_warm_end(A.ad, A.eps, K, k, S.t, A.t0, eps, S.sacc / (double)S.nleaf, wend - 1, S.nleaf);
+                    if constexpr (METRIC) if (wnd) pf_adapt_restart(A.ad[k], sEps);
+                }
                 __syncthreads();
                 eps = sEps;
             }
@@ -342,7 +364,7 @@ __device__ __forceinline__ void nt_step_body(const NtArgs &A_) {
                 vv0 = fma(z, z, vv0);
                 V_(NT_XE, i) = xi; V_(NT_XE + 1, i) = xi; V_(NT_VE, i) = z; V_(NT_VE + 1, i) = z; V_(NT_WE, i) = wi; V_(NT_WE + 1, i) = wi;
                 V_(NT_XC, i) = xi; V_(NT_WC, i) = wi; V_(NT_RHO, i) = z; V_(NT_RHOS, i) = 0.0;
-                V_(NT_V, i) = fma(hk, wi, z);
+                V_(NT_V, i) = fma(hk, KSC_(i, wi), z);
             }
             S.phase = NT_LEAF; S.j = 0; S.n = 0; S.dir = ndir; S.nleaf = 0; S.sacc = 0.0;
             S.logW = 0.0; S.logWs = -INFINITY; S.lpc = S.lp;
@@ -354,7 +376,7 @@ __device__ __forceinline__ void nt_step_body(const NtArgs &A_) {
             // (hm_apply_L of hmc_rows.h, written out: see the rule for the base addresses above)
             const double se = ndir > 0 ? eps : -eps;
             __syncthreads();                                 // the head product above has read sHead
-            if (tid < KPAD) L.sHead[tid] = tid < d ? V_(NT_V, tid) : 0.0;
+            if (tid < KPAD) L.sHead[tid] = tid < d ? VSC_(tid) : 0.0;
             __syncthreads();
             if (tid < KPAD) {
                 double s = 0.0;
@@ -368,9 +390,9 @@ __device__ __forceinline__ void nt_step_body(const NtArgs &A_) {
             for (int q = 0; q < NVM; ++q) w[q] = 0.0;
             if (RES && !staged) {                            // (the opening launch of PFMI_NUTS_CONTINUE: no R-apply came before)
                 for (int i = tid; i < d; i += HM_NT)
-                    hm_row_axpy<KPAD, NVM, true>(gVh + (size_t)i * KPAD, sVh + (size_t)i * KPAD, i < KPAD ? L.sZ[i] : V_(NT_V, i), w);
+                    hm_row_axpy<KPAD, NVM, true>(gVh + (size_t)i * KPAD, sVh + (size_t)i * KPAD, i < KPAD ? L.sZ[i] : VSC_(i), w);
             } else {
-                for (int i = tid; i < d; i += HM_NT) hm_row_axpy<KPAD, NVM, false>(vrow(i), nullptr, i < KPAD ? L.sZ[i] : V_(NT_V, i), w);
+                for (int i = tid; i < d; i += HM_NT) hm_row_axpy<KPAD, NVM, false>(vrow(i), nullptr, i < KPAD ? L.sZ[i] : VSC_(i), w);
             }
             w[KPAD] = vv0;
             pf_block_sum_mv<NVM, NRED>(w, L.red, flip);
@@ -383,13 +405,15 @@ __device__ __forceinline__ void nt_step_body(const NtArgs &A_) {
             }
             __syncthreads();
             for (int i = tid; i < d; i += HM_NT) {
-                const double y = hm_row_sub<KPAD>(vrow(i), L.sTv, i < KPAD ? L.sZ[i] : V_(NT_V, i));
+                const double y = hm_row_sub<KPAD>(vrow(i), L.sTv, i < KPAD ? L.sZ[i] : VSC_(i));
                 X[i] = fma(se, sqa[i] * y, bslot < 0 ? X[i] : V_(bslot, i));
             }
         }
         __syncthreads();                                     // every thread has read S before thread 0 writes
         if (tid == 0) A.st[k] = S;
 #undef V_
+#undef KSC_
+#undef VSC_
     }
     // ---- progress of the round: the last workgroup publishes the number of chains still running
     if (tid == 0) {
@@ -404,11 +428,13 @@ __device__ __forceinline__ void nt_step_body(const NtArgs &A_) {
     }
 }
 
+#ifndef PF_CHAIN_METRIC_TU             // (nuts_metric_kernel.hip takes the body and nt_args from this file and defines its own kernels)
 template <int KPAD, bool RES>
-__global__ __launch_bounds__(HM_NT) void pf_nuts_step_kernel(NtArgs A_) { nt_step_body<KPAD, RES, false>(A_); }
+__global__ __launch_bounds__(HM_NT) void pf_nuts_step_kernel(NtArgs A_) { nt_step_body<KPAD, RES, NT_PLAIN>(A_); }
 
 template <int KPAD, bool RES>
-__global__ __launch_bounds__(HM_NT) void pf_nuts_warm_kernel(NtArgs A_) { nt_step_body<KPAD, RES, true>(A_); }
+__global__ __launch_bounds__(HM_NT) void pf_nuts_warm_kernel(NtArgs A_) { nt_step_body<KPAD, RES, NT_WARM>(A_); }
+#endif
 
 // ---------------------------------------------------------------------------------------------------
 static NtArgs nt_args(pfmi_ctx *c, int64_t round, int64_t prow, bool reopen) {
@@ -429,6 +455,7 @@ static NtArgs nt_args(pfmi_ctx *c, int64_t round, int64_t prow, bool reopen) {
     return A;
 }
 
+#ifndef PF_CHAIN_METRIC_TU
 size_t pf_nuts_chain_bytes() { return sizeof(NtChain); }
 int pf_nuts_vec_slots(int max_depth) { return NT_VECS + 2 * max_depth; }
 
@@ -439,6 +466,7 @@ int32_t pf_launch_nuts_init(pfmi_ctx *c, hipStream_t s) {
 }
 
 struct NtFamily {
+    static constexpr bool has_warm = true;
     template <int KPAD, bool RES, bool ADAPT>
     static auto kernel() { return ADAPT ? &pf_nuts_warm_kernel<KPAD, RES> : &pf_nuts_step_kernel<KPAD, RES>; }
 };
@@ -464,3 +492,4 @@ int32_t pf_nuts_chain_flags(pfmi_ctx *c, std::vector<int32_t> &dead, int64_t *la
 int32_t pf_launch_nuts_step(pfmi_ctx *c, int64_t round, int64_t prow, bool reopen, hipStream_t s) {
     return hm_launch_step<NtFamily>(c, "nuts", nt_args(c, round, prow, reopen), s);
 }
+#endif

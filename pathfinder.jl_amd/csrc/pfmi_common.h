@@ -123,6 +123,12 @@ struct HmcState {
     bool adapting = false;        // the call in flight launches the warm kernels (a later plain CONTINUE does not)
     int64_t W = 0;                // > 0: the adaptation states and the warm-up traces [K][W] are resident (pfmi_adapt_get)
     bool eps_kept = false;        // a plain CONTINUE has replaced hm_eps: the adaptive run's final step sizes are the copy in hm_adapt
+    // the per-coordinate scale (pfmi_chain_scale_set, pfmi_*_adapt_metric_enqueue): the metric kernels step chains that carry one
+    bool scaled = false;          // hm_scale holds the chains' scale
+    bool metric_run = false;      // the adaptive run whose traces are resident was a pfmi_*_adapt_metric_enqueue (pfmi_adapt_metric_get)
+    bool rec_u = false;           // ... with PFMI_ADAPT_RECORD_WHITENED
+    int nwin = 0;                 // its metric windows (adapt.h: pf_adapt_windows); 0: W < 20
+    int64_t win_init = 0, win_ends[32] = {};
 };
 
 struct pfmi_ctx {
@@ -288,6 +294,10 @@ struct pfmi_ctx {
     DevBuf hm_draws, hm_lp, hm_acc, hm_de, hm_div;      // the last call's records [K][T][d], [K][T]
     DevBuf hm_pX, hm_pout, hm_pv;                       // PFMI_HMC_RECORD_PATH: every round's X, closure output and v
     DevBuf hm_adapt;                                    // adaptive runs: PfAdapt [K], PfWarmRow [K][W], then [K] final step sizes (adapt.h, api_adapt.hip)
+    DevBuf hm_scale;                                    // [K][d] the chains' resident scale (hmc.scaled; pfmi_chain_scale_set, the metric windows)
+    DevBuf hm_metric;                                   // runs with metric windows: window table, Welford state, scale trace, whitened rows (pf_metric_layout, api_adapt.hip)
+    std::vector<double> scale_staged;                   // pfmi_chain_scale_set: [scale_staged_K][d] for the next enqueue; empty: none
+    int32_t scale_staged_K = 0;
     DevBuf nt_vec, nt_st, nt_depth, nt_nleap, nt_pev, nt_ctr;   // NUTS: the chains' vectors and checkpoints, their scalars, statistics, events
     int64_t *nt_status = nullptr; // page-locked: round << 32 | chains still running, written by the last workgroup of each NUTS round
     std::map<std::string, int64_t> hmc_plans;           // step launches per plan "hmc:<KPAD>:<res|stream>" (pfmi_kernel_time)
@@ -421,6 +431,9 @@ int pf_nuts_vec_slots(int max_depth);
 int32_t pf_launch_nuts_init(pfmi_ctx *c, hipStream_t s);
 int32_t pf_launch_nuts_step(pfmi_ctx *c, int64_t round, int64_t prow, bool reopen, hipStream_t s);
 int32_t pf_nuts_chain_flags(pfmi_ctx *c, std::vector<int32_t> &dead, int64_t *last_round);
+// hmc_metric_kernel.hip, nuts_metric_kernel.hip: the step launch of chains that carry a scale (c->hmc.scaled), plain or adaptive
+int32_t pf_launch_hmc_metric_step(pfmi_ctx *c, int64_t round, hipStream_t s);
+int32_t pf_launch_nuts_metric_step(pfmi_ctx *c, int64_t round, int64_t prow, bool reopen, hipStream_t s);
 // chain_diag_kernels.hip: bytes of c->cd_ws for K chains of T draws of d coordinates (+ the logp series), and the seven outputs of the
 // device records d_rec [K][T][d] (d_lp [K][T] or NULL) into *d_out [7][d (+ 1)] inside that workspace; enqueued, not waited for
 size_t pf_chain_diag_bytes(int d, int64_t T, int K, bool with_lp);

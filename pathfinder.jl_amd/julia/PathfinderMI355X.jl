@@ -1454,6 +1454,92 @@ function nuts_adapt(b::Batch, points::AbstractVector{<:Integer}, x0::AbstractMat
             warmup = _adapt_get(b, K, W))
 end
 
+# ---- windowed metric adaptation: the warm-up also learns a per-coordinate scale of every chain on its fit's factor, in Stan's windows
+# ("initialise a metric adaptation" of docs/src/examples/initializing-hmc.md; include/pfmi.h: pfmi_hmc_adapt_metric_enqueue).
+"""
+    adapt_windows(nwarmup) -> (init, term, ends)
+
+The metric windows of a warm-up of `nwarmup` transitions: the first window's start, the transitions after the last window, and the windows'
+exclusive ends (empty below 20).
+"""
+function adapt_windows(nwarmup::Integer)
+    init = Ref{Int64}(0); term = Ref{Int64}(0); n = Ref{Int32}(0); ends = Vector{Int64}(undef, 32)
+    check(ccall((:pfmi_adapt_windows, libpfmi), Int32, (Int64, Ref{Int64}, Ref{Int64}, Ptr{Int64}, Int32, Ref{Int32}),
+                nwarmup, init, term, ends, Int32(32), n))
+    return (init = init[], term = term[], ends = ends[1:n[]])
+end
+"""
+    chain_scale_set(b::Batch, scale)
+
+Stages the per-coordinate scale `(d, K)` of K chains for the next `hmc` / `nuts` call (fresh or continued); `nothing` clears the staging.
+"""
+function chain_scale_set(b::Batch, scale::Union{Nothing, AbstractMatrix{Float64}})
+    _live(b.eng, b.gen)
+    if scale === nothing
+        check(ccall((:pfmi_chain_scale_set, libpfmi), Int32, (Ptr{Cvoid}, Int32, Ptr{Float64}), b.eng.ptr, Int32(0), C_NULL))
+    else
+        size(scale, 1) == b.dim || throw(ArgumentError("chain_scale_set: scale must be (d, K)"))
+        check(ccall((:pfmi_chain_scale_set, libpfmi), Int32, (Ptr{Cvoid}, Int32, Ptr{Float64}), b.eng.ptr, size(scale, 2), Matrix{Float64}(scale)))
+    end
+    return nothing
+end
+function _adapt_metric_get(b::Batch, K::Integer, W::Integer)
+    w = adapt_windows(W); nw = length(w.ends)
+    n = Ref{Int32}(0); ends = Vector{Int64}(undef, 32); tr = Array{Float64}(undef, b.dim, nw, K)
+    check(ccall((:pfmi_adapt_metric_get, libpfmi), Int32, (Ptr{Cvoid}, Ref{Int32}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}),
+                b.eng.ptr, n, ends, tr, C_NULL))
+    return (window_ends = ends[1:n[]], scale_trace = tr, metric_scale = nw > 0 ? tr[:, nw, :] : ones(b.dim, K))
+end
+"""
+    hmc_adapt_metric(b::Batch, points, x0, seeds, step_size0; nleapfrog = 8, nwarmup, ntransitions, target_accept = 0.8)
+
+`hmc_adapt` whose warm-up also adapts every chain's per-coordinate scale in windows.  `warmup` gains `window_ends`, `scale_trace`
+`(d, windows, K)` and `metric_scale` `(d, K)`, the scale the sampling transitions used (and a later continued call uses).
+"""
+function hmc_adapt_metric(b::Batch, points::AbstractVector{<:Integer}, x0::AbstractMatrix{Float64}, seeds::AbstractVector{UInt64},
+                          step_size0::AbstractVector{Float64}; nleapfrog::Integer = 8, nwarmup::Integer, ntransitions::Integer,
+                          target_accept::Real = 0.8)
+    _live(b.eng, b.gen)
+    K = length(points); d = b.dim; T = Int(ntransitions); W = Int(nwarmup)
+    (length(seeds) == K && length(step_size0) == K && size(x0) == (d, K)) || throw(ArgumentError("hmc_adapt_metric: K values per argument"))
+    pts = Vector{Int64}(points); X0 = Matrix{Float64}(x0); sd = Vector{UInt64}(seeds); ϵ = Vector{Float64}(step_size0)
+    check(ccall((:pfmi_hmc_adapt_metric_enqueue, libpfmi), Int32,
+                (Ptr{Cvoid}, Int32, Ptr{Int64}, Ptr{Float64}, Ptr{UInt64}, Ptr{Float64}, Int32, Int64, Int64, Float64, Int32),
+                b.eng.ptr, K, pts, X0, sd, ϵ, nleapfrog, W, T, Float64(target_accept), Int32(0)))
+    check(ccall((:pfmi_hmc_wait, libpfmi), Int32, (Ptr{Cvoid},), b.eng.ptr))
+    draws = Array{Float64}(undef, d, T, K)
+    lp = Matrix{Float64}(undef, T, K); acc = similar(lp); de = similar(lp); dv = Matrix{Int32}(undef, T, K)
+    check(ccall((:pfmi_hmc_get, libpfmi), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+                b.eng.ptr, draws, lp, acc, de, dv))
+    return (draws = draws, logp = lp, accept_prob = acc, energy_error = de, divergent = dv,
+            warmup = merge(_adapt_get(b, K, W), _adapt_metric_get(b, K, W)))
+end
+"""
+    nuts_adapt_metric(b::Batch, points, x0, seeds, step_size0; max_depth = 10, nwarmup, ntransitions, target_accept = 0.8)
+
+`nuts_adapt` with the metric windows of `hmc_adapt_metric`.
+"""
+function nuts_adapt_metric(b::Batch, points::AbstractVector{<:Integer}, x0::AbstractMatrix{Float64}, seeds::AbstractVector{UInt64},
+                           step_size0::AbstractVector{Float64}; max_depth::Integer = 10, nwarmup::Integer, ntransitions::Integer,
+                           target_accept::Real = 0.8)
+    _live(b.eng, b.gen)
+    K = length(points); d = b.dim; T = Int(ntransitions); W = Int(nwarmup)
+    (length(seeds) == K && length(step_size0) == K && size(x0) == (d, K)) || throw(ArgumentError("nuts_adapt_metric: K values per argument"))
+    pts = Vector{Int64}(points); X0 = Matrix{Float64}(x0); sd = Vector{UInt64}(seeds); ϵ = Vector{Float64}(step_size0)
+    check(ccall((:pfmi_nuts_adapt_metric_enqueue, libpfmi), Int32,
+                (Ptr{Cvoid}, Int32, Ptr{Int64}, Ptr{Float64}, Ptr{UInt64}, Ptr{Float64}, Int32, Int64, Int64, Float64, Int32),
+                b.eng.ptr, K, pts, X0, sd, ϵ, max_depth, W, T, Float64(target_accept), Int32(0)))
+    check(ccall((:pfmi_nuts_wait, libpfmi), Int32, (Ptr{Cvoid},), b.eng.ptr))
+    draws = Array{Float64}(undef, d, T, K)
+    lp = Matrix{Float64}(undef, T, K); acc = similar(lp); de = similar(lp); dv = Matrix{Int32}(undef, T, K)
+    check(ccall((:pfmi_hmc_get, libpfmi), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+                b.eng.ptr, draws, lp, acc, de, dv))
+    depth = Matrix{Int32}(undef, T, K); nleap = Matrix{Int32}(undef, T, K)
+    check(ccall((:pfmi_nuts_get_stats, libpfmi), Int32, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}), b.eng.ptr, depth, nleap))
+    return (draws = draws, logp = lp, accept_prob = acc, energy_error = de, divergent = dv, tree_depth = depth, n_leapfrog = nleap,
+            warmup = merge(_adapt_get(b, K, W), _adapt_metric_get(b, K, W)))
+end
+
 # ---- chain diagnostics on the device: what summarystats(chns) reports in docs/src/examples/turing.md and initializing-hmc.md
 function _chain_diagnostics(eng::Engine, source::Integer, draws, d::Integer, T::Integer, K::Integer, flags::Integer, len::Integer)
     out = [Vector{Float64}(undef, len) for _ in 1:7]

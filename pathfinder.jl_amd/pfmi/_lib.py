@@ -56,6 +56,8 @@ SYMBOLS = [
     "pfmi_chain_diagnostics",
     "pfmi_nuts_enqueue", "pfmi_nuts_pump", "pfmi_nuts_wait", "pfmi_nuts_get_stats", "pfmi_nuts_get_path", "pfmi_nuts_stats",
     "pfmi_hmc_adapt_enqueue", "pfmi_nuts_adapt_enqueue", "pfmi_adapt_get", "pfmi_host_dual_averaging",
+    "pfmi_chain_scale_set", "pfmi_hmc_adapt_metric_enqueue", "pfmi_nuts_adapt_metric_enqueue", "pfmi_adapt_metric_get", "pfmi_adapt_windows",
+    "pfmi_host_metric_update",
 ]
 
 # declared argument types (entry points not listed here take what the caller wraps by hand)
@@ -88,6 +90,14 @@ ARGTYPES = {
                                 C.c_double, C.c_int32],
     "pfmi_adapt_get": [C.c_void_p, _dp, _dp, _dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
     "pfmi_host_dual_averaging": [C.c_int64, C.c_double, C.c_double, _dp, _dp, _dp],
+    "pfmi_chain_scale_set": [C.c_void_p, C.c_int32, _dp],
+    "pfmi_hmc_adapt_metric_enqueue": [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), _dp, C.POINTER(C.c_uint64), _dp, C.c_int32, C.c_int64,
+                                      C.c_int64, C.c_double, C.c_int32],
+    "pfmi_nuts_adapt_metric_enqueue": [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), _dp, C.POINTER(C.c_uint64), _dp, C.c_int32, C.c_int64,
+                                       C.c_int64, C.c_double, C.c_int32],
+    "pfmi_adapt_metric_get": [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64), _dp, _dp],
+    "pfmi_adapt_windows": [C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_int32)],
+    "pfmi_host_metric_update": [C.c_int64, C.c_int32, _dp, _dp, _dp, C.POINTER(C.c_int32)],
 }
 
 

@@ -21,6 +21,15 @@ def _d(a):
     return a.ctypes.data_as(_dp) if a is not None else None
 
 
+def adapt_windows(nwarmup):
+    """the metric windows of a warm-up of `nwarmup` transitions (pfmi_adapt_windows, the host build of the device's rule): (init, term,
+    ends) -- the first window's start, the transitions after the last window, the windows' exclusive ends (int64; empty below 20)"""
+    init, term, n = C.c_int64(), C.c_int64(), C.c_int32()
+    ends = np.zeros(32, dtype=np.int64)
+    check(_lib.lib().pfmi_adapt_windows(int(nwarmup), C.byref(init), C.byref(term), ends.ctypes.data_as(_i64p), len(ends), C.byref(n)))
+    return init.value, term.value, ends[:n.value].copy()
+
+
 def _f64_of_shape(who, what, a, shape):
     """the optional argument `what` of Engine method `who` as a contiguous float64 array of `shape` (a name in it: any extent), None
     when it is None; ValueError otherwise"""
@@ -106,6 +115,7 @@ class Engine:
         self.J = 0
         self._hmc = None                          # (K, T) of the last hmc_enqueue that succeeded
         self._adapt = None                        # (K, W) of the adaptive run whose traces are resident (adapt_get)
+        self._metric = None                       # (K, W, whitened rows kept) when that run had metric windows (adapt_metric_get)
         self.hmc_runs = 0                         # hmc_enqueue calls that succeeded (HMCResult.summary: is a result still the resident run?)
 
     def close(self):
@@ -486,8 +496,9 @@ class Engine:
     # ---- static HMC with a fitted metric (include/pfmi.h: pfmi_hmc_enqueue) ---------------------------------------------------
     HMC_CONTINUE, HMC_RECORD_PATH = 1, 2
 
-    def _chain_enqueue(self, name, points, x0, seeds, step_size, param, ntransitions, flags, nwarmup=None, target_accept=None):
-        """the one enqueue of both samplers: pfmi_<name>_enqueue, or (nwarmup given) pfmi_<name>_adapt_enqueue, which takes no x0 = None"""
+    def _chain_enqueue(self, name, points, x0, seeds, step_size, param, ntransitions, flags, nwarmup=None, target_accept=None, metric=False):
+        """the one enqueue of both samplers: pfmi_<name>_enqueue, or (nwarmup given) pfmi_<name>_adapt_enqueue (metric=True:
+        pfmi_<name>_adapt_metric_enqueue), which take no x0 = None"""
         points = np.ascontiguousarray(points, dtype=np.int64)
         K = len(points)
         seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
@@ -502,7 +513,8 @@ class Engine:
         if nwarmup is None:
             rc = getattr(self.L, f"pfmi_{name}_enqueue")(*head, int(ntransitions), int(flags))
         else:
-            rc = getattr(self.L, f"pfmi_{name}_adapt_enqueue")(*head, int(nwarmup), int(ntransitions), float(target_accept), int(flags))
+            fn = getattr(self.L, f"pfmi_{name}_adapt_metric_enqueue" if metric else f"pfmi_{name}_adapt_enqueue")
+            rc = fn(*head, int(nwarmup), int(ntransitions), float(target_accept), int(flags))
         if getattr(self.target, "pending_error", None) is not None:
             self.sync()
             self._raise_target_error()
@@ -510,8 +522,9 @@ class Engine:
         self._hmc = (K, int(ntransitions))
         if nwarmup is not None:
             self._adapt = (K, int(nwarmup))
+            self._metric = (K, int(nwarmup), bool(flags & self.ADAPT_RECORD_WHITENED)) if metric else None
         elif not flags & self.HMC_CONTINUE:
-            self._adapt = None
+            self._adapt = self._metric = None
         self.hmc_runs += 1
 
     def _chain_path(self, who, stats, get_path, round0, nrounds, events):
@@ -613,6 +626,48 @@ class Engine:
     def nuts_adapt_enqueue(self, points, x0, seeds, step_size0, max_depth, nwarmup, ntransitions, target_accept=0.8, flags=0):
         """nuts_enqueue with `nwarmup` adaptive warm-up transitions in front (hmc_adapt_enqueue); nuts_pump / nuts_wait issue the rounds"""
         self._chain_enqueue("nuts", points, x0, seeds, step_size0, max_depth, ntransitions, flags, nwarmup, target_accept)
+
+    # ---- windowed metric adaptation (include/pfmi.h: pfmi_chain_scale_set, pfmi_hmc_adapt_metric_enqueue, pfmi_nuts_adapt_metric_enqueue) ----
+    ADAPT_NO_METRIC_WINDOW, ADAPT_KEPT_METRIC, ADAPT_RECORD_WHITENED, ADAPT_MAX_WINDOWS = 2, 4, 4, 32
+
+    def chain_scale_set(self, scale):
+        """stages the per-coordinate scale (K, d) of K chains for the next hmc_enqueue / nuts_enqueue (fresh or cont=True), where it becomes
+        their resident scale: chain k then runs on the metric L diag(scale[k])^2 L'.  None clears the staging."""
+        if scale is None:
+            check(self.L.pfmi_chain_scale_set(self.ctx, 0, None))
+            return
+        c = np.ascontiguousarray(scale, dtype=np.float64)
+        if c.ndim != 2 or c.shape[1] != self.d:
+            raise ValueError(f"chain_scale_set: scale must be (K, {self.d})")
+        check(self.L.pfmi_chain_scale_set(self.ctx, c.shape[0], _d(c)))
+
+    def hmc_adapt_metric_enqueue(self, points, x0, seeds, step_size0, nleapfrog, nwarmup, ntransitions, target_accept=0.8, record_whitened=False):
+        """hmc_adapt_enqueue whose warm-up also adapts every chain's per-coordinate scale in Stan's windows (include/pfmi.h); afterwards the
+        adapted scale is the chains' resident one.  record_whitened keeps the whitened row of every window transition (adapt_metric_get)."""
+        self._chain_enqueue("hmc", points, x0, seeds, step_size0, nleapfrog, ntransitions, self.ADAPT_RECORD_WHITENED if record_whitened else 0,
+                            nwarmup, target_accept, metric=True)
+
+    def nuts_adapt_metric_enqueue(self, points, x0, seeds, step_size0, max_depth, nwarmup, ntransitions, target_accept=0.8, record_whitened=False):
+        """nuts_adapt_enqueue with the metric windows of hmc_adapt_metric_enqueue; nuts_pump / nuts_wait issue the rounds"""
+        self._chain_enqueue("nuts", points, x0, seeds, step_size0, max_depth, ntransitions, self.ADAPT_RECORD_WHITENED if record_whitened else 0,
+                            nwarmup, target_accept, metric=True)
+
+    def adapt_metric_get(self):
+        """the metric windows of the last hmc_adapt_metric_enqueue / nuts_adapt_metric_enqueue: dict of window_ends int64 (nwin,), scale_trace
+        (K, nwin, d) the scale each window left, and with record_whitened `whitened` (K, n, d), the whitened rows of the n window transitions"""
+        if self._metric is None:
+            check(self.L.pfmi_adapt_metric_get(self.ctx, None, None, None, None))            # (PFMI_ERR_STATE: the library's message)
+            raise _lib.PfmiError("adapt_metric_get: no run with metric windows was enqueued through this engine")
+        K, W, rec = self._metric
+        init, _, ends = adapt_windows(W)
+        out = {"window_ends": ends, "scale_trace": np.empty((K, len(ends), self.d))}
+        if rec and len(ends):
+            out["whitened"] = np.empty((K, int(ends[-1]) - init, self.d))
+        nwin, e = C.c_int32(), np.zeros(self.ADAPT_MAX_WINDOWS, dtype=np.int64)
+        check(self.L.pfmi_adapt_metric_get(self.ctx, C.byref(nwin), e.ctypes.data_as(_i64p), _d(out["scale_trace"]),
+                                           _d(out["whitened"]) if "whitened" in out else None))
+        assert nwin.value == len(ends) and np.array_equal(e[:nwin.value], ends)
+        return out
 
     def adapt_get(self):
         """the last adaptive run's warm-up: dict of step_size (K,) the sampling transitions' step sizes, eps_trace, accept_trace (K, W),

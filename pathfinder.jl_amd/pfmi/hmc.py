@@ -6,7 +6,11 @@ The reference's worked example docs/src/examples/initializing-hmc.md, third way:
 where the fits already are.  `hmc`: a fixed number of leapfrog steps per transition, Metropolis correction, full momentum refresh.
 `nuts`: multinomial NUTS, trees of at most 2^max_depth - 1 leapfrog steps.  Both share one driver (`_run`): the same starts, metric,
 seeds and step-size adaptation.  The target must be a device closure with a gradient (DeviceCallbackTarget(..., grad_fn=...),
-TorchDeviceTarget(..., grad=...)); one engine only."""
+TorchDeviceTarget(..., grad=...)); one engine only.
+
+The example's second way, "initialise a metric adaptation" from the fit, is adapt="device" with adapt_metric=True (include/pfmi.h:
+pfmi_hmc_adapt_metric_enqueue): the warm-up also learns a per-coordinate scale c of every chain in Stan's windows, in the coordinates
+whitened by the fit's factor, so that the chain samples with L diag(c)^2 L'.  A start from a poor fit no longer keeps that fit's metric."""
 import sys
 import types
 from dataclasses import dataclass, field
@@ -103,7 +107,10 @@ class HMCResult:
     engine: Any = field(repr=False, default=None)
     run: int = 0                      # engine.hmc_runs after this result's last hmc_enqueue (0: unknown)
     # adapt="device": the warm-up's traces (Engine.adapt_get: eps_trace, accept_trace, divergent, n_leapfrog (nchains, nwarmup), status)
+    # adapt_metric=True: also window_ends (nwin,) and scale_trace (nchains, nwin, d) (Engine.adapt_metric_get)
     warmup: Any = field(default=None, kw_only=True)
+    # adapt_metric=True: (nchains, d) the per-coordinate scale the sampling phase used on the fit's factor (None: the fitted metric itself)
+    metric_scale: Any = field(default=None, kw_only=True)
 
     def summary(self):
         """ChainSummary of the draws and of logp.  While this result is still the engine's latest run the resident records are used; after
@@ -149,9 +156,11 @@ def _starts_and_points(result):
     return dist.engine, draws, np.full(draws.shape[1], dist.point, dtype=np.int64), dist.token
 
 
-def _check_adapt(adapt, auto, nwarmup):
+def _check_adapt(adapt, auto, nwarmup, adapt_metric=False):
     if adapt not in ("windows", "device"):
         raise ValueError('adapt must be "windows" or "device"')
+    if adapt_metric and adapt != "device":
+        raise ValueError('adapt_metric=True adapts the metric in the windows of the device warm-up: it needs adapt="device"')
     if adapt == "device" and not (auto and nwarmup >= 1):
         raise ValueError('adapt="device" adapts the step size during the warm-up: it needs step_size="auto" and nwarmup >= 1')
     return adapt == "device"
@@ -174,7 +183,7 @@ class NUTSResult(HMCResult):
         return "\n".join(lines)
 
 
-def _run(name, result, ndraws, nchains, nwarmup, step_size, param, rng, target_accept, window, adapt):
+def _run(name, result, ndraws, nchains, nwarmup, step_size, param, rng, target_accept, window, adapt, adapt_metric=False):
     """the driver behind hmc() and nuts(): `name` is the sampler ("hmc" / "nuts"), `param` its nleapfrog / max_depth"""
     is_nuts = name == "nuts"
     eng, starts, pts, token = _starts_and_points(result)
@@ -199,12 +208,19 @@ def _run(name, result, ndraws, nchains, nwarmup, step_size, param, rng, target_a
         raise ValueError('step_size must be a number, an array of nchains numbers or "auto"')
     eps = np.full(nchains, d ** -0.25) if auto else np.broadcast_to(np.asarray(step_size, dtype=np.float64), (nchains,)).copy()
     enqueue, wait = (eng.nuts_enqueue, eng.nuts_wait) if is_nuts else (eng.hmc_enqueue, eng.hmc_wait)
-    warm = None
-    if _check_adapt(adapt, auto, int(nwarmup)):
-        (eng.nuts_adapt_enqueue if is_nuts else eng.hmc_adapt_enqueue)(pts, x0, seeds, eps, param, int(nwarmup), int(ndraws), target_accept)
+    warm = scale = None
+    if _check_adapt(adapt, auto, int(nwarmup), adapt_metric):
+        if adapt_metric:
+            aenq = eng.nuts_adapt_metric_enqueue if is_nuts else eng.hmc_adapt_metric_enqueue
+        else:
+            aenq = eng.nuts_adapt_enqueue if is_nuts else eng.hmc_adapt_enqueue
+        aenq(pts, x0, seeds, eps, param, int(nwarmup), int(ndraws), target_accept)
         wait()
         got, warm = eng.hmc_get(), eng.adapt_get()
         eps = warm.pop("step_size")
+        if adapt_metric:
+            warm.update(eng.adapt_metric_get())
+            scale = warm["scale_trace"][:, -1].copy() if len(warm["window_ends"]) else np.ones((nchains, d))
     else:
         done, first = 0, True
         if nwarmup > 0:
@@ -228,11 +244,12 @@ def _run(name, result, ndraws, nchains, nwarmup, step_size, param, rng, target_a
     rows = (got["draws"], got["logp"], got["accept_prob"], got["energy_error"], got["divergent"], eps, np.array(pts))
     if is_nuts:
         depth, nleap = eng.nuts_get_stats()
-        return NUTSResult(*rows, 0, int(nwarmup), eng, eng.hmc_runs, depth, nleap, int(param), warmup=warm)
-    return HMCResult(*rows, int(param), int(nwarmup), eng, eng.hmc_runs, warmup=warm)
+        return NUTSResult(*rows, 0, int(nwarmup), eng, eng.hmc_runs, depth, nleap, int(param), warmup=warm, metric_scale=scale)
+    return HMCResult(*rows, int(param), int(nwarmup), eng, eng.hmc_runs, warmup=warm, metric_scale=scale)
 
 
-def hmc(result, ndraws, *, nchains=None, nwarmup=0, step_size="auto", nleapfrog=8, rng=None, target_accept=0.8, window=10, adapt="windows"):
+def hmc(result, ndraws, *, nchains=None, nwarmup=0, step_size="auto", nleapfrog=8, rng=None, target_accept=0.8, window=10, adapt="windows",
+        adapt_metric=False):
     """`ndraws` transitions of `nchains` chains of static HMC from a PathfinderResult / MultiPathfinderResult.
 
     Chain c starts at result.draws[:, c] (resample(result, nchains, replace=False) first gives distinct starts) and uses the best fit of
@@ -240,16 +257,20 @@ def hmc(result, ndraws, *, nchains=None, nwarmup=0, step_size="auto", nleapfrog=
     `nwarmup` warm-up transitions between windows of `window` transitions by dual averaging on the window's mean acceptance
     (dual_averaging_update); the warm-up draws are discarded and sampling uses the averaged step size.  adapt="device" (step_size="auto"
     only): the device updates every chain's step size after every warm-up transition (include/pfmi.h: pfmi_hmc_adapt_enqueue); warm-up and
-    sampling are ONE enqueue, and the result's `warmup` holds the traces."""
-    return _run("hmc", result, ndraws, nchains, nwarmup, step_size, nleapfrog, rng, target_accept, window, adapt)
+    sampling are ONE enqueue, and the result's `warmup` holds the traces.  adapt_metric=True (adapt="device" only): the warm-up also adapts
+    a per-coordinate scale of every chain on its fit's factor in Stan's windows (pfmi_hmc_adapt_metric_enqueue; no window below 20 warm-up
+    transitions); `metric_scale` is the scale the sampling used, `warmup` also holds window_ends and scale_trace."""
+    return _run("hmc", result, ndraws, nchains, nwarmup, step_size, nleapfrog, rng, target_accept, window, adapt, adapt_metric)
 
 
-def nuts(result, ndraws, *, nchains=None, nwarmup=0, step_size="auto", max_depth=10, rng=None, target_accept=0.8, window=10, adapt="windows"):
+def nuts(result, ndraws, *, nchains=None, nwarmup=0, step_size="auto", max_depth=10, rng=None, target_accept=0.8, window=10, adapt="windows",
+         adapt_metric=False):
     """`ndraws` transitions of `nchains` chains of multinomial NUTS from a PathfinderResult / MultiPathfinderResult: the starts, metrics,
     seeds and step-size rule of `hmc` (dual averaging between windows of `window` warm-up transitions on the windows' mean accept_prob,
     the mean over a tree's leaves of min(1, exp(H0 - H))), with trees of at most 2^max_depth - 1 leapfrog steps instead of a fixed count.
-    adapt="device": as for `hmc`, one enqueue whose warm-up adapts on the device after every transition (pfmi_nuts_adapt_enqueue)."""
-    return _run("nuts", result, ndraws, nchains, nwarmup, step_size, max_depth, rng, target_accept, window, adapt)
+    adapt="device": as for `hmc`, one enqueue whose warm-up adapts on the device after every transition (pfmi_nuts_adapt_enqueue);
+    adapt_metric=True: with the metric windows of `hmc` (pfmi_nuts_adapt_metric_enqueue)."""
+    return _run("nuts", result, ndraws, nchains, nwarmup, step_size, max_depth, rng, target_accept, window, adapt, adapt_metric)
 
 
 class _CallableModule(types.ModuleType):
