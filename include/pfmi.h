@@ -537,6 +537,71 @@ int32_t pfmi_adapt_metric_get(pfmi_ctx *ctx, int32_t *nwindows, int64_t *ends, d
 int32_t pfmi_adapt_windows(int64_t nwarmup, int64_t *init, int64_t *term, int64_t *ends, int32_t cap, int32_t *nwindows);
 int32_t pfmi_host_metric_update(int64_t n, int32_t d, const double *u, const double *scale_in, double *scale_out, int32_t *status);
 
+/* ---- ChEES-HMC: a shared step size and a trajectory length learned across the chains ------------------------------------------------- */
+/* Hoffman, Radul & Sountsov (2021), for many chains resident on one device.  Every transition is pfmi_hmc_enqueue's (steps 1 - 6 above,
+ * the same generators, streams and draw indices, chain k on its own fit point's factor) with ONE step size e and ONE leapfrog count for
+ * all chains, so the chains run in lockstep and no closure column is wasted; what static HMC makes the caller guess, the trajectory
+ * length tau, is learned during the warm-up from a statistic ACROSS the chains.  The rule (one source for host and device, csrc/adapt.h):
+ *   transition t (0-based, over warm-up and sampling, carried across CONTINUE):  h_t = the base-2 radical inverse of t + 1 (the 32-bit
+ *   integer bit-reversed, times 2^-32: 1/2, 1/4, 3/4, 1/8, ...);  n = ceil((h_t tau) / e);  L_t = min(max(n, 1), max_leapfrog);  n >
+ *   max_leapfrog sets PFMI_CHEES_CLAMPED.
+ *   After warm-up transition t < W, with x_k the state before it, x'_k the trial point at its end, a_k its accept_prob (0 when divergent)
+ *   and u'_k = L_k v'_k the x-space velocity at its end (v'_k the whitened momentum after the last half kick) -- sums over chains in chain
+ *   order, chains with a_k = 0 LEFT OUT (their x' may be non-finite), sums over coordinates fixed-order block sums:
+ *     A = sum_k a_k;  xbar_i = (sum_k x_k,i) / K;  xbar'_i = (sum_k a_k x'_k,i) / A
+ *     p_k = sum_i (x_k,i - xbar_i)^2;  q_k = sum_i (x'_k,i - xbar'_i)^2;  r_k = sum_i (x'_k,i - xbar'_i) u'_k,i
+ *     g = h_t tau (sum_k a_k (q_k - p_k) r_k) / A                       (the gradient of the ChEES criterion with respect to log tau)
+ *     hm = 0 if any a_k = 0, else K / sum_k (1 / a_k);  the dual averaging of pfmi_hmc_adapt_enqueue on hm gives le, leb, m;  e+ = exp(le)
+ *     A > 0 and g finite:  s <- 0.95 s + 0.05 g^2,  b <- 0.95 b (b_0 = 1),  lt = log tau + 0.025 g / (sqrt(s / (1 - b)) + 1e-8)   (Adam)
+ *     else                 lt = log tau and PFMI_CHEES_KEPT_TRAJ is set
+ *     w = m^(-3/4);  ltb <- w lt + (1 - w) ltb (ltb_0 = 0);  tau+ = min(max(exp(lt), e+), max_leapfrog e+)
+ *   (a value that is not positive and finite keeps tau and sets PFMI_CHEES_KEPT_TRAJ; a step size likewise: PFMI_ADAPT_KEPT_STEP).  After
+ *   t = W - 1 sampling uses e = exp(leb) and tau = min(max(exp(ltb), e), max_leapfrog e); the sampling transitions keep the jitter h_t.
+ * step_size0: the one initial step size; traj_length0: the initial tau, 0 for step_size0.  nwarmup = 0 samples with both as given.
+ * flags: PFMI_HMC_CONTINUE (nwarmup = 0 only, ChEES chains only: t goes on), PFMI_HMC_RECORD_PATH (one row per round, room for the cap),
+ * PFMI_CHEES_RECORD_UPDATE (keeps x, x' and u' of every update: pfmi_chees_get_update).
+ * Rounds: (fresh ? 1 : 0) + sum_t L_t, decided on the device; the cap is (fresh ? 1 : 0) + (W + T) max_leapfrog.  _enqueue issues a first
+ * window and returns, pfmi_chees_pump / pfmi_chees_wait are pfmi_nuts_pump / pfmi_nuts_wait's counterparts (one pump serves both).  Rounds
+ * issued ahead of the progress word idle.  Two equal runs give equal bits.
+ * The warm-up fills the traces of pfmi_hmc_adapt_enqueue (eps: the shared step size, accept: a_k, n_leapfrog: L_t), so pfmi_adapt_get,
+ * pfmi_hmc_get, pfmi_hmc_draws_dev, pfmi_hmc_get_path and pfmi_chain_diagnostics(PFMI_CHAIN_SRC_HMC) serve a ChEES run after its wait.
+ * Errors are pfmi_hmc_enqueue's; also PFMI_ERR_ARG for max_leapfrog outside 1 .. 1024, target_accept outside (0, 1), traj_length0 < 0 or
+ * not finite, nwarmup < 0, CONTINUE with nwarmup > 0; PFMI_ERR_UNSUPPORTED for a staged scale (pfmi_chain_scale_set) and for
+ * nwarmup + ntransitions >= 2^31; PFMI_ERR_STATE for CONTINUE on static-HMC or NUTS chains (and their CONTINUE on ChEES chains).  Every
+ * error drains this ctx's stream and leaves no chains and no traces behind.
+ * Stage names: "chees" (the step kernel), "chees_closure", "chees_update" (the update's launches and the one that opens the next
+ * trajectory); "chees:<KPAD>:<res|stream>" counts the step launches of one plan. */
+#define PFMI_CHEES_CLAMPED 8         /* status bit: a transition wanted more than max_leapfrog steps */
+#define PFMI_CHEES_KEPT_TRAJ 16      /* status bit: an update kept the trajectory length (no accepted proposal, or a value not finite) */
+#define PFMI_CHEES_RECORD_UPDATE 8   /* flag */
+#define PFMI_CHEES_MAX_LEAPFROG 1024
+int32_t pfmi_chees_enqueue(pfmi_ctx *ctx, int32_t K, const int64_t *points, const double *x0, const uint64_t *seeds, double step_size0,
+                           double traj_length0, int32_t max_leapfrog, int64_t nwarmup, int64_t ntransitions, double target_accept,
+                           int32_t flags);
+int32_t pfmi_chees_pump(pfmi_ctx *ctx, int32_t *finished);
+int32_t pfmi_chees_wait(pfmi_ctx *ctx);
+/* The last ChEES call (finished): *step_size and *traj_length its sampling values; tau_trace, grad_trace, hmean_trace [W]: the tau
+ * transition t used, g and hm of its update; n_leapfrog int32 [W + T]: L_t of the call's transitions; *status: PFMI_CHEES_* and
+ * PFMI_ADAPT_KEPT_STEP.  Any may be NULL.  Waits. */
+int32_t pfmi_chees_get(pfmi_ctx *ctx, double *step_size, double *traj_length, double *tau_trace, double *grad_trace, double *hmean_trace,
+                       int32_t *n_leapfrog, int32_t *status);
+/* PFMI_CHEES_RECORD_UPDATE: x, x' and u' [n][K][d] of the updates after warm-up transitions t0 .. t0 + n - 1.  Any may be NULL. */
+int32_t pfmi_chees_get_update(pfmi_ctx *ctx, int64_t t0, int64_t n, double *x, double *xprop, double *vel);
+/* rounds until the chains went idle = (fresh ? 1 : 0) + sum L_t, and the columns handed to the closure: K per round issued */
+int32_t pfmi_chees_stats(pfmi_ctx *ctx, int64_t *rounds, int64_t *closure_columns);
+/* Host builds of the rule (csrc/adapt.h); no GPU, no ctx.  pfmi_host_chees_leapfrog: L_t (*clamped, may be NULL: n > max_leapfrog).
+ * pfmi_host_chees_update: one update on x, xprop, vel [K][d] and accept [K] with jitter h; last != 0: the update after the last warm-up
+ * transition.  state in/out; grad and hmean are outputs. */
+typedef struct {
+    double step_size, traj_length, s, b, ltb;      /* b starts at 1, s and ltb at 0 */
+    double hbar, leb, mu, delta;                   /* the dual averaging: mu = log(10 step_size0), delta = target_accept */
+    int32_t m, status;
+    double grad, hmean;
+} pfmi_chees_state;
+int32_t pfmi_host_chees_leapfrog(int64_t t, double traj_length, double step_size, int32_t max_leapfrog, int32_t *clamped);
+int32_t pfmi_host_chees_update(int32_t K, int32_t d, const double *x, const double *xprop, const double *vel, const double *accept, double h,
+                               int32_t max_leapfrog, int32_t last, pfmi_chees_state *state);
+
 /* ---- chain diagnostics: rank-normalised split R-hat and ESS ------------------------------------------------------------------- */
 /* The table the reference's worked examples end every chain run with (summarystats(chns), docs/src/examples/turing.md,
  * initializing-hmc.md): mean, sd, mcse, ess_bulk, ess_tail, rhat per coordinate, computed where the draws are.  Definitions: Vehtari,

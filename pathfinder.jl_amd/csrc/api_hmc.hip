@@ -79,7 +79,8 @@ int32_t chain_check_chains(pfmi_ctx *c, const ChainKind &S, const ChainCall &A) 
         PF_CHECK(isfinite(step_size[k]) && step_size[k] > 0.0, PFMI_ERR_ARG, "%s_enqueue: step size of chain %d is not positive and finite", S.name, k);
     }
     PF_CHECK(!cont || (H.have && H.K == K), PFMI_ERR_STATE, "%s_enqueue: PFMI_%s_CONTINUE without %d resident chains", S.name, S.NAME, K);
-    PF_CHECK(!cont || H.kind == S.kind, PFMI_ERR_STATE, "%s_enqueue: PFMI_%s_CONTINUE on the chains of pfmi_%s_enqueue", S.name, S.NAME, S.other);
+    PF_CHECK(!cont || H.kind == S.kind, PFMI_ERR_STATE, "%s_enqueue: PFMI_%s_CONTINUE on the chains of pfmi_%s_enqueue", S.name, S.NAME,
+             H.kind == 0 ? "hmc" : H.kind == 1 ? "nuts" : "chees");
     PF_CHECK(c->scale_staged.empty() || c->scale_staged_K == K, PFMI_ERR_ARG, "%s_enqueue: the scale of pfmi_chain_scale_set is for %d chains, not %d",
              S.name, c->scale_staged_K, K);
     return PFMI_OK;
@@ -159,6 +160,52 @@ int32_t chain_begin(pfmi_ctx *c, const ChainKind &S, const ChainCall &A, int64_t
     return PFMI_OK;
 }
 
+// ---- the one pump of the samplers whose round count is decided on the device (NUTS, ChEES); scheduled as the closure L-BFGS's rounds are
+// (lbc_issue_rounds, api_inputs.hip)
+#define PF_CHAIN_WINDOW 4               // rounds in flight at most
+
+// Issues the rounds a run may have in flight: the gradient closure on all K trial points, then the sampler's launches that consume its answer.
+// At most PF_CHAIN_WINDOW rounds ahead of the last one whose progress word the host has read, never more than the hard cap.  Sets H.finished.
+int32_t chain_issue_rounds(pfmi_ctx *c, const ChainPump &P) {
+    HmcState &H = c->hmc;
+    const TargetDev &Tg = c->target;
+    const int64_t w = __atomic_load_n(c->nt_status, __ATOMIC_ACQUIRE);
+    const int64_t round = w >> 32, active = w & 0xffffffffll;
+    if (round > H.seen) H.seen = round;
+    if (round == H.seen) H.word_low = active;
+    if (round == H.seen && active == 0) H.finished = true;
+    while (!H.finished && H.issued < H.max_rounds && H.issued - H.seen < PF_CHAIN_WINDOW) {
+        pf_kernel_begin(c);
+        Tg.grad_fn(c->hm_X.as<double>(), c->d, H.K, c->hm_out.as<double>(), (void *)c->stream, Tg.grad_user);
+        pf_kernel_end(c, P.closure_stage(H));
+        H.columns += H.K;
+        const int64_t prow = H.issued++;
+        PF_TRY(P.round(c, H.issued, prow));
+    }
+    if (!H.finished && H.issued >= H.max_rounds && H.seen >= H.issued) H.finished = true;      // the hard cap: a stuck flag cannot loop forever
+    return PFMI_OK;
+}
+
+int32_t chain_pump_pass(pfmi_ctx *c, const ChainPump &P, int32_t *finished) {
+    HmcState &H = c->hmc;
+    PF_TRY(chain_issue_rounds(c, P));
+    if (!H.finished) {
+        const hipError_t e = hipStreamQuery(c->stream);
+        PF_CHECK(e == hipSuccess || e == hipErrorNotReady, PFMI_ERR_HIP, "%s_pump: %s", P.name, hipGetErrorString(e));
+    }
+    *finished = H.finished ? 1 : 0;
+    return PFMI_OK;
+}
+
+int32_t chain_drain(pfmi_ctx *c, const ChainPump &P) {   // pump to the end (every pass is bounded by the window, the run by the cap)
+    int32_t fin = c->hmc.finished ? 1 : 0;
+    while (!fin) {
+        PF_TRY(chain_pump_pass(c, P, &fin));
+        if (!fin) for (int i = 0; i < 64; ++i) __builtin_ia32_pause();
+    }
+    return PFMI_OK;
+}
+
 static const ChainKind HMC_KIND = {"hmc", "HMC", "nuts", 0};
 
 int32_t hmc_enqueue(pfmi_ctx *c, int32_t K, const int64_t *points, const double *x0, const uint64_t *seeds, const double *step_size,
@@ -213,7 +260,8 @@ int32_t pfmi_hmc_enqueue(pfmi_ctx *c, int32_t K, const int64_t *points, const do
 int32_t pfmi_hmc_wait(pfmi_ctx *c) {
     PF_CTX(c);
     PF_CHECK(c->hmc.have, PFMI_ERR_STATE, "hmc_wait: no pfmi_hmc_enqueue outstanding");
-    PF_CHECK(c->hmc.kind == 0, PFMI_ERR_STATE, "hmc_wait: the run on this ctx is pfmi_nuts_enqueue's (pfmi_nuts_wait)");
+    PF_CHECK(c->hmc.kind == 0, PFMI_ERR_STATE, "hmc_wait: the run on this ctx is pfmi_%s_enqueue's (pfmi_%s_wait)", c->hmc.kind == 1 ? "nuts" : "chees",
+             c->hmc.kind == 1 ? "nuts" : "chees");
     PF_TRY(pf_stream_sync(c));
     c->hmc.active = false;
     std::vector<int32_t> dead;
@@ -248,7 +296,8 @@ int32_t pfmi_hmc_draws_dev(pfmi_ctx *c, void **dev_ptr, int64_t *count) {
 int32_t pfmi_hmc_get_path(pfmi_ctx *c, int64_t round0, int64_t nrounds, double *X, double *closure_out, double *v) {
     PF_CTX(c);
     const HmcState &H = c->hmc;
-    PF_CHECK(H.have && H.record && H.kind == 0, PFMI_ERR_STATE, "hmc_get_path: the last pfmi_hmc_enqueue did not run with PFMI_HMC_RECORD_PATH");
+    PF_CHECK(H.have && H.record && H.kind != 1, PFMI_ERR_STATE, "hmc_get_path: the last pfmi_hmc_enqueue did not run with PFMI_HMC_RECORD_PATH");
+    PF_CHECK(H.finished, PFMI_ERR_STATE, "hmc_get_path: the ChEES run has rounds to go (pfmi_chees_wait)");
     PF_CHECK(round0 >= 0 && nrounds >= 0 && round0 + nrounds <= H.path_rounds, PFMI_ERR_ARG, "hmc_get_path: rounds [%lld, %lld) outside [0, %lld)",
              (long long)round0, (long long)(round0 + nrounds), (long long)H.path_rounds);
     PF_TRY(chain_path_download(c, round0, nrounds, X, closure_out, v));

@@ -75,6 +75,13 @@ int32_t chain_check_chains(pfmi_ctx *c, const ChainKind &S, const ChainCall &A);
 // the metric kernels); a run with metric windows starts from it, or from ones.  The caller launches init / reopen and issues the rounds.
 int32_t chain_begin(pfmi_ctx *c, const ChainKind &S, const ChainCall &A, int64_t per_transition, const char *need_detail,
                     std::vector<ChainBuf> bufs, int32_t (*drain)(pfmi_ctx *), int64_t *rounds_out);
+// The one pump of the samplers whose round count the device decides (NUTS, ChEES): `closure_stage` names the closure's stage of the run,
+// `round` issues what follows the closure in a round -- the launches that consume its answer, with their own stage names -- as round number
+// `round` (published with the progress word c->nt_status: round << 32 | low, low = 0 once every chain is idle) and path row `prow`.
+struct ChainPump { const char *name; const char *(*closure_stage)(const HmcState &); int32_t (*round)(pfmi_ctx *c, int64_t round, int64_t prow); };
+int32_t chain_issue_rounds(pfmi_ctx *c, const ChainPump &P);            // what may be in flight; sets H.finished
+int32_t chain_pump_pass(pfmi_ctx *c, const ChainPump &P, int32_t *finished);      // one pass: never blocks
+int32_t chain_drain(pfmi_ctx *c, const ChainPump &P);                   // pump to the end
 int32_t chain_refused(pfmi_ctx *c, int32_t rc);           // rc != OK: drain, no run, no chains, no traces; returns rc
 int32_t chain_dead_check(pfmi_ctx *c, const char *name, const std::vector<int32_t> &dead);         // the waits: a dead start point is PFMI_ERR_NUMERIC
 int32_t chain_path_download(pfmi_ctx *c, int64_t round0, int64_t nrounds, double *X, double *closure_out, double *v);     // queued, not waited for

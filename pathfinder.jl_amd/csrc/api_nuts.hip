@@ -1,56 +1,23 @@
 // api_nuts.hip -- NUTS on a fitted metric for gradient closures: the entry points of include/pfmi.h over nuts_kernel.hip.  The chains, the
 // closure buffers and the record buffers are static HMC's (api_hmc.hip: pfmi_hmc_get, pfmi_hmc_draws_dev and pfmi_chain_diagnostics serve a
 // NUTS run unchanged), and so is the enqueue path (chain_begin, api_hmc.hip); what is NUTS's own is here: its buffers, the progress word
-// and the pump.  The rounds are scheduled as the closure L-BFGS's are (lbc_issue_rounds, api_inputs.hip).
+// and its rounds.  The rounds are scheduled by the one pump of the samplers whose round count the device decides (chain_issue_rounds, api_hmc.hip).
 #include "api_internal.h"
 
 #include <math.h>
 #include <vector>
 
-#define PF_NUTS_WINDOW 4                // rounds in flight at most
-
-// Issues the rounds a NUTS run may have in flight: the gradient closure on all K trial points, then the step kernel that consumes its answer.
-// At most PF_NUTS_WINDOW rounds ahead of the last one whose progress word the host has read, never more than the hard cap.  Sets H.finished.
-static int32_t nuts_issue_rounds(pfmi_ctx *c) {
-    HmcState &H = c->hmc;
-    const TargetDev &Tg = c->target;
-    const int64_t w = __atomic_load_n(c->nt_status, __ATOMIC_ACQUIRE);
-    const int64_t round = w >> 32, active = w & 0xffffffffll;
-    if (round > H.seen) H.seen = round;
-    if (round == H.seen && active == 0) H.finished = true;
-    while (!H.finished && H.issued < H.max_rounds && H.issued - H.seen < PF_NUTS_WINDOW) {
-        pf_kernel_begin(c);
-        Tg.grad_fn(c->hm_X.as<double>(), c->d, H.K, c->hm_out.as<double>(), (void *)c->stream, Tg.grad_user);
-        pf_kernel_end(c, H.scaled ? "nuts_metric_closure" : H.adapting ? "nuts_adapt_closure" : "nuts_closure");
-        H.columns += H.K;
-        const int64_t prow = H.issued++;
-        pf_kernel_begin(c);
-        PF_TRY((H.scaled ? pf_launch_nuts_metric_step : pf_launch_nuts_step)(c, H.issued, prow, false, c->stream));
-        pf_kernel_end(c, H.scaled ? "nuts_metric" : H.adapting ? "nuts_adapt" : "nuts");
-    }
-    if (!H.finished && H.issued >= H.max_rounds && H.seen >= H.issued) H.finished = true;      // the hard cap: a stuck flag cannot loop forever
+// a NUTS round: the closure's stage name, and the step launch behind the closure
+static const char *nuts_closure_stage(const HmcState &H) { return H.scaled ? "nuts_metric_closure" : H.adapting ? "nuts_adapt_closure" : "nuts_closure"; }
+static int32_t nuts_round(pfmi_ctx *c, int64_t round, int64_t prow) {
+    const HmcState &H = c->hmc;
+    pf_kernel_begin(c);
+    PF_TRY((H.scaled ? pf_launch_nuts_metric_step : pf_launch_nuts_step)(c, round, prow, false, c->stream));
+    pf_kernel_end(c, H.scaled ? "nuts_metric" : H.adapting ? "nuts_adapt" : "nuts");
     return PFMI_OK;
 }
-
-static int32_t nuts_pump_pass(pfmi_ctx *c, int32_t *finished) {
-    HmcState &H = c->hmc;
-    PF_TRY(nuts_issue_rounds(c));
-    if (!H.finished) {
-        const hipError_t e = hipStreamQuery(c->stream);
-        PF_CHECK(e == hipSuccess || e == hipErrorNotReady, PFMI_ERR_HIP, "nuts_pump: %s", hipGetErrorString(e));
-    }
-    *finished = H.finished ? 1 : 0;
-    return PFMI_OK;
-}
-
-static int32_t nuts_drain(pfmi_ctx *c) {                  // pump to the end (every pass is bounded by the window, the run by the cap)
-    int32_t fin = c->hmc.finished ? 1 : 0;
-    while (!fin) {
-        PF_TRY(nuts_pump_pass(c, &fin));
-        if (!fin) for (int i = 0; i < 64; ++i) __builtin_ia32_pause();
-    }
-    return PFMI_OK;
-}
+static const ChainPump NUTS_PUMP = {"nuts", nuts_closure_stage, nuts_round};
+static int32_t nuts_drain(pfmi_ctx *c) { return chain_drain(c, NUTS_PUMP); }
 
 static const ChainKind NUTS_KIND = {"nuts", "NUTS", "hmc", 1};
 
@@ -92,7 +59,7 @@ int32_t nuts_enqueue(pfmi_ctx *c, int32_t K, const int64_t *points, const double
         PF_TRY((H.scaled ? pf_launch_nuts_metric_step : pf_launch_nuts_step)(c, 0, 0, true, c->stream));
         pf_kernel_end(c, H.scaled ? "nuts_metric" : "nuts");
     }
-    return nuts_issue_rounds(c);
+    return chain_issue_rounds(c, NUTS_PUMP);
 }
 
 extern "C" {
@@ -107,7 +74,7 @@ int32_t pfmi_nuts_pump(pfmi_ctx *c, int32_t *finished) {
     PF_CHECK(c != nullptr && finished != nullptr, PFMI_ERR_ARG, "nuts_pump: null argument");
     PF_CHECK(c->hmc.have && c->hmc.kind == 1, PFMI_ERR_STATE, "nuts_pump: no pfmi_nuts_enqueue outstanding");
     PF_HIP(hipSetDevice(c->device));
-    return chain_refused(c, nuts_pump_pass(c, finished));  // a failed pass ends the run: what is in flight is drained
+    return chain_refused(c, chain_pump_pass(c, NUTS_PUMP, finished));  // a failed pass ends the run: what is in flight is drained
 }
 
 int32_t pfmi_nuts_wait(pfmi_ctx *c) {

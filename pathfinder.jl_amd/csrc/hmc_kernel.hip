@@ -74,11 +74,17 @@ __global__ __launch_bounds__(HM_NT) void pf_hmc_init_kernel(HmArgs A) {
 // MODE HM_METRIC (pf_hmc_metric_kernel, hmc_metric_kernel.hip): the chain carries a per-coordinate scale c (HmMetric, hmc_rows.h): a kick is
 // v += e c . (R g), a drift x += e L (c . v) -- wg, wt and v themselves stay what they are without a scale, so a new scale needs no
 // conversion of the state -- and a warm-up transition inside a metric window ends with hm_metric_end.  Plain and adaptive runs share it.
-enum { HM_PLAIN = 0, HM_WARM = 1, HM_METRIC = 2 };
+//
+// MODE HM_CHEES (pf_chees_step_kernel, chees_kernel.hip): the step size and the trajectory length are the run's shared ones (A.C, adapt.h:
+// PfChees), the leapfrog count of transition t is pf_chees_leapfrog's -- the same in every chain, so the chains end their trajectories in
+// the same launch.  A warm-up transition ends with the inputs of the cross-chain update (the state before it, the trial point, a and
+// u' = L v') and does NOT open the next trajectory: the update's launches follow, then a launch with A.reopen that opens it.  A launch
+// that finds its chain idle returns at once.  Workgroup 0 alone writes L_t, the status bits and the progress word.
+enum { HM_PLAIN = 0, HM_WARM = 1, HM_METRIC = 2, HM_CHEES = 3 };
 
 template <int KPAD, bool RES, int MODE, class Args>
 __device__ __forceinline__ void hm_step_body(const Args &A) {
-    constexpr bool ADAPT = MODE != HM_PLAIN, METRIC = MODE == HM_METRIC;
+    constexpr bool ADAPT = MODE != HM_PLAIN, METRIC = MODE == HM_METRIC, CHEES = MODE == HM_CHEES;
     constexpr int NVM = KPAD + 4;                        // KPAD sums + one rider, padded to the multiple of 4 pf_block_sum_mv takes
     __shared__ HmLds<KPAD, NVM> L;
     const int k = blockIdx.x, tid = threadIdx.x, d = A.d, K = A.K;
@@ -90,6 +96,28 @@ __device__ __forceinline__ void hm_step_body(const Args &A) {
     const double *sqa = A.sqa + (size_t)p * d;
     double *X = A.X + kd, *x = A.x + kd, *wg = A.wg + kd, *wt = A.wt + kd, *v = A.v + kd;
     double eps = A.eps[k];
+    int nleap = A.nleap;
+    [[maybe_unused]] bool clamped = false, ended = false, warm_end = false;
+    [[maybe_unused]] size_t uo = kd;                     // CHEES: the chain's place among the vectors of the update this transition may end with
+    if constexpr (CHEES) {
+        // (the shared state is read beside the chain's own, before the branch: one load latency, not two in a row)
+        const double ceps = A.C->eps, ctau = A.C->tau;
+        const int32_t cLmax = A.C->Lmax;
+        if (A.reopen ? (S.i != HM_OPEN || S.t >= A.t_end) : S.i == HM_OPEN) return;      // (the same in every thread and every chain)
+        if (A.nrec > 1) uo += (size_t)S.t * A.vec;
+        eps = ceps;
+        nleap = pf_chees_leapfrog(S.t, ctau, ceps, cLmax, &clamped);
+        if (k == 0 && tid == 0 && !A.reopen) {           // the chains run in lockstep: chain 0 speaks for the run
+            // The progress word, by its single writer.  What this launch leaves is known before its work (it ends a trajectory iff
+            // i has reached L_t), so the store to the page-locked word is issued first and its latency runs beside the passes.  Low
+            // word: 0 idle, else 1, + 2 while warm-up transitions (and so cross-chain updates) are still to come.  Relaxed: the host
+            // schedules by the word alone and reads results only behind a stream synchronisation.
+            const bool ends = S.i != HM_START && S.i >= nleap;
+            const int64_t tn = S.t + (ends ? 1 : 0);
+            const bool running = !(ends && tn >= A.t_end);
+            __hip_atomic_store(A.h_status, (int64_t)((A.pround << 32) | (running ? (tn < A.t0 ? 3 : 1) : 0)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
     const uint64_t seed = A.seeds[k];
     const HmFactor F = {gVh, T, Vc, sqa};
     bool staged = false;                                 // an R pass came before the L pass (hmc_rows.h)
@@ -114,7 +142,7 @@ __device__ __forceinline__ void hm_step_body(const Args &A) {
             S.lp = bad ? -DBL_MAX : lpt;
             S.dead = bad ? 1 : 0;
             open = true;
-        } else if (S.i < A.nleap) {
+        } else if (S.i < nleap) {
             for (int i = tid; i < d; i += HM_NT) v[i] = fma(eps, hm_scaled<METRIC>(sc, i, wt[i]), v[i]);
             if (nbad > 0.0 || !isfinite(lpt)) S.bad = 1;
             ++S.i;
@@ -122,7 +150,11 @@ __device__ __forceinline__ void hm_step_body(const Args &A) {
         } else {
             // ---- the trajectory's end: last half kick, H1, the decision, row t
             double e = 0.0;
-            for (int i = tid; i < d; i += HM_NT) { const double vi = fma(0.5 * eps, hm_scaled<METRIC>(sc, i, wt[i]), v[i]); e = fma(vi, vi, e); }
+            for (int i = tid; i < d; i += HM_NT) {
+                const double vi = fma(0.5 * eps, hm_scaled<METRIC>(sc, i, wt[i]), v[i]);
+                e = fma(vi, vi, e);
+                if constexpr (CHEES) v[i] = vi;          // v' of the update (row i is this thread's own in every pass)
+            }
             e = pf_block_sum1_pp<NVM>(e, L.red, flip);
             const double H1 = -lpt + 0.5 * e, dH = H1 - S.H0;
             const bool div = S.bad || nbad > 0.0 || !isfinite(lpt) || !isfinite(H1) || dH > 1000.0;
@@ -134,6 +166,7 @@ __device__ __forceinline__ void hm_step_body(const Args &A) {
             double *dr = A.draws + ((size_t)k * A.T + (warm ? 0 : row)) * d;
             for (int i = tid; i < d; i += HM_NT) {
                 double xi = x[i];
+                if constexpr (CHEES) if (warm) { A.ux[uo + i] = xi; A.uxp[uo + i] = X[i]; }
                 if (acc) { xi = X[i]; x[i] = xi; wg[i] = wt[i]; }
                 if (!warm) dr[i] = xi;
             }
@@ -143,21 +176,33 @@ __device__ __forceinline__ void hm_step_body(const Args &A) {
                 A.rlp[r] = S.lp; A.racc[r] = a; A.rde[r] = isfinite(dH) ? dH : DBL_MAX; A.rdiv[r] = div ? 1 : 0;
             }
             ++S.t; S.bad = 0;
-            if constexpr (ADAPT) {
+            if constexpr (CHEES) {
+                ended = true; warm_end = warm;
+                if (warm) {
+                    if (tid == 0) {
+                        PfWarmRow *tr = reinterpret_cast<PfWarmRow *>(A.ad + K) + (size_t)k * A.t0 + (S.t - 1);
+                        tr->eps = eps; tr->acc = a; tr->div = div ? 1 : 0; tr->nleap = nleap;
+                        A.ua[k] = a;
+                    }
+                    // u' = L v': the drift's pass with a base of 0 and e = 1
+                    hm_apply_L<KPAD, RES, HM_NT, NVM>(F, L, A.uv + uo, 1.0, 0.0, staged, d, flip, [&](int i) -> const double & { return v[i]; },
+                                                      [&](int) { return 0.0; }, [&](double) {});
+                }
+            } else if constexpr (ADAPT) {
                 if (warm) {
                     __shared__ double sNext;
                     bool wnd = false;                    // METRIC: the transition ended a metric window
                     if constexpr (METRIC)
                         wnd = hm_metric_end<KPAD, RES, NVM>(F, L, A.M, A.ad, k, d, S.t - 1, A.x0 + kd, flip, [&](int i) { return x[i]; });
                     if (tid == 0) {
-                        sNext = hm_warm_end(A.ad, A.eps, K, k, S.t, A.t0, eps, a, div ? 1 : 0, A.nleap);
+                        sNext = hm_warm_end(A.ad, A.eps, K, k, S.t, A.t0, eps, a, div ? 1 : 0, nleap);
                         if constexpr (METRIC) if (wnd) pf_adapt_restart(A.ad[k], sNext);
                     }
                     __syncthreads();
                     eps = sNext;
                 }
             }
-            if (S.t < A.t_end) open = true; else S.i = HM_OPEN;
+            if (S.t < A.t_end && !(CHEES && warm)) open = true; else S.i = HM_OPEN;
         }
     }
     double vv0 = 0.0;
@@ -188,6 +233,16 @@ __device__ __forceinline__ void hm_step_body(const Args &A) {
     }
     __syncthreads();                                     // every thread has read S before thread 0 writes
     if (tid == 0) A.st[k] = S;
+    if constexpr (CHEES) {
+        if (k == 0 && tid == 0 && !A.reopen) {
+            if (ended) {
+                A.nl[S.t - 1 - A.tcall] = nleap;
+                if (clamped) A.C->status |= PF_CHEES_CLAMPED;
+                if (warm_end) { A.C->pending = 1; A.C->t_upd = S.t - 1; }
+            }
+            if (S.i == HM_OPEN && S.t >= A.t_end) A.C->fin_round = A.pround;
+        }
+    }
 }
 
 #ifndef PF_CHAIN_METRIC_TU             // (hmc_metric_kernel.hip takes the body and hm_args from this file and defines its own kernels)

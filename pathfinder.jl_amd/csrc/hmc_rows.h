@@ -14,6 +14,25 @@
 // the staged factor rows of one chain fit in LDS beside the reduction buffers
 inline bool pf_hmc_resident(int d, int kpad) { return (size_t)d * kpad * sizeof(double) <= (size_t)HM_LDS_RES; }
 
+// c->hm_chees of a ChEES call (adapt.h: PfChees), stated ONCE, in doubles from the buffer's start: the shared state (PF_CHEES_HEAD bytes),
+// the traces tau, g, hm [W] each, the update's inputs a [K] and its sums p, q, r [K] each, xbar and xbar' [d] each, the vectors x, x' and u'
+// of an update [nrec][K][d] each (nrec = W under PFMI_CHEES_RECORD_UPDATE, else 1 when W > 0), then L_t int32 [W + T]
+#define PF_CHEES_HEAD 256
+static_assert(sizeof(PfChees) <= PF_CHEES_HEAD, "the shared state fits its slot");
+struct CheesLayout {
+    size_t trace, ua, pqr, xbar, upd, nl, bytes, vec;
+    CheesLayout(int K, int d, int64_t W, int64_t T, int64_t nrec) {
+        vec = (size_t)K * d;
+        trace = PF_CHEES_HEAD / sizeof(double);
+        ua = trace + 3 * (size_t)W;
+        pqr = ua + (size_t)K;
+        xbar = pqr + 3 * (size_t)K;
+        upd = xbar + 2 * (size_t)d;
+        nl = upd + 3 * vec * (size_t)nrec;
+        bytes = sizeof(double) * nl + sizeof(int32_t) * (size_t)(W + T);
+    }
+};
+
 #ifdef __HIPCC__
 // One step launch of a kernel family (Family::kernel<KPAD, RES, ADAPT>() is its step or warm kernel; Args carries d and K): one workgroup
 // per chain, the factor rows in dynamic LDS when they fit, counted under the plan name "<plan>[_adapt]:<KPAD>:<res|stream>".  (A family

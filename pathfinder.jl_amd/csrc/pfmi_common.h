@@ -115,7 +115,7 @@ struct HmcState {
     int64_t t0 = 0, T = 0;        // the last call made transitions t0 .. t0 + T - 1
     int64_t rounds = 0, columns = 0, path_rounds = 0;
     // kind 1 (pfmi_nuts_enqueue, nuts_kernel.hip): the round count is not known up front, the rounds are pumped as the closure L-BFGS's are
-    int kind = 0;                 // 0: static HMC, 1: NUTS -- PFMI_*_CONTINUE goes on only from chains of its own kind
+    int kind = 0;                 // 0: static HMC, 1: NUTS, 2: ChEES-HMC -- PFMI_*_CONTINUE goes on only from chains of its own kind
     int max_depth = 0, md_alloc = 0;                  // the stop rule of the last call; the depth the chains' checkpoints were made for
     int64_t issued = 0, seen = 0, max_rounds = 0;     // rounds launched / last round whose progress word the host has read / hard cap
     bool finished = true;         // every chain has made its transitions (or the cap is reached and seen)
@@ -129,6 +129,12 @@ struct HmcState {
     bool rec_u = false;           // ... with PFMI_ADAPT_RECORD_WHITENED
     int nwin = 0;                 // its metric windows (adapt.h: pf_adapt_windows); 0: W < 20
     int64_t win_init = 0, win_ends[32] = {};
+    // kind 2 (pfmi_chees_enqueue, chees_kernel.hip): static HMC's transitions with a shared step size and a trajectory length learned across
+    // the chains; the leapfrog counts are decided on the device, so the rounds are pumped as NUTS's are
+    int64_t ch_W = 0, ch_T = 0, ch_nrec = 0;          // the last ChEES call's warm-up and sampling transitions; updates whose vectors it kept
+    int ch_Lmax = 0;
+    bool ch_rec = false;          // PFMI_CHEES_RECORD_UPDATE of that call
+    int64_t word_low = 0;         // the low half of the last progress word read (NUTS: chains still running; ChEES: 1 running, + 2 warming up)
 };
 
 struct pfmi_ctx {
@@ -295,6 +301,7 @@ struct pfmi_ctx {
     DevBuf hm_pX, hm_pout, hm_pv;                       // PFMI_HMC_RECORD_PATH: every round's X, closure output and v
     DevBuf hm_adapt;                                    // adaptive runs: PfAdapt [K], PfWarmRow [K][W], then [K] final step sizes (adapt.h, api_adapt.hip)
     DevBuf hm_scale;                                    // [K][d] the chains' resident scale (hmc.scaled; pfmi_chain_scale_set, the metric windows)
+    DevBuf hm_chees;                                    // ChEES: shared state, traces, the update's inputs and sums, L_t (CheesLayout, hmc_rows.h)
     DevBuf hm_metric;                                   // runs with metric windows: window table, Welford state, scale trace, whitened rows (pf_metric_layout, api_adapt.hip)
     std::vector<double> scale_staged;                   // pfmi_chain_scale_set: [scale_staged_K][d] for the next enqueue; empty: none
     int32_t scale_staged_K = 0;
@@ -433,6 +440,11 @@ int32_t pf_launch_nuts_step(pfmi_ctx *c, int64_t round, int64_t prow, bool reope
 int32_t pf_nuts_chain_flags(pfmi_ctx *c, std::vector<int32_t> &dead, int64_t *last_round);
 // hmc_metric_kernel.hip, nuts_metric_kernel.hip: the step launch of chains that carry a scale (c->hmc.scaled), plain or adaptive
 int32_t pf_launch_hmc_metric_step(pfmi_ctx *c, int64_t round, hipStream_t s);
+// chees_kernel.hip: round: the number the launch publishes with its progress word; prow: its row of the recorded path; reopen: the launch
+// that opens the next trajectory without reading the closure (after an update, or first in a CONTINUE).  _update: the three launches of
+// the cross-chain update, which do nothing unless the step launch before them ended a warm-up transition.
+int32_t pf_launch_chees_step(pfmi_ctx *c, int64_t round, int64_t prow, bool reopen, hipStream_t s);
+int32_t pf_launch_chees_update(pfmi_ctx *c, hipStream_t s);
 int32_t pf_launch_nuts_metric_step(pfmi_ctx *c, int64_t round, int64_t prow, bool reopen, hipStream_t s);
 // chain_diag_kernels.hip: bytes of c->cd_ws for K chains of T draws of d coordinates (+ the logp series), and the seven outputs of the
 // device records d_rec [K][T][d] (d_lp [K][T] or NULL) into *d_out [7][d (+ 1)] inside that workspace; enqueued, not waited for

@@ -1540,6 +1540,47 @@ function nuts_adapt_metric(b::Batch, points::AbstractVector{<:Integer}, x0::Abst
             warmup = merge(_adapt_get(b, K, W), _adapt_metric_get(b, K, W)))
 end
 
+# ---- ChEES-HMC (Hoffman, Radul & Sountsov 2021; include/pfmi.h: pfmi_chees_enqueue): static HMC's transitions with ONE step size and ONE
+# jittered leapfrog count for all chains; the warm-up learns the step size and the trajectory length across the chains, on the device.
+"""
+    chees(b::Batch, points, x0, seeds, step_size0; traj_length0 = 0.0, max_leapfrog = 64, nwarmup = 200, ntransitions,
+          target_accept = 0.651)
+
+`ntransitions` sampling transitions of `K` chains of ChEES-HMC after `nwarmup` warm-up transitions.  Returns `hmc`'s rows and
+`step_size`, `trajectory_length` (the sampling values), `n_leapfrog` (`ntransitions`: the leapfrog steps of every sampling transition,
+the same in all chains), `status`, and for `nwarmup > 0` `warmup`: what `hmc_adapt` gives plus `tau_trace`, `grad_trace`, `hmean_trace`.
+"""
+function chees(b::Batch, points::AbstractVector{<:Integer}, x0::AbstractMatrix{Float64}, seeds::AbstractVector{UInt64},
+               step_size0::Real; traj_length0::Real = 0.0, max_leapfrog::Integer = 64, nwarmup::Integer = 200, ntransitions::Integer,
+               target_accept::Real = 0.651)
+    _live(b.eng, b.gen)
+    K = length(points); d = b.dim; T = Int(ntransitions); W = Int(nwarmup)
+    (length(seeds) == K && size(x0) == (d, K)) || throw(ArgumentError("chees: K values per argument"))
+    pts = Vector{Int64}(points); X0 = Matrix{Float64}(x0); sd = Vector{UInt64}(seeds)
+    check(ccall((:pfmi_chees_enqueue, libpfmi), Int32,
+                (Ptr{Cvoid}, Int32, Ptr{Int64}, Ptr{Float64}, Ptr{UInt64}, Float64, Float64, Int32, Int64, Int64, Float64, Int32),
+                b.eng.ptr, K, pts, X0, sd, Float64(step_size0), Float64(traj_length0), max_leapfrog, W, T, Float64(target_accept), Int32(0)))
+    check(ccall((:pfmi_chees_wait, libpfmi), Int32, (Ptr{Cvoid},), b.eng.ptr))
+    draws = Array{Float64}(undef, d, T, K)
+    lp = Matrix{Float64}(undef, T, K); acc = similar(lp); de = similar(lp); dv = Matrix{Int32}(undef, T, K)
+    check(ccall((:pfmi_hmc_get, libpfmi), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+                b.eng.ptr, draws, lp, acc, de, dv))
+    ϵ = Ref{Float64}(0.0); τ = Ref{Float64}(0.0); st = Ref{Int32}(0)
+    tt = Vector{Float64}(undef, W); gt = similar(tt); ht = similar(tt); nl = Vector{Int32}(undef, W + T)
+    check(ccall((:pfmi_chees_get, libpfmi), Int32,
+                (Ptr{Cvoid}, Ref{Float64}, Ref{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ref{Int32}),
+                b.eng.ptr, ϵ, τ, tt, gt, ht, nl, st))
+    warm = W > 0 ? merge(_adapt_get(b, K, W), (tau_trace = tt, grad_trace = gt, hmean_trace = ht)) : nothing
+    return (draws = draws, logp = lp, accept_prob = acc, energy_error = de, divergent = dv, step_size = ϵ[], trajectory_length = τ[],
+            n_leapfrog = nl[W+1:end], status = st[], warmup = warm)
+end
+"rounds until the chains went idle and closure columns of the last `chees` call (pfmi_chees_stats)"
+function chees_stats(b::Batch)
+    r = Ref{Int64}(0); n = Ref{Int64}(0)
+    check(ccall((:pfmi_chees_stats, libpfmi), Int32, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), b.eng.ptr, r, n))
+    return (rounds = r[], closure_columns = n[])
+end
+
 # ---- chain diagnostics on the device: what summarystats(chns) reports in docs/src/examples/turing.md and initializing-hmc.md
 function _chain_diagnostics(eng::Engine, source::Integer, draws, d::Integer, T::Integer, K::Integer, flags::Integer, len::Integer)
     out = [Vector{Float64}(undef, len) for _ in 1:7]

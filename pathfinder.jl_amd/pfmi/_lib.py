@@ -58,6 +58,8 @@ SYMBOLS = [
     "pfmi_hmc_adapt_enqueue", "pfmi_nuts_adapt_enqueue", "pfmi_adapt_get", "pfmi_host_dual_averaging",
     "pfmi_chain_scale_set", "pfmi_hmc_adapt_metric_enqueue", "pfmi_nuts_adapt_metric_enqueue", "pfmi_adapt_metric_get", "pfmi_adapt_windows",
     "pfmi_host_metric_update",
+    "pfmi_chees_enqueue", "pfmi_chees_pump", "pfmi_chees_wait", "pfmi_chees_get", "pfmi_chees_get_update", "pfmi_chees_stats",
+    "pfmi_host_chees_leapfrog", "pfmi_host_chees_update",
 ]
 
 # declared argument types (entry points not listed here take what the caller wraps by hand)
@@ -98,7 +100,22 @@ ARGTYPES = {
     "pfmi_adapt_metric_get": [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64), _dp, _dp],
     "pfmi_adapt_windows": [C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_int32)],
     "pfmi_host_metric_update": [C.c_int64, C.c_int32, _dp, _dp, _dp, C.POINTER(C.c_int32)],
+    "pfmi_chees_enqueue": [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), _dp, C.POINTER(C.c_uint64), C.c_double, C.c_double, C.c_int32, C.c_int64,
+                           C.c_int64, C.c_double, C.c_int32],
+    "pfmi_chees_pump": [C.c_void_p, C.POINTER(C.c_int32)],
+    "pfmi_chees_wait": [C.c_void_p],
+    "pfmi_chees_get": [C.c_void_p, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
+    "pfmi_chees_get_update": [C.c_void_p, C.c_int64, C.c_int64, _dp, _dp, _dp],
+    "pfmi_chees_stats": [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
+    "pfmi_host_chees_leapfrog": [C.c_int64, C.c_double, C.c_double, C.c_int32, C.POINTER(C.c_int32)],
+    "pfmi_host_chees_update": [C.c_int32, C.c_int32, _dp, _dp, _dp, _dp, C.c_double, C.c_int32, C.c_int32, C.c_void_p],
 }
+
+
+class CheesState(C.Structure):
+    """pfmi_chees_state (include/pfmi.h)"""
+    _fields_ = [(k, C.c_double) for k in ("step_size", "traj_length", "s", "b", "ltb", "hbar", "leb", "mu", "delta")] + \
+               [("m", C.c_int32), ("status", C.c_int32), ("grad", C.c_double), ("hmean", C.c_double)]
 
 
 def build(force=False):

@@ -116,6 +116,7 @@ class Engine:
         self._hmc = None                          # (K, T) of the last hmc_enqueue that succeeded
         self._adapt = None                        # (K, W) of the adaptive run whose traces are resident (adapt_get)
         self._metric = None                       # (K, W, whitened rows kept) when that run had metric windows (adapt_metric_get)
+        self._chees = None                        # (K, W, T, updates kept) of the last chees_enqueue that succeeded, while it is the latest run
         self.hmc_runs = 0                         # hmc_enqueue calls that succeeded (HMCResult.summary: is a result still the resident run?)
 
     def close(self):
@@ -520,6 +521,7 @@ class Engine:
             self._raise_target_error()
         check(rc)
         self._hmc = (K, int(ntransitions))
+        self._chees = None
         if nwarmup is not None:
             self._adapt = (K, int(nwarmup))
             self._metric = (K, int(nwarmup), bool(flags & self.ADAPT_RECORD_WHITENED)) if metric else None
@@ -711,6 +713,84 @@ class Engine:
         """PFMI_NUTS_RECORD_PATH: (X (d, K, n), logp (K, n), grad (d, K, n), v (d, K, n), events (n, K) of NUTS_EVENT) of rounds
         round0 .. round0 + n - 1; v is the synchronised momentum of the leaf the round finished"""
         return self._chain_path("nuts_path", self.nuts_stats, self.L.pfmi_nuts_get_path, round0, nrounds, True)
+
+    # ---- ChEES-HMC (include/pfmi.h: pfmi_chees_enqueue) ----------------------------------------------------------------------------
+    CHEES_CLAMPED, CHEES_KEPT_TRAJ, CHEES_RECORD_UPDATE, CHEES_MAX_LEAPFROG = 8, 16, 8, 1024
+
+    def chees_enqueue(self, points, x0, seeds, step_size0, traj_length0, max_leapfrog, nwarmup, ntransitions, target_accept=0.651, cont=False,
+                      record_path=False, record_update=False):
+        """K chains of ChEES-HMC: static HMC's transitions with ONE step size and ONE jittered leapfrog count for all chains; the `nwarmup`
+        warm-up transitions learn the step size (towards target_accept) and the trajectory length (from the chains' spread) on the device.
+        traj_length0 = 0 starts from step_size0.  cont=True (nwarmup = 0 only) goes on from resident ChEES chains.  Issues the first window
+        of rounds and returns; chees_pump / chees_wait issue the rest.  hmc_get, adapt_get, hmc_path and chain_diagnostics serve the run."""
+        points = np.ascontiguousarray(points, dtype=np.int64)
+        K = len(points)
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
+        assert seeds.shape == (K,)
+        x0p = None
+        if x0 is not None:
+            x0 = np.asfortranarray(x0, dtype=np.float64)
+            assert x0.shape == (self.d, K), (x0.shape, self.d, K)
+            x0p = _d(x0)
+        flags = (self.HMC_CONTINUE if cont else 0) | (self.HMC_RECORD_PATH if record_path else 0) | (self.CHEES_RECORD_UPDATE if record_update else 0)
+        rc = self.L.pfmi_chees_enqueue(self.ctx, K, points.ctypes.data_as(_i64p), x0p, seeds.ctypes.data_as(C.POINTER(C.c_uint64)), float(step_size0),
+                                       float(traj_length0), int(max_leapfrog), int(nwarmup), int(ntransitions), float(target_accept), flags)
+        if getattr(self.target, "pending_error", None) is not None:
+            self.sync()
+            self._raise_target_error()
+        check(rc)
+        self._hmc = (K, int(ntransitions))
+        self._chees = (K, int(nwarmup), int(ntransitions), bool(record_update) and nwarmup > 0)
+        if nwarmup > 0:
+            self._adapt, self._metric = (K, int(nwarmup)), None
+        elif not cont:
+            self._adapt = self._metric = None
+        self.hmc_runs += 1
+
+    def chees_pump(self):
+        """one scheduling pass; True once every chain has made its transitions"""
+        fin = C.c_int32(0)
+        check(self.L.pfmi_chees_pump(self.ctx, C.byref(fin)))
+        return bool(fin.value)
+
+    def chees_wait(self):
+        check(self.L.pfmi_chees_wait(self.ctx))
+        self._raise_target_error()
+
+    def chees_get(self):
+        """the last chees_enqueue: dict of step_size, traj_length (the sampling values), tau_trace, grad_trace, hmean_trace (W,), n_leapfrog
+        int32 (W + T,) and status (CHEES_CLAMPED, CHEES_KEPT_TRAJ, ADAPT_KEPT_STEP)"""
+        if self._chees is None:
+            check(self.L.pfmi_chees_get(self.ctx, None, None, None, None, None, None, None))     # (PFMI_ERR_STATE: the library's message)
+            raise _lib.PfmiError("chees_get: no ChEES run was enqueued through this engine")
+        K, W, T, _ = self._chees
+        eps, tau, st = C.c_double(), C.c_double(), C.c_int32()
+        out = {"tau_trace": np.empty(W), "grad_trace": np.empty(W), "hmean_trace": np.empty(W), "n_leapfrog": np.empty(W + T, dtype=np.int32)}
+        check(self.L.pfmi_chees_get(self.ctx, C.byref(eps), C.byref(tau), _d(out["tau_trace"]), _d(out["grad_trace"]), _d(out["hmean_trace"]),
+                                    out["n_leapfrog"].ctypes.data_as(C.POINTER(C.c_int32)), C.byref(st)))
+        out.update(step_size=eps.value, traj_length=tau.value, status=st.value)
+        return out
+
+    def chees_get_update(self, t0=0, n=None):
+        """record_update=True: (x, xprop, vel), each (n, K, d), of the updates after warm-up transitions t0 .. t0 + n - 1"""
+        if self._chees is None or not self._chees[3]:
+            check(self.L.pfmi_chees_get_update(self.ctx, 0, 0, None, None, None))
+            raise _lib.PfmiError("chees_get_update: the last chees_enqueue did not keep its updates")
+        K, W, _, _ = self._chees
+        n = W - t0 if n is None else n
+        out = [np.empty((n, K, self.d)) for _ in range(3)]
+        check(self.L.pfmi_chees_get_update(self.ctx, int(t0), int(n), *[_d(o) for o in out]))
+        return tuple(out)
+
+    def chees_path(self, round0=0, nrounds=None):
+        """record_path=True: hmc_path's (X, logp, grad, v) of a ChEES run, rounds round0 .. round0 + n - 1 (n at most chees_stats' rounds)"""
+        return self._chain_path("chees_path", self.chees_stats, self.L.pfmi_hmc_get_path, round0, nrounds, False)
+
+    def chees_stats(self):
+        """(rounds until the chains went idle = (fresh ? 1 : 0) + sum of n_leapfrog, closure columns: K per round issued)"""
+        r, n = C.c_int64(), C.c_int64()
+        check(self.L.pfmi_chees_stats(self.ctx, C.byref(r), C.byref(n)))
+        return r.value, n.value
 
     # ---- pool / PSIS / resample -------------------------------------------------------------------------
     def pool_build(self, N_r, points, seeds):

@@ -183,9 +183,9 @@ class NUTSResult(HMCResult):
         return "\n".join(lines)
 
 
-def _run(name, result, ndraws, nchains, nwarmup, step_size, param, rng, target_accept, window, adapt, adapt_metric=False):
-    """the driver behind hmc() and nuts(): `name` is the sampler ("hmc" / "nuts"), `param` its nleapfrog / max_depth"""
-    is_nuts = name == "nuts"
+def _chains(name, result, nchains, rng, check_param=None):
+    """what every sampler here starts from: (engine, starts x0 (d, nchains), fit points, seeds) of `result`; check_param: the sampler's
+    own argument check, made where it has always been made (after the engine's and the target's, before nchains')"""
     eng, starts, pts, token = _starts_and_points(result)
     if eng is None:
         raise ValueError(f"pfmi.{name} needs a result whose fits are still on an engine")
@@ -193,16 +193,24 @@ def _run(name, result, ndraws, nchains, nwarmup, step_size, param, rng, target_a
     if not getattr(eng.target, "has_device_gradient", False):
         raise ValueError(f"pfmi.{name} needs a device closure target with a gradient (built-in targets, host closures and device closures "
                          "without a gradient are not supported)")
-    if is_nuts and not 1 <= int(param) <= 10:
-        raise ValueError("max_depth must be in 1 .. 10")
+    if check_param is not None:
+        check_param()
     nchains = starts.shape[1] if nchains is None else int(nchains)
     if not 1 <= nchains <= starts.shape[1]:
         raise ValueError(f"nchains must be in 1 .. {starts.shape[1]} (the result's draws)")
-    d = starts.shape[0]
-    x0 = np.asfortranarray(starts[:, :nchains])
-    pts = pts[:nchains]
     rng = rng if rng is not None else HostRNG(0)
-    seeds = rng.rand_u64(nchains)
+    return eng, np.asfortranarray(starts[:, :nchains]), pts[:nchains], rng.rand_u64(nchains)
+
+
+def _run(name, result, ndraws, nchains, nwarmup, step_size, param, rng, target_accept, window, adapt, adapt_metric=False):
+    """the driver behind hmc() and nuts(): `name` is the sampler ("hmc" / "nuts"), `param` its nleapfrog / max_depth"""
+    is_nuts = name == "nuts"
+    def check_param():
+        if is_nuts and not 1 <= int(param) <= 10:
+            raise ValueError("max_depth must be in 1 .. 10")
+
+    eng, x0, pts, seeds = _chains(name, result, nchains, rng, check_param)
+    d, nchains = x0.shape
     auto = isinstance(step_size, str)
     if auto and step_size != "auto":
         raise ValueError('step_size must be a number, an array of nchains numbers or "auto"')
@@ -271,6 +279,51 @@ def nuts(result, ndraws, *, nchains=None, nwarmup=0, step_size="auto", max_depth
     adapt="device": as for `hmc`, one enqueue whose warm-up adapts on the device after every transition (pfmi_nuts_adapt_enqueue);
     adapt_metric=True: with the metric windows of `hmc` (pfmi_nuts_adapt_metric_enqueue)."""
     return _run("nuts", result, ndraws, nchains, nwarmup, step_size, max_depth, rng, target_accept, window, adapt, adapt_metric)
+
+
+@dataclass
+class CheesResult(HMCResult):
+    """the fields of HMCResult (step_size: the one shared step size, repeated per chain; nleapfrog is 0: it is jittered) and what ChEES
+    learned; `warmup` holds Engine.adapt_get's traces plus tau_trace, grad_trace, hmean_trace (nwarmup,) and status"""
+    trajectory_length: float = 0.0
+    n_leapfrog: np.ndarray = None     # (ndraws,) int32: leapfrog steps of every sampling transition, the same in all chains
+    max_leapfrog: int = 0
+
+    def __str__(self):
+        d, n, k = self.draws.shape
+        lines = ["ChEES-HMC result (fitted Woodbury metric)", f"  chains: {k}", f"  draws per chain: {n} (warm-up: {self.nwarmup})",
+                 f"  trajectory length: {self.trajectory_length:.3g}", f"  step size: {float(self.step_size[0]):.3g}",
+                 f"  leapfrog steps per draw: {float(np.mean(self.n_leapfrog)):.1f} (limit {self.max_leapfrog})",
+                 f"  mean acceptance: {float(np.mean(self.accept_prob)):.2f}", f"  divergent transitions: {int(np.sum(self.divergent))}"]
+        return "\n".join(lines)
+
+
+def chees(result, ndraws, *, nchains=None, nwarmup=200, step_size="auto", max_leapfrog=64, rng=None, target_accept=0.651):
+    """`ndraws` transitions of `nchains` chains of ChEES-HMC (Hoffman, Radul & Sountsov 2021) from a PathfinderResult /
+    MultiPathfinderResult: the starts, metrics and seeds of `hmc`, but ONE step size and ONE trajectory length for all chains, both learned
+    on the device during the `nwarmup` warm-up transitions -- the step size by dual averaging on the harmonic mean of the chains'
+    acceptance, the trajectory length from the chains' spread -- so no leapfrog count has to be guessed and, unlike `nuts`, every closure
+    call is a full round of all chains (include/pfmi.h: pfmi_chees_enqueue).  step_size: a number or "auto" (d^(-1/4)), the initial one;
+    nwarmup = 0 samples with it and a trajectory of one step.  More chains give a better estimate: use all of the result's draws."""
+    if not 1 <= int(max_leapfrog) <= Engine.CHEES_MAX_LEAPFROG:
+        raise ValueError(f"max_leapfrog must be in 1 .. {Engine.CHEES_MAX_LEAPFROG}")
+    if isinstance(step_size, str) and step_size != "auto":
+        raise ValueError('step_size must be a number or "auto"')
+    eng, x0, pts, seeds = _chains("chees", result, nchains, rng)
+    d, nchains = x0.shape
+    eps0 = d ** -0.25 if isinstance(step_size, str) else float(step_size)
+    eng.chees_enqueue(pts, x0, seeds, eps0, 0.0, int(max_leapfrog), int(nwarmup), int(ndraws), target_accept)
+    eng.chees_wait()
+    got, ch = eng.hmc_get(), eng.chees_get()
+    warm = None
+    if nwarmup > 0:
+        warm = eng.adapt_get()
+        warm.pop("step_size")
+        warm["status"] = ch["status"]
+        warm.update({k: ch[k] for k in ("tau_trace", "grad_trace", "hmean_trace")})
+    return CheesResult(got["draws"], got["logp"], got["accept_prob"], got["energy_error"], got["divergent"], np.full(nchains, ch["step_size"]),
+                       np.array(pts), 0, int(nwarmup), eng, eng.hmc_runs, ch["traj_length"], ch["n_leapfrog"][int(nwarmup):].copy(),
+                       int(max_leapfrog), warmup=warm)
 
 
 class _CallableModule(types.ModuleType):
