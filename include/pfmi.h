@@ -128,7 +128,13 @@ int32_t pfmi_debug_set(const char *key, const char *value);
  * large-d kernels decline, and PFMI_FIT_KERNEL=mem.
  * "fit:tsqr:<KPAD>": the TSQR kernel with Householder reconstruction (d > 1024) -- KPAD (8 .. 32).
  * "fit:panel:<KPAD>,<RPT>,<cols>": the left-looking panel kernel (d > 1024) -- KPAD (8 .. 32), RPT the bucket of rows per thread
- * (5, 10, 20, 32), cols the panel width (4; 2 in the last bucket). */
+ * (5, 10, 20, 32), cols the panel width (4; 2 in the last bucket).
+ * The history walk likewise, one count per kernel launch (the stage name "history" keeps its meaning):
+ * "hist:reg:<EPT>,<NT>": the register-set kernel -- EPT coordinates per thread and NT threads per path: 1,64 2,64 4,64 (d <= 64,
+ * 128, 256), 2,256 4,256 (d <= 512, 1024), 2,1024 (d <= 2048), 12,1024 16,1024 (d <= 12 288, 16 384), and 4,1024 .. 10,1024 under
+ * PFMI_HISTORY_KERNEL=prefetch (2048 < d <= 10 240).
+ * "hist:lean:<EPT>": the lean kernel with 1 / alpha in LDS (2048 < d <= 10 240) -- EPT 4, 6, 8, 10.
+ * "hist:mem": the memory-resident kernel (d > 16 384, and PFMI_HISTORY_KERNEL=mem). */
 int32_t pfmi_timer_start(pfmi_ctx *ctx);
 int32_t pfmi_timer_stop(pfmi_ctx *ctx, double *milliseconds);
 int32_t pfmi_profile(pfmi_ctx *ctx, int32_t enable);

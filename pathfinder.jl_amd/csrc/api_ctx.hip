@@ -391,7 +391,7 @@ int32_t pfmi_kernel_time(pfmi_ctx *c, const char *name, double *ms, int64_t *lau
         if (launches) *launches = (pl == c->cd_plans.end()) ? 0 : pl->second;
         return PFMI_OK;
     }
-    if (strncmp(name, "fit:", 4) == 0) {                              // launches of one fit-kernel plan, host-side count ("fit" itself stays the stage)
+    if (strncmp(name, "fit:", 4) == 0 || strncmp(name, "hist:", 5) == 0) {   // launches of one fit-kernel or history-walk plan, host-side count ("fit" and "history" stay the stages)
         auto pl = c->fit_plans.find(name);
         if (ms) *ms = 0.0;
         if (launches) *launches = (pl == c->fit_plans.end()) ? 0 : pl->second;

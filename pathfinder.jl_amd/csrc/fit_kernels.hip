@@ -1186,16 +1186,20 @@ int32_t pf_launch_history(pfmi_ctx *c, double eps, const HistSeg *seg) {
             hipLaunchKernelGGL(pf_history_mem_kernel, dim3(c->K), dim3(1024), 0, c->stream, c->d, c->J, eps, c->d_off.as<int64_t>(),
                                c->th(), c->gr(), c->alpha_all.as<double>(), c->hist_len.as<int>(),
                                c->hist_src.as<int>(), c->n_rej.as<int>(), c->hist_acc.as<int>(), sg);
+            pf_note_fit_plan(c, "hist:mem");
             pf_kernel_end(c, "history");
             PF_HIP(hipGetLastError());
             return PFMI_OK;
         }
     }
 #define PF_HIST(E, NT)                                                                                           \
-    hipLaunchKernelGGL((pf_history_kernel<E, NT>), dim3(c->K), dim3(NT), 0, c->stream, c->d, c->J, eps,           \
-                       c->d_off.as<int64_t>(), c->th(), c->gr(),                      \
-                       c->alpha_all.as<double>(), c->hist_len.as<int>(), c->hist_src.as<int>(), c->n_rej.as<int>(),          \
-                       c->hist_acc.as<int>(), sg)
+    do {                                                                                                         \
+        hipLaunchKernelGGL((pf_history_kernel<E, NT>), dim3(c->K), dim3(NT), 0, c->stream, c->d, c->J, eps,       \
+                           c->d_off.as<int64_t>(), c->th(), c->gr(),                                             \
+                           c->alpha_all.as<double>(), c->hist_len.as<int>(), c->hist_src.as<int>(), c->n_rej.as<int>(), \
+                           c->hist_acc.as<int>(), sg);                                                           \
+        pf_note_fit_plan(c, "hist:reg:" #E "," #NT);                                                              \
+    } while (0)
     // the walk is sequential in l: one block reduction per iteration, cheaper across 4 waves than across 16
     // (a single wave for d <= 256: no cross-wave exchange at all)
     if (c->d <= 64) PF_HIST(1, 64); else if (c->d <= 128) PF_HIST(2, 64); else if (c->d <= 256) PF_HIST(4, 64);
@@ -1210,6 +1214,7 @@ int32_t pf_launch_history(pfmi_ctx *c, double eps, const HistSeg *seg) {
         hipLaunchKernelGGL(kern, dim3(c->K), dim3(1024), sizeof(double) * E * 1024, c->stream, c->d, c->J, eps,         \
                            c->d_off.as<int64_t>(), c->th(), c->gr(), c->alpha_all.as<double>(), \
                            c->hist_len.as<int>(), c->hist_src.as<int>(), c->n_rej.as<int>(), c->hist_acc.as<int>(), sg);  \
+        pf_note_fit_plan(c, "hist:lean:" #E);                                                                            \
     } while (0)
            if (ept <= 2) PF_HIST(2, 1024);
            else if (ept <= 4) { if (lean) PF_HIST_LEAN(4); else PF_HIST(4, 1024); }

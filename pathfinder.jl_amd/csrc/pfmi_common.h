@@ -256,7 +256,7 @@ struct pfmi_ctx {
     int64_t qf_lost_total = 0; // pieces that ever gave up waiting (pfmi_kernel_time("qf_handover_lost") reports it as `launches`)
     std::map<std::string, int64_t> qf_plans;   // scan launches per plan "qf:<KC>,<TGT>,<RPAD>,<NG>:<res|stream>:<cut>" (launch_qf_ng; pfmi_kernel_time)
     std::map<std::string, int64_t> draw_plans; // draw-kernel launches per plan "xw:.." / "mf:.." / "lane:.." (pf_note_draw_plan; pfmi_kernel_time)
-    std::map<std::string, int64_t> fit_plans;  // fit-kernel launches per plan "fit:reg:.." / "fit:gen:.." / "fit:tsqr:.." / "fit:panel:.." (pf_note_fit_plan; pfmi_kernel_time)
+    std::map<std::string, int64_t> fit_plans;  // fit-kernel launches per plan "fit:reg:.." / "fit:gen:.." / "fit:tsqr:.." / "fit:panel:.." and history-walk launches "hist:reg:.." / "hist:lean:.." / "hist:mem" (pf_note_fit_plan; pfmi_kernel_time)
 
     // pool / PSIS / resample state
     bool pooled = false;
@@ -365,7 +365,7 @@ int32_t pf_launch_history(pfmi_ctx *c, double eps, const HistSeg *seg = nullptr)
 int32_t pf_launch_fit(pfmi_ctx *c, int seg_l0 = 0, int seg_len = 0);
 // one launch of a draw kernel under its plan name, counted per ctx for pfmi_kernel_time (include/pfmi.h); host side only
 static inline void pf_note_draw_plan(pfmi_ctx *c, const char *name) { ++c->draw_plans[name]; }
-// the same for one launch of a fit kernel ("fit:<kernel>:<instance>", include/pfmi.h)
+// the same for one launch of a fit kernel ("fit:<kernel>:<instance>") or of a history-walk kernel ("hist:<kernel>[:<instance>]", include/pfmi.h)
 static inline void pf_note_fit_plan(pfmi_ctx *c, const char *name) { ++c->fit_plans[name]; }
 int32_t pf_launch_elbo_draws(pfmi_ctx *c, const int32_t *d_points, const uint64_t *d_seeds, int64_t nfits,
                              int64_t n0, int64_t N, const double *d_u, int64_t u_stride,

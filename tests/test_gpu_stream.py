@@ -42,7 +42,8 @@ def _packed(pfmi, tg, x0, J, maxiters, N, sd_stride, N_r, ndraws):
     return out
 
 
-def _streamed(pfmi, tg, x0, J, maxiters, N, sd_stride, N_r, ndraws, repeat=1):
+def _streamed(pfmi, tg, x0, J, maxiters, N, sd_stride, N_r, ndraws, repeat=1, count=()):
+    """count: plan names whose launch counts on the streaming engine (pfmi_kernel_time) are returned under `launches`"""
     K = x0.shape[0]
     e = pfmi.Engine(0)
     e.set_target(tg)
@@ -58,7 +59,7 @@ def _streamed(pfmi, tg, x0, J, maxiters, N, sd_stride, N_r, ndraws, repeat=1):
         traces = [e.get_trace(k) for k in range(K)]
         fit = e.get_fit(int(e.offsets[0]) + int(best[0]), int(jeff[int(e.offsets[0]) + int(best[0])])) if best[0] > 0 else None
         outs.append(dict(npts=npts, off=e.offsets.copy(), status=status, jeff=jeff, logdet=logdet, nrej=nrej, elbo=elbo, se=se, best=best,
-                         res=res, idx=idx, draws=draws, traces=traces, fit=fit))
+                         res=res, idx=idx, draws=draws, traces=traces, fit=fit, launches={nm: e.kernel_time(nm)[1] for nm in count}))
         comm.close()
     e.close()
     return outs
