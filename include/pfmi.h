@@ -134,7 +134,10 @@ int32_t pfmi_debug_set(const char *key, const char *value);
  * 128, 256), 2,256 4,256 (d <= 512, 1024), 2,1024 (d <= 2048), 12,1024 16,1024 (d <= 12 288, 16 384), and 4,1024 .. 10,1024 under
  * PFMI_HISTORY_KERNEL=prefetch (2048 < d <= 10 240).
  * "hist:lean:<EPT>": the lean kernel with 1 / alpha in LDS (2048 < d <= 10 240) -- EPT 4, 6, 8, 10.
- * "hist:mem": the memory-resident kernel (d > 16 384, and PFMI_HISTORY_KERNEL=mem). */
+ * "hist:mem": the memory-resident kernel (d > 16 384, and PFMI_HISTORY_KERNEL=mem).
+ * The operator surface likewise, one count per kernel launch:
+ * "woodbury:<KPAD>:<mode>": the lane-per-column kernel behind pfmi_woodbury_apply -- column padding KPAD (4 .. 64), mode 0 .. 3.
+ * "woodbury_diag:<KPAD>": the kernel behind pfmi_woodbury_diag. */
 int32_t pfmi_timer_start(pfmi_ctx *ctx);
 int32_t pfmi_timer_stop(pfmi_ctx *ctx, double *milliseconds);
 int32_t pfmi_profile(pfmi_ctx *ctx, int32_t enable);
@@ -332,8 +335,15 @@ int32_t pfmi_mixture_logpdf_dev(pfmi_ctx *ctx, int32_t K, const int64_t *points,
 #define PFMI_OP_SOLVE 5        /* W \ x = R \ (L \ x)                src/woodbury.jl:344, 70-74       */
 #define PFMI_OP_QUAD 6         /* quad(W, x)    = |R x|^2 per column  src/woodbury.jl:384-397          */
 #define PFMI_OP_INVQUAD 7      /* invquad(W, x) = |L \ x|^2           src/woodbury.jl:369-382          */
+/* A fit whose status is not PFMI_FIT_OK has no factor: every entry of out (d x N, or the N quadratic forms) is NaN, whatever X holds,
+ * as pfmi_mixture_logpdf reports such a component.  For a PFMI_FIT_OK fit a column of out depends on that column of X alone (one lane
+ * per column): an all-zero column gives exact zeros (+0.0 for the quadratic forms) and a non-finite entry stays in its own column.
+ * Launches are counted per instantiation under "woodbury:<KPAD>:<mode>" (pfmi_kernel_time; host-side counters like "hmc:..", ms = 0):
+ * mode 0 unwhiten, 1 whiten, 2 R x, 3 invunwhiten; MUL = mode 2 then 0, SOLVE = mode 1 then 3, QUAD = mode 2, INVQUAD = mode 1. */
 int32_t pfmi_woodbury_apply(pfmi_ctx *ctx, int64_t point, int32_t op, int64_t N, const double *X, double *out);
-/* diag(W) = diag(A) + rowwise b' D b   (src/woodbury.jl:326-329); diag[d] */
+/* diag(W) = diag(A) + rowwise b' D b   (src/woodbury.jl:326-329); diag[d].  b is recomputed from the trace (theta, grad, the fit's
+ * hist_src), not read from the stored B.  Every entry is NaN for a fit whose status is not PFMI_FIT_OK, as pfmi_woodbury_apply.
+ * Counted under "woodbury_diag:<KPAD>". */
 int32_t pfmi_woodbury_diag(pfmi_ctx *ctx, int64_t point, double *diag);
 
 /* ---- static HMC with a fitted metric, for gradient closures ------------------------------------------------------------ */

@@ -307,7 +307,7 @@ struct pfmi_ctx {
     int32_t scale_staged_K = 0;
     DevBuf nt_vec, nt_st, nt_depth, nt_nleap, nt_pev, nt_ctr;   // NUTS: the chains' vectors and checkpoints, their scalars, statistics, events
     int64_t *nt_status = nullptr; // page-locked: round << 32 | chains still running, written by the last workgroup of each NUTS round
-    std::map<std::string, int64_t> hmc_plans;           // step launches per plan "hmc:<KPAD>:<res|stream>" (pfmi_kernel_time)
+    std::map<std::string, int64_t> hmc_plans;           // step launches per plan "hmc:<KPAD>:<res|stream>", operator launches "woodbury:<KPAD>:<mode>", "woodbury_diag:<KPAD>" (pfmi_kernel_time)
     DevBuf cd_ws, cd_in;                                // pfmi_chain_diagnostics: its workspace (chain_diag_kernels.hip) and uploaded host records
     std::map<std::string, int64_t> cd_plans;            // its counting launches per plan "chain_diag:count:<one|tiled>" (pfmi_kernel_time)
     bool elbo_pending = false;    // pfmi_elbo_batch_enqueue issued

@@ -152,9 +152,11 @@ template <int KPAD>
 __global__ void pf_woodbury_diag_kernel(int d, int J, int p, int64_t p0, const double *__restrict__ theta,
                                         const double *__restrict__ grad, const double *__restrict__ alpha_all,
                                         const int32_t *__restrict__ hist_len, const int32_t *__restrict__ hist_src,
-                                        const double *__restrict__ dmat, double *__restrict__ out) {
+                                        const double *__restrict__ dmat, const int32_t *__restrict__ status,
+                                        double *__restrict__ out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= d) return;
+    if (status[p] != PFMI_FIT_OK) { out[i] = NAN; return; }      // a failed fit has no covariance: NaN, as pf_woodbury_kernel
     const int j = hist_len[p], m = 2 * j;
     const double al = alpha_all[(size_t)p * d + i];
     const double *D = dmat + (size_t)p * KPAD * KPAD;
@@ -190,6 +192,9 @@ __global__ void pf_woodbury_diag_kernel(int d, int J, int p, int64_t p0, const d
 template <int KPAD>
 static void launch_wb(pfmi_ctx *c, int mode, int64_t p, int64_t N, const double *in, double *out) {
     dim3 grid((unsigned)((N + WB_THREADS - 1) / WB_THREADS)), block(WB_THREADS);
+    char name[32];
+    snprintf(name, sizeof name, "woodbury:%d:%d", KPAD, mode);
+    ++c->hmc_plans[name];                                          // one count per launch (pfmi_kernel_time)
     auto go = [&](auto M) {
         hipLaunchKernelGGL((pf_woodbury_kernel<KPAD, M()>), grid, block, 0, c->stream, c->d, (int)p, N, in, out,
                            c->vh.as<double>(), c->tmat.as<double>(), c->vchol.as<double>(), c->sqrt_alpha.as<double>(),
@@ -202,6 +207,7 @@ static void launch_wb(pfmi_ctx *c, int mode, int64_t p, int64_t N, const double 
 
 int32_t pf_launch_woodbury_prim(pfmi_ctx *c, int mode, int64_t p, int64_t N, const double *d_in, double *d_out) {
     if (N <= 0) return PFMI_OK;
+    PF_CHECK(mode >= 0 && mode <= 3, PFMI_ERR_ARG, "woodbury: unknown mode %d", mode);
     PF_CHECK((pf_dispatch_kpad<4, 8, 12, 16, 20, 32, 64>(c->kpad, [&](auto KP) { launch_wb<KP()>(c, mode, p, N, d_in, d_out); })),
              PFMI_ERR_UNSUPPORTED, "unsupported kpad %d", c->kpad);
     PF_HIP(hipGetLastError());
@@ -219,9 +225,13 @@ int32_t pf_launch_woodbury_diag(pfmi_ctx *c, int64_t p, double *d_out) {
     const int64_t p0 = c->off[(size_t)c->path_of[(size_t)p]];
     dim3 grid((unsigned)((c->d + 255) / 256)), block(256);
     const bool ok = pf_dispatch_kpad<4, 8, 12, 16, 20, 32, 64>(c->kpad, [&](auto KP) {
+        char name[32];
+        snprintf(name, sizeof name, "woodbury_diag:%d", (int)KP());
+        ++c->hmc_plans[name];                                      // one count per launch (pfmi_kernel_time)
         hipLaunchKernelGGL(pf_woodbury_diag_kernel<KP()>, grid, block, 0, c->stream, c->d, c->J, (int)p, p0,
                            c->th(), c->gr(), c->alpha_all.as<double>(),
-                           c->hist_len.as<int32_t>(), c->hist_src.as<int32_t>(), c->dmat.as<double>(), d_out);
+                           c->hist_len.as<int32_t>(), c->hist_src.as<int32_t>(), c->dmat.as<double>(),
+                           c->status.as<int32_t>(), d_out);
     });
     PF_CHECK(ok, PFMI_ERR_UNSUPPORTED, "unsupported kpad %d", c->kpad);
     PF_HIP(hipGetLastError());

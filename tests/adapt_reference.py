@@ -176,8 +176,9 @@ def mirror(M, logp_and_grad, x0, seed, eps0, Lf, W, T, delta=0.8):
 
 # ---- the cases of tests/test_gpu_adapt.py ------------------------------------------------------------------------------------------------
 # bit equality with the plain calls: the shapes of hmc_reference.GRID that cover the column paddings 4, 12, 32, both targets and the
-# streamed factor route; (d, J, target, W, T)
-BIT_CASES = [(d, J, tn, 12, 4) for d, J in ((5, 2), (64, 6), (257, 16)) for tn in ("gauss", "funnel")] + [(20000, 6, "gauss", 3, 1)]
+# streamed factor route, and the one padding that is no power of two (J = 10: KPAD 20) on the Gaussian; (d, J, target, W, T)
+BIT_CASES = ([(d, J, tn, 12, 4) for d, J in ((5, 2), (64, 6), (257, 16)) for tn in ("gauss", "funnel")] + [(64, 10, "gauss", 12, 4)]
+             + [(20000, 6, "gauss", 3, 1)])
 BIT_LF, BIT_DEPTH = 3, 4
 # the sampling case (hmc_reference.sampling_case): the warm-up the CPU test admits on the mirror, then the T of the plain sampling test
 SAMPLING_W, SAMPLING_T = 150, H.SAMPLING_T

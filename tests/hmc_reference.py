@@ -312,7 +312,10 @@ def check(M, rec, seed, eps, Lf, kpad, label=""):
 
 # ---- the grid of tests/test_gpu_hmc_steps.py (shapes, targets, seeds, step sizes; the CPU test runs the same cases on the mirror) ----
 GRID_T, GRID_LF, GRID_K = 4, 3, 3
-GRID = [(d, J, tn, GRID_T) for d in (5, 64, 257, 1000) for J in (2, 6, 16, 32) for tn in ("gauss", "funnel")] + [(20000, 6, "gauss", 2)]
+# d x J in {2, 6, 16, 32} (KPAD 4, 12, 32, 64); the paddings in between (J = 4, 8, 10: KPAD 8, 16, 20) at d = 64, and KPAD 20 at d = 5 < KPAD
+GRID_MID = [(64, 4), (64, 8), (64, 10), (5, 10)]
+GRID = ([(d, J, tn, GRID_T) for d in (5, 64, 257, 1000) for J in (2, 6, 16, 32) for tn in ("gauss", "funnel")]
+        + [(d, J, tn, GRID_T) for d, J in GRID_MID for tn in ("gauss", "funnel")] + [(20000, 6, "gauss", 2)])
 EPS_MULT = (0.4, 1.0, 2.2)        # per chain, times d^(-1/4): a small step accepts, a large one rejects
 
 

@@ -466,7 +466,8 @@ def check(M, rec, seed, eps, max_depth, kpad, label=""):
 
 # ---- the grid of tests/test_gpu_nuts_steps.py (the fits, targets, seeds and step sizes of tests/test_gpu_hmc_steps.py) ---------------------
 GRID_DEPTH, GRID_T, GRID_K = 5, 3, 3
-GRID = [(d, J, tn, GRID_DEPTH, GRID_T) for d in (5, 64, 257, 1000) for J in (2, 6, 16, 32) for tn in ("gauss", "funnel")] + [(20000, 6, "gauss", 3, 1)]
+GRID = ([(d, J, tn, GRID_DEPTH, GRID_T) for d in (5, 64, 257, 1000) for J in (2, 6, 16, 32) for tn in ("gauss", "funnel")]
+        + [(d, J, tn, GRID_DEPTH, GRID_T) for d, J in H.GRID_MID for tn in ("gauss", "funnel")] + [(20000, 6, "gauss", 3, 1)])
 
 
 def case_id(case):

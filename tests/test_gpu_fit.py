@@ -201,9 +201,12 @@ def test_large_d_general_paths(pfmi_mod, eng, d, maxit):
 
 @pytest.mark.parametrize("name,K,J", [("iso10", 1, 6), ("lr50", 2, 6), ("diag30", 1, 10), ("lr10", 1, 8), ("lr10", 1, 6)])
 def test_woodbury_operator_surface(pfmi_mod, eng, name, K, J):
-    """remaining PDMats surface on the device vs the oracle and dense algebra (reference test/woodbury.jl:239-402):
-    unwhiten / whiten / invunwhiten / R*x / W*x / W\\x / quad / invquad / diag, matrices and vectors; the lr10 cases are the
-    n < m ones (d = 10, 2j = 16 / 12: test/woodbury.jl:21-31 has n = 5, m = 8)."""
+    """remaining PDMats surface on the device vs dense algebra and the oracle's own factor (reference test/woodbury.jl:239-402): what ties
+    the device's factor to W itself -- W*x / W\\x / quad / invquad / diag against F.dense(), matrices and vectors -- and L, R and their
+    inverses against the oracle's independently computed factor where its QR is well conditioned; the lr10 cases are the n < m ones
+    (d = 10, 2j = 16 / 12: test/woodbury.jl:21-31 has n = 5, m = 8).  The operators' own arithmetic -- every op under a derived bound
+    against long double at every column padding, head-block edge and block edge, and the round trips L (L \\ x) = x, R \\ (R x) = x as
+    long-double residuals with no conditioning gate -- is in tests/test_gpu_woodbury.py."""
     tg, traces = _setup(pfmi_mod, eng, name, K, J)
     status, jeff, logdet, _ = eng.fit_status()
     rng = np.random.default_rng(5)
@@ -225,18 +228,13 @@ def test_woodbury_operator_surface(pfmi_mod, eng, name, K, J):
         np.testing.assert_allclose(eng.woodbury_diag(l), np.diag(W), rtol=1e-9, atol=1e-12)
         x = X[:, 0].copy()
         np.testing.assert_allclose(eng.woodbury_apply(l, "mul", x), W @ x, **tol)
-        # L and R themselves agree with the oracle's factor when the QR is well conditioned, and always satisfy
-        # L (L \ x) = x, R \ (R x) = x, unwhiten(whiten(x)) = x
+        # L and R themselves agree with the oracle's factor when the QR is well conditioned
         if _well_conditioned(F):
             n_strict += 1
             np.testing.assert_allclose(eng.woodbury_apply(l, "unwhiten", X), F.lmul_L(X), rtol=1e-7, atol=1e-8 * np.abs(X).max() * np.sqrt(np.abs(W).max()))
             np.testing.assert_allclose(eng.woodbury_apply(l, "rmul", X), F.lmul_R(X), rtol=1e-7, atol=1e-8 * np.abs(X).max() * np.sqrt(np.abs(W).max()))
             np.testing.assert_allclose(eng.woodbury_apply(l, "whiten", X), F.ldiv_L(X), rtol=1e-6, atol=1e-7 * np.abs(F.ldiv_L(X)).max())
             np.testing.assert_allclose(eng.woodbury_apply(l, "invunwhiten", X), F.ldiv_R(X), rtol=1e-6, atol=1e-7 * np.abs(F.ldiv_R(X)).max())
-        back = eng.woodbury_apply(l, "unwhiten", eng.woodbury_apply(l, "whiten", X))
-        np.testing.assert_allclose(back, X, rtol=1e-6, atol=1e-7 * np.abs(X).max())
-        back = eng.woodbury_apply(l, "invunwhiten", eng.woodbury_apply(l, "rmul", X))
-        np.testing.assert_allclose(back, X, rtol=1e-6, atol=1e-7 * np.abs(X).max())
     assert n_strict >= MIN_STRICT.get(name, 2), (name, n_strict)
     if name == "lr10":
         assert n_wide >= 2, n_wide

@@ -117,14 +117,25 @@ def _snapshot(eng, jeff, X):
         f = eng.get_fit(p, int(jeff[p]))
         out += [np.asarray(f[nm]).tobytes() for nm in ("alpha", "B", "D", "qr_factors", "T", "V", "mu")] + [np.float64(f["logdet"]).tobytes()]
         out.append(eng.logpdf(p, X).tobytes())
+        # the operator surface reads the same padding: mode 3 back-substitutes through the identity padding of V, mode 1 divides by its
+        # padded diagonal, every mode contracts over the padded columns of Vh and T, diag over the padding of D
+        out += [np.asarray(eng.woodbury_apply(p, op, X)).tobytes() for op in _ops(eng)]
+        out.append(eng.woodbury_diag(p).tobytes())
     return out
+
+
+def _ops(eng):
+    ops = sorted(eng.OPS, key=eng.OPS.get)
+    assert len(ops) == 8
+    return ops
 
 
 @pytest.mark.parametrize("d,J,regime,force", REFIT, ids=[fr.plan_for(d, J, f) for d, J, _, f in REFIT])
 def test_refit_on_a_used_context_is_bit_identical(pfmi_mod, eng, monkeypatch, d, J, regime, force):
-    """the padding of Vh, T and V (columns 2 j .. KPAD, rows beyond k) is read by the scan and the density kernels but is invisible through
-    pfmi_get_fit.  On an engine that has just fitted a full J = 8 history of the same d (KPAD = 16: another layout, every slot written)
-    the case's fits, statuses and densities at 8 columns must be the bits a fresh engine gives."""
+    """the padding of Vh, T, V and D (columns 2 j .. KPAD, rows beyond k) is read by the scan, the density kernels and the operator surface
+    (pfmi_woodbury_apply, pfmi_woodbury_diag) but is invisible through pfmi_get_fit.  On an engine that has just fitted a full J = 8
+    history of the same d (KPAD = 16: another layout, every slot written) the case's fits, statuses, densities, all eight operators at 8
+    columns and diag must be the bits a fresh engine gives."""
     c = fr.make_case(d, J, regime, 900 + d)
     plan = fr.plan_for(d, J, force)
     X = np.random.default_rng(d).normal(size=(d, 8))

@@ -2,8 +2,9 @@
 long-double checker of tests/hmc_reference.py, through the example closure of examples/device_logp with PFMI_HMC_RECORD_PATH.
 
 Grid (hmc_reference.GRID): d in {5, 64, 257, 1000} x history_length in {2, 6, 16, 32} (column padding 4, 12, 32, 64) x {Gaussian rank-2
-target, funnel}, K = 3 chains whose metrics are the fits of a path's first point (j_eff = 0), of an early point with 0 < j_eff < J and
-of the path's best fit; Lf = 3, T = 4; and one d = 20 000, J = 6 case (the factor rows streamed from HBM), T = 2.  Every chain starts
+target, funnel}, and history_length 4, 8, 10 (column padding 8, 16, 20) at d = 64 and 10 at d = 5 (d < KPAD = 20): all seven paddings
+of hm_launch_step.  K = 3 chains whose metrics are the fits of a path's first point (j_eff = 0), of an early point with 0 < j_eff < J
+and of the path's best fit; Lf = 3, T = 4; and one d = 20 000, J = 6 case (the factor rows streamed from HBM), T = 2.  Every chain starts
 at the best fit's trace point; the three chains step by 0.4, 1 and 2.2 times d^(-1/4), so that small and large energy errors both occur.
 The bounds are derived in hmc_reference's docstring; borderline decisions (exempt) are capped at 2 % of a case's transitions, i.e.
 none at these sizes.  Largest ratios seen: profiles/hmc_step_parity.md."""
@@ -16,6 +17,7 @@ import hmc_reference as H
 import margins as mg
 from helpers import demo_device_target, fit_seeds
 from lbfgs_step_reference import HAVE_LONGDOUBLE, SKIP_REASON
+from woodbury_reference import c_lane
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not HAVE_LONGDOUBLE, reason=SKIP_REASON)]
 
@@ -52,9 +54,10 @@ def _run_case(pfmi_mod, eng, case):
         p = int(pts[k])
         M = H.Metric.from_fit(eng.get_fit(p, int(jeff[p])))
         # the checker's operators are the library's: Metric.L / Metric.R against pfmi_woodbury_apply (PFMI_OP_UNWHITEN / PFMI_OP_RMUL) on this
-        # fit, within the lane kernel's bound (one fma per row: d + 3 KPAD + 16 roundings of the same absolute sums)
+        # fit, within the lane kernel's bound (woodbury_reference.c_lane: one fma per row, d + 3 KPAD + 16 roundings of the same absolute
+        # sums), at every padding of the grid; the whole surface against long double: tests/test_gpu_woodbury.py
         for op, ref, scale in (("unwhiten", M.L(z), M.L_abs(np.abs(z))), ("rmul", M.R(z), M.R_abs(np.abs(z)))):
-            dev = np.abs(eng.woodbury_apply(p, op, z) - ref) / ((d + 3 * kpad + 16) * H.EPS * scale)
+            dev = np.abs(eng.woodbury_apply(p, op, z) - ref) / (c_lane(d, kpad) * H.EPS * scale)
             mg.check("hmc:" + cid, "hmc_op_" + op, [dev.max()], 1.0)
         rec = H.gpu_recording(x0[:, k], path, got, k)
         out = H.check(M, rec, int(seeds[k]), float(eps[k]), Lf, kpad, label=(cid, k))
@@ -81,7 +84,8 @@ def test_grid_coverage(pfmi_mod, eng):
     for case in H.GRID:
         if H.case_id(case) not in _COV["cases"]:
             _run_case(pfmi_mod, eng, case)
-    for kpad in (4, 12, 32, 64):
+    assert {H.kpad_for(c[1]) for c in H.GRID} == set(H.KPADS)
+    for kpad in H.KPADS:
         assert sum(eng.kernel_time("hmc:%d:%s" % (kpad, r))[1] for r in ("res", "stream")) > 0, kpad
     assert eng.kernel_time("hmc:12:res")[1] > 0 and eng.kernel_time("hmc:12:stream")[1] > 0 and eng.kernel_time("hmc:64:stream")[1] > 0
     assert _COV["accepted"] > 0 and _COV["rejected"] > 0, _COV

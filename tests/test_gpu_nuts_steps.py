@@ -2,8 +2,9 @@
 checker of tests/nuts_reference.py, through the example closure of examples/device_logp with PFMI_NUTS_RECORD_PATH.
 
 Grid (nuts_reference.GRID): d in {5, 64, 257, 1000} x history_length in {2, 6, 16, 32} (column padding 4, 12, 32, 64) x {Gaussian rank-2
-target, funnel}, K = 3 chains on the fits tests/test_gpu_hmc_steps.py picks (a path's first point, an early point with 0 < j_eff < J, the
-best fit), stepping by 0.4, 1 and 2.2 times d^(-1/4); max_depth 5, T = 3; and one d = 20 000, J = 6 case (the factor rows streamed from
+target, funnel}, and history_length 4, 8, 10 (column padding 8, 16, 20) at d = 64 and 10 at d = 5 (d < KPAD = 20): all seven paddings
+of hm_launch_step.  K = 3 chains on the fits tests/test_gpu_hmc_steps.py picks (a path's first point, an early point with
+0 < j_eff < J, the best fit), stepping by 0.4, 1 and 2.2 times d^(-1/4); max_depth 5, T = 3; and one d = 20 000, J = 6 case (the factor rows streamed from
 HBM), max_depth 3, T = 1.  The bounds are derived in nuts_reference's docstring; borderline decisions (exempt) are capped at 2 % of a
 case's decisions, i.e. none at these sizes.  Largest ratios seen: profiles/nuts_step_parity.md."""
 import json
@@ -78,7 +79,8 @@ def test_grid_coverage(pfmi_mod, eng):
     for case in N.GRID:
         if N.case_id(case) not in _COV["cases"]:
             _run_case(pfmi_mod, eng, case)
-    for kpad in (4, 12, 32, 64):
+    assert {H.kpad_for(c[1]) for c in N.GRID} == set(H.KPADS)
+    for kpad in H.KPADS:
         assert sum(eng.kernel_time("nuts:%d:%s" % (kpad, r))[1] for r in ("res", "stream")) > 0, kpad
     assert eng.kernel_time("nuts:12:res")[1] > 0 and eng.kernel_time("nuts:12:stream")[1] > 0 and eng.kernel_time("nuts:64:stream")[1] > 0
     assert _COV["seen"] >= {"dir+", "dir-", "subtree_turn", "tree_turn", "max_depth", "divergent", "candidate_replaced", "candidate_kept"}, _COV["seen"]

@@ -50,7 +50,8 @@ def test_mirror_passes_the_checker_without_borderline_decisions(pfmi_cpu, case):
 
 def test_grid_reaches_every_instantiation_and_both_factor_routes():
     kp = {H.kpad_for(J) for _, J, _, _ in H.GRID}
-    assert kp == {4, 12, 32, 64}                                # the paddings history_length 2, 6, 16, 32 select
+    assert kp == set(H.KPADS)                                   # all seven paddings of pf_dispatch_kpad (hm_launch_step)
+    assert {(d, H.kpad_for(J)) for d, J, _, _ in H.GRID} >= {(64, 8), (64, 16), (64, 20), (5, 20)}
     routes = {H.resident(d, H.kpad_for(J)) for d, J, _, _ in H.GRID}
     assert routes == {True, False}
     assert not H.resident(20000, 12) and H.resident(1000, 12) and not H.resident(1000, 64)

@@ -119,6 +119,11 @@ def test_mirror_samples_a_gaussian(pfmi_cpu):
     assert H.sampling_ok(mean, var, n=256), (mean, var)
 
 
+def test_grid_reaches_every_instantiation():
+    assert {H.kpad_for(c[1]) for c in N.GRID} == set(H.KPADS)   # all seven paddings of pf_dispatch_kpad (hm_launch_step)
+    assert {(c[0], H.kpad_for(c[1])) for c in N.GRID} >= {(64, 8), (64, 16), (64, 20), (5, 20)}
+
+
 def test_grid_reaches_every_kind_of_event(pfmi_cpu):
     """what the coverage test of tests/test_gpu_nuts_steps.py asks of the GPU runs occurs on the mirror's runs of the same grid"""
     for case in N.GRID[:-1]:
