@@ -94,7 +94,7 @@ int32_t pfmi_create(int32_t device, pfmi_ctx **out);
 int32_t pfmi_destroy(pfmi_ctx *ctx);   /* communicators that hold ctx are closed first: any finaliser order is safe */
 int32_t pfmi_sync(pfmi_ctx *ctx);
 /* Test / tuning hooks (kernel selection PFMI_ELBO_KERNEL / PFMI_FIT_KERNEL / PFMI_HISTORY_KERNEL / PFMI_PSIS_KERNEL / PFMI_QF_NO_TAIL,
- * PFMI_DEVCB_CHUNK_MB, PFMI_LBFGS_REJECT_EVERY, the collective path's PFMI_RCCL_LIB / PFMI_COMM_ALLOW_SHARED_GPU / PFMI_COMM_FORCE_RCCL;
+ * PFMI_DEVCB_CHUNK_MB, PFMI_LBFGS_REJECT_EVERY, PFMI_HMC_FUSED_ROUNDS, the collective path's PFMI_RCCL_LIB / PFMI_COMM_ALLOW_SHARED_GPU / PFMI_COMM_FORCE_RCCL;
  * INTEGRATION.md section 3).  A hook is read from this explicit table, or from the environment variable of the same name ONLY when
  * the process was started with PFMI_DEBUG_HOOKS=1: a production process is never re-configured by a stray environment variable.
  * value == NULL unsets: the hook is then read from the environment again (under PFMI_DEBUG_HOOKS=1) or is off.  Process-global; set hooks before other threads use the library.  No reference counterpart. */
@@ -137,7 +137,10 @@ int32_t pfmi_debug_set(const char *key, const char *value);
  * "hist:mem": the memory-resident kernel (d > 16 384, and PFMI_HISTORY_KERNEL=mem).
  * The operator surface likewise, one count per kernel launch:
  * "woodbury:<KPAD>:<mode>": the lane-per-column kernel behind pfmi_woodbury_apply -- column padding KPAD (4 .. 64), mode 0 .. 3.
- * "woodbury_diag:<KPAD>": the kernel behind pfmi_woodbury_diag. */
+ * "woodbury_diag:<KPAD>": the kernel behind pfmi_woodbury_diag.
+ * The fused static-HMC kernel (pfmi_hmc_fused_enqueue) has the stage name "hmc_fused" and, one count per kernel launch,
+ * "hmc_fused:<KPAD>:<res|stream>:<f|g0|g8|g16>": column padding KPAD (4 .. 64), the chain's factor rows staged in LDS or streamed
+ * from HBM, and the target -- the funnel, or the Gaussian family with rank padding 0, 8 or 16. */
 int32_t pfmi_timer_start(pfmi_ctx *ctx);
 int32_t pfmi_timer_stop(pfmi_ctx *ctx, double *milliseconds);
 int32_t pfmi_profile(pfmi_ctx *ctx, int32_t enable);
@@ -484,6 +487,28 @@ int32_t pfmi_hmc_adapt_enqueue(pfmi_ctx *ctx, int32_t K, const int64_t *points, 
 int32_t pfmi_nuts_adapt_enqueue(pfmi_ctx *ctx, int32_t K, const int64_t *points, const double *x0, const uint64_t *seeds,
                                 const double *step_size0, int32_t max_depth, int64_t nwarmup, int64_t ntransitions, double target_accept,
                                 int32_t flags);
+/* ---- static HMC on the built-in targets: whole runs in one persistent kernel ------------------------------------------------ */
+/* pfmi_hmc_enqueue and pfmi_hmc_adapt_enqueue for a ctx whose target is PFMI_TARGET_GAUSS (any rank) or PFMI_TARGET_FUNNEL.  The library
+ * knows the density, so nothing is cut into closure rounds: one workgroup per chain evaluates logp and its gradient in the kernel and loops
+ * over the rounds, with the chain's factor rows staged in LDS once per launch.  No launch makes more than 1024 rounds (csrc/hmc_rows.h:
+ * HM_FUSED_ROUNDS; the hook PFMI_HMC_FUSED_ROUNDS of pfmi_debug_set overrides it): a longer call is several launches that re-enter from the
+ * chains' resident state -- in mid-trajectory too -- and give the same bits whatever the cut.  No kernel waits for another.
+ * nwarmup == 0: the transition of pfmi_hmc_enqueue, steps 1 - 6 above, with the in-kernel value and gradient in the closure's place: the
+ * same normals, acceptance uniform, divergence rule and rows; flags: PFMI_HMC_CONTINUE, PFMI_HMC_RECORD_PATH; target_accept is ignored.
+ * nwarmup >= 1: the run of pfmi_hmc_adapt_enqueue (dual averaging after every warm-up transition, the traces of pfmi_adapt_get, exp(leb)
+ * for sampling); flags must be 0 and target_accept in (0, 1).  nwarmup < 0: PFMI_ERR_ARG.
+ * The run is a static-HMC run in the same buffers and layouts: pfmi_hmc_wait, pfmi_hmc_get, pfmi_hmc_draws_dev, pfmi_hmc_get_path (the
+ * closure_out rows hold the in-kernel value and gradient), pfmi_adapt_get and pfmi_chain_diagnostics(PFMI_CHAIN_SRC_HMC) serve it;
+ * pfmi_hmc_stats reports rounds = (fresh ? 1 : 0) + (nwarmup + ntransitions) nleapfrog evaluations and closure_columns = 0.
+ * Errors are those of pfmi_hmc_enqueue / pfmi_hmc_adapt_enqueue, in their order and with the drain-on-error rule, except that
+ * PFMI_ERR_UNSUPPORTED is returned for any callback target (a DEVICE_CALLBACK target with a gradient closure runs through pfmi_hmc_enqueue)
+ * and for a staged scale (pfmi_chain_scale_set: the metric kernels are not fused).
+ * Out of scope: NUTS, ChEES, the metric windows and scaled chains on built-in targets; pfmi_hmc_enqueue, pfmi_nuts_enqueue, the adaptive
+ * enqueues and pfmi_chees_enqueue are unchanged and still refuse a built-in target.
+ * Stage name "hmc_fused"; plan counters "hmc_fused:<KPAD>:<res|stream>:<f|g0|g8|g16>" (pfmi_kernel_time). */
+int32_t pfmi_hmc_fused_enqueue(pfmi_ctx *ctx, int32_t K, const int64_t *points, const double *x0, const uint64_t *seeds,
+                               const double *step_size, int32_t nleapfrog, int64_t nwarmup, int64_t ntransitions, double target_accept,
+                               int32_t flags);
 /* The last adaptive run: step_size [K] the one its sampling transitions used (a later plain CONTINUE with step sizes of the caller's own
  * does not change what is reported here); eps_trace, accept_trace [K][W] the step size warm-up transition
  * t used and its a_t; divergent, n_leapfrog int32 [K][W]; status [K] (PFMI_ADAPT_*).  Any may be NULL.  Waits for the stream (a NUTS run

@@ -72,7 +72,7 @@ int32_t metric_begin(pfmi_ctx *c, const ChainCall &A, const MetricPlan &P) {
     return PFMI_OK;
 }
 
-static int32_t adapt_args(const char *who, int64_t W, double delta, int32_t flags, int32_t allowed = 0) {
+int32_t adapt_args(const char *who, int64_t W, double delta, int32_t flags, int32_t allowed) {
     PF_CHECK((flags & ~allowed) == 0, PFMI_ERR_ARG, "%s: flags %d not among %d (an adaptive run is a fresh run without a recorded path)", who, flags, allowed);
     PF_CHECK(W >= 1, PFMI_ERR_ARG, "%s: nwarmup %lld must be >= 1", who, (long long)W);
     PF_CHECK(delta > 0.0 && delta < 1.0, PFMI_ERR_ARG, "%s: target_accept %g outside (0, 1)", who, delta);

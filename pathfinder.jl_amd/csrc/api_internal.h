@@ -92,6 +92,8 @@ struct MetricPlan { int nwin = 0; int64_t init = 0, ends[32] = {}; std::vector<d
 int32_t metric_plan(pfmi_ctx *c, const ChainCall &A, std::vector<ChainBuf> &bufs, MetricPlan &P);
 int32_t metric_begin(pfmi_ctx *c, const ChainCall &A, const MetricPlan &P);
 size_t adapt_bytes(int32_t K, int64_t W);
+// api_adapt.hip: what every adaptive enqueue checks first (flags among `allowed`, nwarmup >= 1, target_accept in (0, 1))
+int32_t adapt_args(const char *who, int64_t W, double delta, int32_t flags, int32_t allowed = 0);
 // a plain CONTINUE is about to replace hm_eps: keep the adaptive run's final step sizes for pfmi_adapt_get (stream-ordered copy, once)
 int32_t adapt_keep_step_sizes(pfmi_ctx *c);
 int32_t ensure_pinned(pfmi_ctx *c, size_t x_bytes, size_t lp_bytes);

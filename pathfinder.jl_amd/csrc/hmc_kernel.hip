@@ -26,7 +26,9 @@
 // chain's output depends on nothing but its own inputs.
 #include "pfmi_common.h"
 #include "hmc_rows.h"
+#include "hmc_target.h"
 #include <float.h>
+#include <type_traits>
 
 enum { HM_OPEN = -1, HM_START = 0 };   // HmChain::i: open a trajectory without reading the closure; the start point is being evaluated;
                                        // 1 .. Lf: the leapfrog evaluation the next launch consumes
@@ -82,20 +84,35 @@ __global__ __launch_bounds__(HM_NT) void pf_hmc_init_kernel(HmArgs A) {
 // that finds its chain idle returns at once.  Workgroup 0 alone writes L_t, the status bits and the progress word.
 enum { HM_PLAIN = 0, HM_WARM = 1, HM_METRIC = 2, HM_CHEES = 3 };
 
-template <int KPAD, bool RES, int MODE, class Args>
-__device__ __forceinline__ void hm_step_body(const Args &A) {
-    constexpr bool ADAPT = MODE != HM_PLAIN, METRIC = MODE == HM_METRIC, CHEES = MODE == HM_CHEES;
-    constexpr int NVM = KPAD + 4;                        // KPAD sums + one rider, padded to the multiple of 4 pf_block_sum_mv takes
-    __shared__ HmLds<KPAD, NVM> L;
+//
+// ONE ROUND (hm_round) is what a launch of the step kernels does.  TG == HM_TG_NONE (the step kernels): the round reads the chain's scalar
+// state and step size, consumes the closure's output and writes the state back.  TG a built-in target (pf_hmc_fused_kernel,
+// hmc_fused_kernel.hip: HM_TG_FUNNEL or the Gaussian family's rank padding): the kernel enters the round once per trip of its loop; the
+// round evaluates the target itself where a step kernel reads the closure's output (hm_target_eval, hmc_target.h; a trip that only opens a
+// trajectory evaluates nothing), and the CALLER loads S and eps before the first trip and stores S after the last.  What a trip carries to
+// the next is HmCarry: S, the step size (a warm-up transition's end changes it), `staged` (the factor rows are in LDS: staged ONCE per
+// launch), the ping-pong side `flip` of the reduction buffers and `round`, the row of the recorded path.  The chain's vectors stay in HBM.
+struct HmCarry { HmChain S; double eps; int64_t round; int flip; bool staged; };
+template <int KPAD, bool RES, int MODE, int TG, class Args>
+__device__ __forceinline__ void hm_round(const Args &A, HmCarry &C) {
+    constexpr bool ADAPT = MODE != HM_PLAIN, METRIC = MODE == HM_METRIC, CHEES = MODE == HM_CHEES, FUSED = TG != HM_TG_NONE;
+    // KPAD sums + one rider, padded to the multiple of 4 pf_block_sum_mv takes; FUSED: or the evaluation's reduction, if that is wider
+    constexpr int NVM = FUSED && HmTargetShape<TG>::NV > KPAD + 4 ? HmTargetShape<TG>::NV : KPAD + 4;
+    // (the kernel's one LDS object is declared where it is used: handed on by reference it would lose its address space)
+    __shared__ std::conditional_t<FUSED, HmTargetLds<KPAD, NVM, TG>, HmLds<KPAD, NVM>> L;
     const int k = blockIdx.x, tid = threadIdx.x, d = A.d, K = A.K;
     int flip = 0;
-    HmChain S = A.st[k];
+    HmChain S;
+    if constexpr (FUSED) { flip = C.flip; S = C.S; } else S = A.st[k];
     const int p = A.pts[k];
     const size_t kd = (size_t)k * d;
     const double *gVh = A.vh + (size_t)p * d * KPAD, *T = A.tmat + (size_t)p * KPAD * KPAD, *Vc = A.vchol + (size_t)p * KPAD * KPAD;
     const double *sqa = A.sqa + (size_t)p * d;
     double *X = A.X + kd, *x = A.x + kd, *wg = A.wg + kd, *wt = A.wt + kd, *v = A.v + kd;
-    double eps = A.eps[k];
+    double eps;
+    if constexpr (FUSED) eps = C.eps; else eps = A.eps[k];
+    [[maybe_unused]] int64_t round = 0;
+    if constexpr (FUSED) round = C.round;
     int nleap = A.nleap;
     [[maybe_unused]] bool clamped = false, ended = false, warm_end = false;
     [[maybe_unused]] size_t uo = kd;                     // CHEES: the chain's place among the vectors of the update this transition may end with
@@ -120,20 +137,25 @@ __device__ __forceinline__ void hm_step_body(const Args &A) {
     }
     const uint64_t seed = A.seeds[k];
     const HmFactor F = {gVh, T, Vc, sqa};
-    bool staged = false;                                 // an R pass came before the L pass (hmc_rows.h)
+    bool staged = false;                                 // a pass of this launch has left the factor rows in LDS (hmc_rows.h)
+    if constexpr (FUSED) staged = C.staged;
+    if constexpr (TG > 0) if (!staged) hm_target_stage<TG>(A.tg, L);     // G, once per launch: the first trip's first barrier publishes it
     bool open = S.i == HM_OPEN, drift = false;
     // METRIC: the chain's scale; c_i w of a kick is hm_scaled's (row i is the calling thread's own)
     const double *sc = nullptr;
     if constexpr (METRIC) sc = A.M.scale + kd;
     if (S.i != HM_OPEN) {
-        const double lpt = A.out[k];
+        double lpt;
+        if constexpr (FUSED) lpt = hm_target_eval<TG, NVM>(A.tg, L, X, A.gout + K + kd, d, flip);
+        else lpt = A.out[k];
         const double *g = A.out + K + kd;
         if (A.record) {                                  // what the closure saw and what it answered, before X is rewritten
-            double *pX = A.pX + ((size_t)A.round * K + k) * d, *pout = A.pout + (size_t)A.round * ((size_t)K * (d + 1));
+            const int64_t rnd = FUSED ? round : A.round;
+            double *pX = A.pX + ((size_t)rnd * K + k) * d, *pout = A.pout + (size_t)rnd * ((size_t)K * (d + 1));
             for (int i = tid; i < d; i += HM_NT) { pX[i] = X[i]; pout[K + kd + i] = g[i]; }
             if (tid == 0) pout[k] = lpt;
         }
-        const double nbad = hm_apply_R<KPAD, RES, HM_NT, NVM>(F, L, g, d, flip, [&](int i) -> double & { return wt[i]; });
+        const double nbad = hm_apply_R<KPAD, RES, HM_NT, NVM>(F, L, g, d, flip, [&](int i) -> double & { return wt[i]; }, FUSED && staged);
         staged = true;
         // ---- the pending kick
         if (S.i == HM_START) {
@@ -226,11 +248,13 @@ __device__ __forceinline__ void hm_step_body(const Args &A) {
             hm_apply_L<KPAD, RES, HM_NT, NVM>(F, L, X, eps, vv0, staged, d, flip, [&](int i) -> const double & { return v[i]; }, [&](int i) { return base[i]; },
                                               [&](double vv) { if (open) S.H0 = -S.lp + 0.5 * vv; });
         }
+        if constexpr (FUSED) staged = true;
     }
-    if (A.record && A.round >= 0) {
-        double *pv = A.pv + ((size_t)A.round * K + k) * d;
+    if (A.record && (FUSED ? round : A.round) >= 0) {
+        double *pv = A.pv + ((size_t)(FUSED ? round : A.round) * K + k) * d;
         for (int i = tid; i < d; i += HM_NT) pv[i] = v[i];
     }
+    if constexpr (FUSED) { C = {S, eps, round + 1, flip, staged}; return; }
     __syncthreads();                                     // every thread has read S before thread 0 writes
     if (tid == 0) A.st[k] = S;
     if constexpr (CHEES) {
@@ -243,6 +267,13 @@ __device__ __forceinline__ void hm_step_body(const Args &A) {
             if (S.i == HM_OPEN && S.t >= A.t_end) A.C->fin_round = A.pround;
         }
     }
+}
+
+// one launch of the step kernels: one round on the chain's state in HBM
+template <int KPAD, bool RES, int MODE, class Args>
+__device__ __forceinline__ void hm_step_body(const Args &A) {
+    HmCarry none;                                        // (not read, not written)
+    hm_round<KPAD, RES, MODE, HM_TG_NONE>(A, none);
 }
 
 #ifndef PF_CHAIN_METRIC_TU             // (hmc_metric_kernel.hip takes the body and hm_args from this file and defines its own kernels)

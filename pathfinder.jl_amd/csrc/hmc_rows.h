@@ -11,6 +11,10 @@
 #define HM_NW (HM_NT / 64)
 #define HM_LDS_RES (150 * 1024)        // most dynamic LDS the staged factor rows may take (of 160 KB, beside the kernels' static buffers)
 
+// The most rounds one launch of the fused static-HMC kernel (hmc_fused_kernel.hip) makes: a longer call is several launches that re-enter
+// from the chains' resident state.  Bounds the time one kernel holds the GPU; the test hook PFMI_HMC_FUSED_ROUNDS overrides it.
+#define HM_FUSED_ROUNDS 1024
+
 // the staged factor rows of one chain fit in LDS beside the reduction buffers
 inline bool pf_hmc_resident(int d, int kpad) { return (size_t)d * kpad * sizeof(double) <= (size_t)HM_LDS_RES; }
 
@@ -116,20 +120,29 @@ struct HmLds {
 #define HM_STAGED_ROWS extern __shared__ __attribute__((aligned(32))) double sVh[]
 
 // wt = R g: z = s . g, w = Vh'z (one block reduction), tv = T'w, y = z - Vh tv, head <- V head.  wt(i) is the caller's element i of the
-// result (double &).  Returns the number of non-finite entries of g.  With RES this pass stages the rows.
+// result (double &).  Returns the number of non-finite entries of g.  With RES this pass stages the rows, unless an earlier pass of the
+// launch has (staged: the fused kernel, hmc_fused_kernel.hip, makes many rounds in one launch and stages once).
 template <int KPAD, bool RES, int NT, int NRED, class Lds, class Wt>
-__device__ __forceinline__ double hm_apply_R(const HmFactor &F, Lds &L, const double *g, int d, int &flip, Wt wt) {
+__device__ __forceinline__ double hm_apply_R(const HmFactor &F, Lds &L, const double *g, int d, int &flip, Wt wt, bool staged = false) {
     HM_STAGED_ROWS;
     constexpr int NVM = KPAD + 4;                        // KPAD sums + one rider, padded to the multiple of 4 pf_block_sum_mv takes
     const int tid = threadIdx.x;
     double w[NVM];
 #pragma unroll
     for (int j = 0; j < NVM; ++j) w[j] = 0.0;
-    for (int i = tid; i < d; i += NT) {
-        const double gi = g[i], zi = F.sqa[i] * gi;
-        if (RES) hm_row_axpy<KPAD, NVM, true>(F.gVh + (size_t)i * KPAD, sVh + (size_t)i * KPAD, zi, w);
-        else hm_row_axpy<KPAD, NVM, false>(F.gVh + (size_t)i * KPAD, nullptr, zi, w);
-        w[KPAD] += isfinite(gi) ? 0.0 : 1.0;
+    const double *rows = RES ? sVh : F.gVh;
+    if (RES && !staged) {
+        for (int i = tid; i < d; i += NT) {
+            const double gi = g[i], zi = F.sqa[i] * gi;
+            hm_row_axpy<KPAD, NVM, true>(F.gVh + (size_t)i * KPAD, sVh + (size_t)i * KPAD, zi, w);
+            w[KPAD] += isfinite(gi) ? 0.0 : 1.0;
+        }
+    } else {
+        for (int i = tid; i < d; i += NT) {
+            const double gi = g[i], zi = F.sqa[i] * gi;
+            hm_row_axpy<KPAD, NVM, false>(rows + (size_t)i * KPAD, nullptr, zi, w);
+            w[KPAD] += isfinite(gi) ? 0.0 : 1.0;
+        }
     }
     pf_block_sum_mv<NVM, NRED>(w, L.red, flip);
     const double nbad = w[KPAD];
@@ -140,7 +153,6 @@ __device__ __forceinline__ double hm_apply_R(const HmFactor &F, Lds &L, const do
         L.sTv[tid] = s;
     }
     __syncthreads();
-    const double *rows = RES ? sVh : F.gVh;
     for (int i = tid; i < d; i += NT) {
         const double y = hm_row_sub<KPAD>(rows + (size_t)i * KPAD, L.sTv, F.sqa[i] * g[i]);
         if (i < KPAD) L.sHead[i] = y; else wt(i) = y;

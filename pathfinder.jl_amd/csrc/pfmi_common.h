@@ -432,6 +432,9 @@ size_t pf_hmc_chain_bytes();
 int32_t pf_launch_hmc_init(pfmi_ctx *c, hipStream_t s);
 int32_t pf_launch_hmc_step(pfmi_ctx *c, int64_t round, hipStream_t s);      // round < 0: open the next trajectory only (no closure output is read)
 int32_t pf_hmc_dead_flags(pfmi_ctx *c, std::vector<int32_t> &dead);
+// hmc_fused_kernel.hip: static HMC on a built-in target, `ntrips` rounds from round `round` in ONE launch (round -1: the opening trip of a
+// CONTINUE, which evaluates nothing); the chains' state and buffers are those of pf_launch_hmc_step
+int32_t pf_launch_hmc_fused(pfmi_ctx *c, int64_t round, int ntrips, hipStream_t s);
 // nuts_kernel.hip
 size_t pf_nuts_chain_bytes();
 int pf_nuts_vec_slots(int max_depth);

@@ -548,6 +548,33 @@ class Engine:
         flags = (self.HMC_CONTINUE if cont else 0) | (self.HMC_RECORD_PATH if record_path else 0)
         self._chain_enqueue("hmc", points, x0, seeds, step_size, nleapfrog, ntransitions, flags)
 
+    def hmc_fused_enqueue(self, points, x0, seeds, step_size, nleapfrog, ntransitions, nwarmup=0, target_accept=0.8, cont=False,
+                          record_path=False):
+        """hmc_enqueue (nwarmup = 0) or hmc_adapt_enqueue (nwarmup >= 1: cont and record_path must be False) for an engine whose target
+        is BUILT IN (Gaussian family, funnel): logp and its gradient are evaluated inside the chain kernel, one workgroup per chain
+        loops over the rounds of a launch (include/pfmi.h: pfmi_hmc_fused_enqueue).  hmc_wait, hmc_get, hmc_path, adapt_get and
+        chain_diagnostics serve the run; hmc_stats reports its evaluations and 0 closure columns.  Does not wait."""
+        points = np.ascontiguousarray(points, dtype=np.int64)
+        K = len(points)
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
+        eps = np.ascontiguousarray(np.broadcast_to(np.asarray(step_size, dtype=np.float64), (K,)))
+        assert seeds.shape == (K,)
+        x0p = None
+        if x0 is not None:
+            x0 = np.asfortranarray(x0, dtype=np.float64)
+            assert x0.shape == (self.d, K), (x0.shape, self.d, K)
+            x0p = _d(x0)
+        flags = (self.HMC_CONTINUE if cont else 0) | (self.HMC_RECORD_PATH if record_path else 0)
+        check(self.L.pfmi_hmc_fused_enqueue(self.ctx, K, points.ctypes.data_as(_i64p), x0p, seeds.ctypes.data_as(C.POINTER(C.c_uint64)), _d(eps),
+                                            int(nleapfrog), int(nwarmup), int(ntransitions), float(target_accept), flags))
+        self._hmc = (K, int(ntransitions))
+        self._chees = None
+        if nwarmup:
+            self._adapt, self._metric = (K, int(nwarmup)), None
+        elif not cont:
+            self._adapt = self._metric = None
+        self.hmc_runs += 1
+
     # ---- chain diagnostics (include/pfmi.h: pfmi_chain_diagnostics) ---------------------------------------------------------------
     CHAIN_SRC_HMC, CHAIN_SRC_HOST, CHAIN_WITH_LP = 0, 1, 1
     CHAIN_KEYS = ("mean", "sd", "mcse_mean", "ess_mean", "ess_bulk", "ess_tail", "rhat")

@@ -6,7 +6,9 @@ The reference's worked example docs/src/examples/initializing-hmc.md, third way:
 where the fits already are.  `hmc`: a fixed number of leapfrog steps per transition, Metropolis correction, full momentum refresh.
 `nuts`: multinomial NUTS, trees of at most 2^max_depth - 1 leapfrog steps.  Both share one driver (`_run`): the same starts, metric,
 seeds and step-size adaptation.  The target must be a device closure with a gradient (DeviceCallbackTarget(..., grad_fn=...),
-TorchDeviceTarget(..., grad=...)); one engine only.
+TorchDeviceTarget(..., grad=...)); one engine only.  On a BUILT-IN target (t_iso, t_diag, t_lowrank, t_funnel, any GaussTarget /
+FunnelTarget) `hmc` takes the fused route instead (pfmi_hmc_fused_enqueue): the chain kernel evaluates logp and its gradient itself and
+loops over a run's rounds in one launch.  All three modes of `hmc` run there; `nuts`, `chees` and adapt_metric=True do not.
 
 The example's second way, "initialise a metric adaptation" from the fit, is adapt="device" with adapt_metric=True (include/pfmi.h:
 pfmi_hmc_adapt_metric_enqueue): the warm-up also learns a per-coordinate scale c of every chain in Stan's windows, in the coordinates
@@ -20,6 +22,7 @@ import numpy as np
 
 from .core import Engine
 from .hostrng import HostRNG
+from .targets import KIND_FUNNEL, KIND_GAUSS
 
 # Nesterov dual averaging of the step size (Hoffman & Gelman 2014, Algorithm 5 and section 3.2.1: their constants)
 DA_GAMMA, DA_T0, DA_KAPPA = 0.05, 10.0, 0.75
@@ -183,16 +186,28 @@ class NUTSResult(HMCResult):
         return "\n".join(lines)
 
 
-def _chains(name, result, nchains, rng, check_param=None):
+def _builtin(target):
+    """the engine's target is one the library evaluates itself (Gaussian family, funnel): static HMC runs fused"""
+    return getattr(target, "kind", None) in (KIND_GAUSS, KIND_FUNNEL)
+
+
+def _chains(name, result, nchains, rng, check_param=None, adapt_metric=False):
     """what every sampler here starts from: (engine, starts x0 (d, nchains), fit points, seeds) of `result`; check_param: the sampler's
     own argument check, made where it has always been made (after the engine's and the target's, before nchains')"""
     eng, starts, pts, token = _starts_and_points(result)
     if eng is None:
         raise ValueError(f"pfmi.{name} needs a result whose fits are still on an engine")
     eng.check_token(token, f"pfmi.{name}")
-    if not getattr(eng.target, "has_device_gradient", False):
-        raise ValueError(f"pfmi.{name} needs a device closure target with a gradient (built-in targets, host closures and device closures "
-                         "without a gradient are not supported)")
+    if _builtin(eng.target):
+        if name != "hmc":
+            raise ValueError(f"pfmi.{name} needs a device closure target with a gradient; on a built-in target static HMC is available "
+                             "(pfmi.hmc: fixed step, adapt=\"windows\" and adapt=\"device\")")
+        if adapt_metric:
+            raise ValueError("pfmi.hmc: adapt_metric=True needs a device closure target with a gradient; on a built-in target static HMC is "
+                             "available with the fitted metric itself (adapt_metric=False)")
+    elif not getattr(eng.target, "has_device_gradient", False):
+        raise ValueError(f"pfmi.{name} needs a device closure target with a gradient (host closures and device closures without a gradient "
+                         "are not supported; on built-in targets static HMC is available through pfmi.hmc)")
     if check_param is not None:
         check_param()
     nchains = starts.shape[1] if nchains is None else int(nchains)
@@ -209,20 +224,24 @@ def _run(name, result, ndraws, nchains, nwarmup, step_size, param, rng, target_a
         if is_nuts and not 1 <= int(param) <= 10:
             raise ValueError("max_depth must be in 1 .. 10")
 
-    eng, x0, pts, seeds = _chains(name, result, nchains, rng, check_param)
+    eng, x0, pts, seeds = _chains(name, result, nchains, rng, check_param, adapt_metric)
     d, nchains = x0.shape
+    fused = _builtin(eng.target)                         # (static HMC only: _chains has refused everything else)
     auto = isinstance(step_size, str)
     if auto and step_size != "auto":
         raise ValueError('step_size must be a number, an array of nchains numbers or "auto"')
     eps = np.full(nchains, d ** -0.25) if auto else np.broadcast_to(np.asarray(step_size, dtype=np.float64), (nchains,)).copy()
-    enqueue, wait = (eng.nuts_enqueue, eng.nuts_wait) if is_nuts else (eng.hmc_enqueue, eng.hmc_wait)
+    enqueue, wait = (eng.nuts_enqueue, eng.nuts_wait) if is_nuts else (eng.hmc_fused_enqueue if fused else eng.hmc_enqueue, eng.hmc_wait)
     warm = scale = None
     if _check_adapt(adapt, auto, int(nwarmup), adapt_metric):
-        if adapt_metric:
-            aenq = eng.nuts_adapt_metric_enqueue if is_nuts else eng.hmc_adapt_metric_enqueue
+        if fused:
+            eng.hmc_fused_enqueue(pts, x0, seeds, eps, param, int(ndraws), int(nwarmup), target_accept)
         else:
-            aenq = eng.nuts_adapt_enqueue if is_nuts else eng.hmc_adapt_enqueue
-        aenq(pts, x0, seeds, eps, param, int(nwarmup), int(ndraws), target_accept)
+            if adapt_metric:
+                aenq = eng.nuts_adapt_metric_enqueue if is_nuts else eng.hmc_adapt_metric_enqueue
+            else:
+                aenq = eng.nuts_adapt_enqueue if is_nuts else eng.hmc_adapt_enqueue
+            aenq(pts, x0, seeds, eps, param, int(nwarmup), int(ndraws), target_accept)
         wait()
         got, warm = eng.hmc_get(), eng.adapt_get()
         eps = warm.pop("step_size")
@@ -267,7 +286,10 @@ def hmc(result, ndraws, *, nchains=None, nwarmup=0, step_size="auto", nleapfrog=
     only): the device updates every chain's step size after every warm-up transition (include/pfmi.h: pfmi_hmc_adapt_enqueue); warm-up and
     sampling are ONE enqueue, and the result's `warmup` holds the traces.  adapt_metric=True (adapt="device" only): the warm-up also adapts
     a per-coordinate scale of every chain on its fit's factor in Stan's windows (pfmi_hmc_adapt_metric_enqueue; no window below 20 warm-up
-    transitions); `metric_scale` is the scale the sampling used, `warmup` also holds window_ends and scale_trace."""
+    transitions); `metric_scale` is the scale the sampling used, `warmup` also holds window_ends and scale_trace.
+
+    On a built-in target (pfmi.t_lowrank, t_diag, t_iso, t_funnel) the run takes the fused route (pfmi_hmc_fused_enqueue) in all three
+    modes -- fixed step, adapt="windows", adapt="device" -- and returns the same HMCResult; adapt_metric=True raises ValueError there."""
     return _run("hmc", result, ndraws, nchains, nwarmup, step_size, nleapfrog, rng, target_accept, window, adapt, adapt_metric)
 
 
