@@ -94,7 +94,7 @@ int32_t pfmi_create(int32_t device, pfmi_ctx **out);
 int32_t pfmi_destroy(pfmi_ctx *ctx);   /* communicators that hold ctx are closed first: any finaliser order is safe */
 int32_t pfmi_sync(pfmi_ctx *ctx);
 /* Test / tuning hooks (kernel selection PFMI_ELBO_KERNEL / PFMI_FIT_KERNEL / PFMI_HISTORY_KERNEL / PFMI_PSIS_KERNEL / PFMI_QF_NO_TAIL,
- * PFMI_DEVCB_CHUNK_MB, PFMI_LBFGS_REJECT_EVERY, PFMI_HMC_FUSED_ROUNDS, the collective path's PFMI_RCCL_LIB / PFMI_COMM_ALLOW_SHARED_GPU / PFMI_COMM_FORCE_RCCL;
+ * PFMI_DEVCB_CHUNK_MB, PFMI_LBFGS_REJECT_EVERY, PFMI_HMC_FUSED_ROUNDS, PFMI_NUTS_FUSED_ROUNDS, the collective path's PFMI_RCCL_LIB / PFMI_COMM_ALLOW_SHARED_GPU / PFMI_COMM_FORCE_RCCL;
  * INTEGRATION.md section 3).  A hook is read from this explicit table, or from the environment variable of the same name ONLY when
  * the process was started with PFMI_DEBUG_HOOKS=1: a production process is never re-configured by a stray environment variable.
  * value == NULL unsets: the hook is then read from the environment again (under PFMI_DEBUG_HOOKS=1) or is off.  Process-global; set hooks before other threads use the library.  No reference counterpart. */
@@ -140,7 +140,8 @@ int32_t pfmi_debug_set(const char *key, const char *value);
  * "woodbury_diag:<KPAD>": the kernel behind pfmi_woodbury_diag.
  * The fused static-HMC kernel (pfmi_hmc_fused_enqueue) has the stage name "hmc_fused" and, one count per kernel launch,
  * "hmc_fused:<KPAD>:<res|stream>:<f|g0|g8|g16>": column padding KPAD (4 .. 64), the chain's factor rows staged in LDS or streamed
- * from HBM, and the target -- the funnel, or the Gaussian family with rank padding 0, 8 or 16. */
+ * from HBM, and the target -- the funnel, or the Gaussian family with rank padding 0, 8 or 16.  The fused NUTS kernel
+ * (pfmi_nuts_fused_enqueue) likewise: stage "nuts_fused", counters "nuts_fused:<KPAD>:<res|stream>:<f|g0|g8|g16>". */
 int32_t pfmi_timer_start(pfmi_ctx *ctx);
 int32_t pfmi_timer_stop(pfmi_ctx *ctx, double *milliseconds);
 int32_t pfmi_profile(pfmi_ctx *ctx, int32_t enable);
@@ -503,12 +504,42 @@ int32_t pfmi_nuts_adapt_enqueue(pfmi_ctx *ctx, int32_t K, const int64_t *points,
  * Errors are those of pfmi_hmc_enqueue / pfmi_hmc_adapt_enqueue, in their order and with the drain-on-error rule, except that
  * PFMI_ERR_UNSUPPORTED is returned for any callback target (a DEVICE_CALLBACK target with a gradient closure runs through pfmi_hmc_enqueue)
  * and for a staged scale (pfmi_chain_scale_set: the metric kernels are not fused).
- * Out of scope: NUTS, ChEES, the metric windows and scaled chains on built-in targets; pfmi_hmc_enqueue, pfmi_nuts_enqueue, the adaptive
- * enqueues and pfmi_chees_enqueue are unchanged and still refuse a built-in target.
+ * NUTS on a built-in target is pfmi_nuts_fused_enqueue below.  Out of scope: ChEES, the metric windows and scaled chains on built-in
+ * targets; pfmi_hmc_enqueue, pfmi_nuts_enqueue, the adaptive enqueues and pfmi_chees_enqueue are unchanged and still refuse a built-in target.
  * Stage name "hmc_fused"; plan counters "hmc_fused:<KPAD>:<res|stream>:<f|g0|g8|g16>" (pfmi_kernel_time). */
 int32_t pfmi_hmc_fused_enqueue(pfmi_ctx *ctx, int32_t K, const int64_t *points, const double *x0, const uint64_t *seeds,
                                const double *step_size, int32_t nleapfrog, int64_t nwarmup, int64_t ntransitions, double target_accept,
                                int32_t flags);
+/* ---- NUTS on the built-in targets: whole runs in one persistent kernel ------------------------------------------------------- */
+/* pfmi_nuts_enqueue and pfmi_nuts_adapt_enqueue for a ctx whose target is PFMI_TARGET_GAUSS (any rank) or PFMI_TARGET_FUNNEL.  One
+ * workgroup per chain loops over TRIPS: it evaluates logp and its gradient at the trial point in the kernel, then makes the NUTS round
+ * of pfmi_nuts_enqueue (one leaf of the tree, its checkpoints and decisions, the end of a transition, the opening of the next and the
+ * drift to the next trial point), with the chain's factor rows staged in LDS once per launch.  A chain builds its trees at its own pace
+ * and leaves the launch when it has made its transitions.  No launch makes more than 1024 trips per chain (csrc/hmc_rows.h:
+ * HM_FUSED_ROUNDS; the hook PFMI_NUTS_FUSED_ROUNDS of pfmi_debug_set overrides it): a longer call is several launches that re-enter from
+ * the chains' resident state -- in mid-tree too -- and give the same bits whatever the cut.  No kernel waits for another.
+ * nwarmup == 0: the transition of pfmi_nuts_enqueue with the in-kernel value and gradient in the closure's place: the same normals,
+ * directions, uniforms (stream for stream, counter for counter), divergence rule and rows; flags: PFMI_NUTS_CONTINUE,
+ * PFMI_NUTS_RECORD_PATH; target_accept is ignored.  The opening trip of a CONTINUE evaluates nothing and writes no path row.
+ * nwarmup >= 1: the run of pfmi_nuts_adapt_enqueue; flags must be 0 and target_accept in (0, 1).  nwarmup < 0: PFMI_ERR_ARG.
+ * The device decides how many launches a call takes, so they are pumped like the closure route's rounds: pfmi_nuts_enqueue's window of
+ * launches ahead of the last progress word read (launch << 32 | chains still running), at most
+ * ceil(((fresh ? 1 : 0) + (nwarmup + ntransitions) (2^max_depth - 1)) / cap) launches; a run that fits one launch is exactly one.
+ * The run is a NUTS run in the same buffers and layouts: pfmi_nuts_wait, pfmi_nuts_pump, pfmi_nuts_get_stats, pfmi_nuts_get_path,
+ * pfmi_hmc_get, pfmi_hmc_draws_dev, pfmi_adapt_get and pfmi_chain_diagnostics(PFMI_CHAIN_SRC_HMC) serve it.  pfmi_nuts_stats reports
+ * rounds = the most trips a chain made (a fresh call: 1 + the largest per-chain sum of n_leapfrog) and closure_columns = 0.  A path row
+ * is a TRIP of the chain, not a launch: pfmi_nuts_get_path takes rows [0, rounds), the closure_out rows hold the in-kernel value and
+ * gradient, and a chain's rows beyond its own trips keep event t = -1.
+ * Errors are those of pfmi_nuts_enqueue / pfmi_nuts_adapt_enqueue, in their order and with the drain-on-error rule, except that
+ * PFMI_ERR_UNSUPPORTED is returned for any callback target (a DEVICE_CALLBACK target with a gradient closure runs through
+ * pfmi_nuts_enqueue) and for a staged scale or resident scaled chains (the metric kernels are not fused).  PFMI_NUTS_CONTINUE on the
+ * chains of another sampler -- pfmi_hmc_fused_enqueue's included -- is PFMI_ERR_STATE, with max_depth above the chains' PFMI_ERR_ARG.
+ * Fused and closure NUTS calls never meet on the same resident chains: replacing the target forgets the chains.
+ * Out of scope: ChEES (its chains talk to each other), the metric windows and scaled chains on built-in targets.
+ * Stage name "nuts_fused"; plan counters "nuts_fused:<KPAD>:<res|stream>:<f|g0|g8|g16>", one count per launch (pfmi_kernel_time). */
+int32_t pfmi_nuts_fused_enqueue(pfmi_ctx *ctx, int32_t K, const int64_t *points, const double *x0, const uint64_t *seeds,
+                                const double *step_size, int32_t max_depth, int64_t nwarmup, int64_t ntransitions, double target_accept,
+                                int32_t flags);
 /* The last adaptive run: step_size [K] the one its sampling transitions used (a later plain CONTINUE with step sizes of the caller's own
  * does not change what is reported here); eps_trace, accept_trace [K][W] the step size warm-up transition
  * t used and its a_t; divergent, n_leapfrog int32 [K][W]; status [K] (PFMI_ADAPT_*).  Any may be NULL.  Waits for the stream (a NUTS run

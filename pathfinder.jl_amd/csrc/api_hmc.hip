@@ -166,6 +166,7 @@ int32_t chain_begin(pfmi_ctx *c, const ChainKind &S, const ChainCall &A, int64_t
 
 // Issues the rounds a run may have in flight: the gradient closure on all K trial points, then the sampler's launches that consume its answer.
 // At most PF_CHAIN_WINDOW rounds ahead of the last one whose progress word the host has read, never more than the hard cap.  Sets H.finished.
+// A pump without a closure stage (closure_stage null: fused NUTS on a built-in target, api_nuts_fused.hip) issues its launches alone.
 int32_t chain_issue_rounds(pfmi_ctx *c, const ChainPump &P) {
     HmcState &H = c->hmc;
     const TargetDev &Tg = c->target;
@@ -175,10 +176,12 @@ int32_t chain_issue_rounds(pfmi_ctx *c, const ChainPump &P) {
     if (round == H.seen) H.word_low = active;
     if (round == H.seen && active == 0) H.finished = true;
     while (!H.finished && H.issued < H.max_rounds && H.issued - H.seen < PF_CHAIN_WINDOW) {
-        pf_kernel_begin(c);
-        Tg.grad_fn(c->hm_X.as<double>(), c->d, H.K, c->hm_out.as<double>(), (void *)c->stream, Tg.grad_user);
-        pf_kernel_end(c, P.closure_stage(H));
-        H.columns += H.K;
+        if (P.closure_stage) {
+            pf_kernel_begin(c);
+            Tg.grad_fn(c->hm_X.as<double>(), c->d, H.K, c->hm_out.as<double>(), (void *)c->stream, Tg.grad_user);
+            pf_kernel_end(c, P.closure_stage(H));
+            H.columns += H.K;
+        }
         const int64_t prow = H.issued++;
         PF_TRY(P.round(c, H.issued, prow));
     }

@@ -78,7 +78,10 @@ int32_t chain_begin(pfmi_ctx *c, const ChainKind &S, const ChainCall &A, int64_t
 // The one pump of the samplers whose round count the device decides (NUTS, ChEES): `closure_stage` names the closure's stage of the run,
 // `round` issues what follows the closure in a round -- the launches that consume its answer, with their own stage names -- as round number
 // `round` (published with the progress word c->nt_status: round << 32 | low, low = 0 once every chain is idle) and path row `prow`.
+// closure_stage null: a pump without a closure (nuts_fused_pump, api_nuts_fused.hip): a round is `round` alone and no column is counted.
 struct ChainPump { const char *name; const char *(*closure_stage)(const HmcState &); int32_t (*round)(pfmi_ctx *c, int64_t round, int64_t prow); };
+const ChainPump &nuts_fused_pump();                      // api_nuts_fused.hip: a round is one launch of up to HmcState::fused_cap evaluations
+int32_t nuts_drain(pfmi_ctx *c);                         // api_nuts.hip: pumps the NUTS run on the ctx (closure rounds or fused launches) to its end
 int32_t chain_issue_rounds(pfmi_ctx *c, const ChainPump &P);            // what may be in flight; sets H.finished
 int32_t chain_pump_pass(pfmi_ctx *c, const ChainPump &P, int32_t *finished);      // one pass: never blocks
 int32_t chain_drain(pfmi_ctx *c, const ChainPump &P);                   // pump to the end

@@ -17,7 +17,9 @@ static int32_t nuts_round(pfmi_ctx *c, int64_t round, int64_t prow) {
     return PFMI_OK;
 }
 static const ChainPump NUTS_PUMP = {"nuts", nuts_closure_stage, nuts_round};
-static int32_t nuts_drain(pfmi_ctx *c) { return chain_drain(c, NUTS_PUMP); }
+// the pump of the NUTS run on the ctx: a fused run's rounds are launches without a closure (api_nuts_fused.hip)
+static const ChainPump &nuts_pump_of(const HmcState &H) { return H.fused ? nuts_fused_pump() : NUTS_PUMP; }
+int32_t nuts_drain(pfmi_ctx *c) { return chain_drain(c, nuts_pump_of(c->hmc)); }
 
 static const ChainKind NUTS_KIND = {"nuts", "NUTS", "hmc", 1};
 
@@ -50,6 +52,7 @@ int32_t nuts_enqueue(pfmi_ctx *c, int32_t K, const int64_t *points, const double
     H.nleap = 0;
     H.max_depth = max_depth;
     if (!cont) H.md_alloc = max_depth;                    // (a CONTINUE never asks for more checkpoints than the chains were given)
+    H.fused = false;
     H.issued = 0; H.seen = 0; H.max_rounds = rounds; H.finished = false;
     __atomic_store_n(c->nt_status, (int64_t)K, __ATOMIC_RELEASE);               // round 0: every chain running
     PF_HIP(hipMemsetAsync(c->nt_ctr.p, 0, sizeof(int32_t) * 2, c->stream));
@@ -74,7 +77,7 @@ int32_t pfmi_nuts_pump(pfmi_ctx *c, int32_t *finished) {
     PF_CHECK(c != nullptr && finished != nullptr, PFMI_ERR_ARG, "nuts_pump: null argument");
     PF_CHECK(c->hmc.have && c->hmc.kind == 1, PFMI_ERR_STATE, "nuts_pump: no pfmi_nuts_enqueue outstanding");
     PF_HIP(hipSetDevice(c->device));
-    return chain_refused(c, chain_pump_pass(c, NUTS_PUMP, finished));  // a failed pass ends the run: what is in flight is drained
+    return chain_refused(c, chain_pump_pass(c, nuts_pump_of(c->hmc), finished));  // a failed pass ends the run: what is in flight is drained
 }
 
 int32_t pfmi_nuts_wait(pfmi_ctx *c) {
@@ -109,8 +112,13 @@ int32_t pfmi_nuts_get_path(pfmi_ctx *c, int64_t round0, int64_t nrounds, double 
     const HmcState &H = c->hmc;
     PF_CHECK(H.have && H.record && H.kind == 1, PFMI_ERR_STATE, "nuts_get_path: the last pfmi_nuts_enqueue did not run with PFMI_NUTS_RECORD_PATH");
     PF_CHECK(H.finished, PFMI_ERR_STATE, "nuts_get_path: the run has rounds to go (pfmi_nuts_wait)");
-    PF_CHECK(round0 >= 0 && nrounds >= 0 && round0 + nrounds <= H.issued, PFMI_ERR_ARG, "nuts_get_path: rounds [%lld, %lld) outside [0, %lld)",
-             (long long)round0, (long long)(round0 + nrounds), (long long)H.issued);
+    int64_t bound = H.issued;                             // a row per round issued; a fused run: per trip of the chain that made the most
+    if (H.fused) {
+        std::vector<int32_t> dead;
+        PF_TRY(pf_nuts_chain_flags(c, dead, &bound));
+    }
+    PF_CHECK(round0 >= 0 && nrounds >= 0 && round0 + nrounds <= bound, PFMI_ERR_ARG, "nuts_get_path: rounds [%lld, %lld) outside [0, %lld)",
+             (long long)round0, (long long)(round0 + nrounds), (long long)bound);
     PF_TRY(chain_path_download(c, round0, nrounds, X, closure_out, v));
     if (events)
         PF_TRY(pf_download(c, events, c->nt_pev.as<pfmi_nuts_event>() + (size_t)round0 * H.K, sizeof(pfmi_nuts_event) * (size_t)H.K * (size_t)nrounds));

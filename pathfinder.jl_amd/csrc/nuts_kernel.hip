@@ -6,7 +6,7 @@
 //
 // What a step shares with static HMC is hmc_rows.h: the R pass (hm_apply_R), the thread count, the LDS budget, the launch helper and the end
 // of a warm-up transition.  The L pass is static HMC's statement for statement but stays written out here (see the rule for the base
-// addresses in nt_step_body).
+// addresses in nt_round).  pf_nuts_fused_kernel (nuts_fused_kernel.hip) enters the same round once per trip of its loop.
 //
 // As in hmc_kernel.hip the run is cut into ROUNDS: one call of the closure on all K columns of X, then one launch of pf_nuts_step_kernel (one
 // workgroup per chain), which consumes the evaluation -- exactly ONE leapfrog step of every running chain -- and writes the next trial
@@ -37,7 +37,9 @@
 // the two progress counters.  A chain's output depends on nothing but its own inputs.
 #include "pfmi_common.h"
 #include "hmc_rows.h"
+#include "hmc_target.h"
 #include <float.h>
+#include <type_traits>
 
 #define NT_MAXD 10                     // deepest tree: 2^10 - 1 leaves per transition
 #define NT_NDOT 24                     // |v|^2, two dot products per checkpoint, two of the full tree, padded to a multiple of 4
@@ -112,9 +114,33 @@ __global__ __launch_bounds__(HM_NT) void pf_nuts_init_kernel(NtArgs A) {
 // metric window ends with hm_metric_end.  Plain runs (which may record their path) and adaptive runs share it.
 enum { NT_PLAIN = 0, NT_WARM = 1, NT_METRIC = 2 };
 
-template <int KPAD, bool RES, int MODE, class Args>
-__device__ __forceinline__ void nt_step_body(const Args &A_) {
-    constexpr bool ADAPT = MODE != NT_PLAIN, METRIC = MODE == NT_METRIC;
+// progress of a launch, by thread 0 of every workgroup: the last one publishes (A.round << 32 | chains still running)
+template <class Args>
+__device__ __forceinline__ void nt_publish(const Args &A, bool running, int K) {
+    if (threadIdx.x == 0) {
+        if (running) __hip_atomic_fetch_add(A.ctr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __threadfence();
+        const int ticket = __hip_atomic_fetch_add(A.ctr + 1, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+        if (ticket == K - 1) {
+            const int active = __hip_atomic_load(A.ctr, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
+            A.ctr[0] = 0; A.ctr[1] = 0;
+            __hip_atomic_store(A.h_status, (int64_t)((A.round << 32) | (int64_t)active), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+}
+
+// ONE ROUND (nt_round) is what a launch of the step kernels does.  TG == HM_TG_NONE (the step kernels): the round loads the chain's scalars,
+// consumes the closure's output, stores the state and takes the launch's ticket.  TG a built-in target (pf_nuts_fused_kernel,
+// nuts_fused_kernel.hip: MODE NT_WARM, which there may record its path): the kernel enters the round once per TRIP of its loop; the round
+// evaluates the target itself where a step kernel reads the closure's output (hm_target_eval, hmc_target.h; the opening trip of a CONTINUE
+// evaluates nothing), and the CALLER loads the scalars before the first trip, stores S after the last and takes the ticket.  What a trip
+// carries to the next is NtCarry: S, the step size (a warm-up transition's end changes it), the seed and fit point, `trip` (evaluations the
+// call has made: the row of the recorded path, and + 1 the round number of the closure route), the ping-pong side `flip` of the reduction
+// buffers, `staged` (the factor rows are in LDS: staged ONCE per launch) and `reopen` (this trip is the opening one of a CONTINUE).
+struct NtCarry { NtChain S; double eps; uint64_t seed; int64_t trip; int pt, flip; bool staged, reopen; };
+template <int KPAD, bool RES, int MODE, int TG, class Args>
+__device__ __forceinline__ void nt_round(const Args &A_, NtCarry &C) {
+    constexpr bool ADAPT = MODE != NT_PLAIN, METRIC = MODE == NT_METRIC, FUSED = TG != HM_TG_NONE;
     // The arguments are read where they are used, through the kernel-argument segment itself (A_ is the kernel's first and only entry): as a
     // by-value parameter all 80 dwords are loaded on entry and stay in scalar registers until their one use.
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -124,18 +150,22 @@ __device__ __forceinline__ void nt_step_body(const Args &A_) {
 #endif
     // an adaptive run records no path (its flags are 0): the warm kernel carries none of that code and none of its addresses
     auto rec = [&]() -> int {
-        if constexpr (MODE == NT_WARM) return 0;
+        if constexpr (MODE == NT_WARM && !FUSED) return 0;
         else return A.record;
     };
     constexpr int NVM = KPAD + 4;                        // KPAD sums + one rider (pf_block_sum_mv takes multiples of 4)
-    constexpr int NRED = NVM > NT_NDOT ? NVM : NT_NDOT;
+    constexpr int NOPS = NVM > NT_NDOT ? NVM : NT_NDOT;  // FUSED: or the evaluation's reduction, if that is wider
+    constexpr int NRED = FUSED && HmTargetShape<TG>::NV > NOPS ? HmTargetShape<TG>::NV : NOPS;
     // (HmLds of hmc_rows.h with the vectors first: with the reduction buffers first pf_nuts_warm_kernel<12, true> moves a seventh scalar
     // register into a lane)
     struct NtLds {
         alignas(16) double sTv[KPAD], sZ[KPAD], sHead[KPAD];
         alignas(16) double red[2 * HM_NW * NRED];
     };
-    __shared__ NtLds L;
+    struct NtTargetLds : NtLds {                         // FUSED: G's copy behind them (hm_target_stage)
+        alignas(16) double sG[HmTargetShape<TG>::NG];
+    };
+    __shared__ std::conditional_t<FUSED, NtTargetLds, NtLds> L;
     const int k = blockIdx.x, tid = threadIdx.x, d = A.d, K = A.K;
     int flip = 0;
     // the chain's scalars, its step size, seed and fit point go through LDS: the values (and the factor's addresses, which depend on the
@@ -144,12 +174,21 @@ __device__ __forceinline__ void nt_step_body(const Args &A_) {
     __shared__ double sEps;
     __shared__ uint64_t sSeed;
     __shared__ int sPt;
-    if (tid == 0) { sS = A.st[k]; sEps = A.eps[k]; sSeed = A.seeds[k]; sPt = A.pts[k]; }
-    __syncthreads();
-    NtChain S = sS;
+    NtChain S;
+    if constexpr (FUSED) { flip = C.flip; S = C.S; }
+    else {
+        if (tid == 0) { sS = A.st[k]; sEps = A.eps[k]; sSeed = A.seeds[k]; sPt = A.pts[k]; }
+        __syncthreads();
+        S = sS;
+    }
     const bool idle_in = S.phase == NT_IDLE;
-    if (!(idle_in && !A.reopen)) {
-        const int p = sPt;
+    // the opening launch (trip) of a CONTINUE; the row of the recorded path; the number of the round -- each read where it is used
+    auto reopen = [&]() -> bool { if constexpr (FUSED) return C.reopen; else return A.reopen != 0; };
+    auto prow = [&]() -> int64_t { if constexpr (FUSED) return C.trip; else return A.prow; };
+    auto round = [&]() -> int64_t { if constexpr (FUSED) return C.trip + 1; else return A.round; };
+    if (!(idle_in && !reopen())) {
+        int p;
+        if constexpr (FUSED) p = C.pt; else p = sPt;
         const size_t kd = (size_t)k * d;
         // The rule for the base addresses: in the warm kernel, and only there, the argument addresses that live through the whole launch pass
         // through an empty asm, which makes each an opaque value in scalar registers.  Left as the result of the merged eight-dword argument
@@ -171,8 +210,9 @@ __device__ __forceinline__ void nt_step_body(const Args &A_) {
         double *B = A.blk + (size_t)k * A.nslot * d;
         const int ckv = NT_VECS, ckr = NT_VECS + (A.nslot - NT_VECS) / 2;        // first checkpoint slots
 #define V_(slot, i) B[(size_t)(slot) * d + (i)]
-        double eps = sEps;
-        const uint64_t seed = sSeed;
+        double eps;
+        uint64_t seed;
+        if constexpr (FUSED) { eps = C.eps; seed = C.seed; } else { eps = sEps; seed = sSeed; }
         const HmFactor F = {gVh, T, Vc, sqa};
         // METRIC: the chain's scale; c_i w of a kick and c_i v_i of a drift (row i is the calling thread's own; without METRIC the plain operand)
         // (macros on the constant METRIC and not hm_scaled of hmc_rows.h: through the function the step and warm kernels with staged rows
@@ -187,20 +227,25 @@ __device__ __forceinline__ void nt_step_body(const Args &A_) {
             else return gVh + (size_t)i * KPAD;
         };
         bool staged = false;                                 // an R pass came before the L pass (hmc_rows.h)
+        if constexpr (FUSED) staged = C.staged;
+        if constexpr (TG > 0) if (!staged) hm_target_stage<TG>(A.tg, L);     // G, once per launch: the first trip's first barrier publishes it
         bool open = idle_in, drift = false;
         int wend = 0;                                        // ADAPT: this launch ended a warm-up transition (2: a divergent one)
         int bslot = -1;                                      // the drift's base: a slot, or (-1) the trial point itself
         int ndir = S.dir;                                    // direction of the leapfrog step this launch starts
         if (!idle_in) {
-            const double lpt = A.out[k];
+            double lpt;
+            if constexpr (FUSED) lpt = hm_target_eval<TG, NRED>(A.tg, L, X, A.gout + K + kd, d, flip);
+            else lpt = A.out[k];
             const double *g = A.out + K + kd;
-            const size_t pr = ((size_t)A.prow * K + k);
+            const size_t pr = ((size_t)prow() * K + k);
             if (rec()) {                                  // what the closure saw and what it answered, before X is rewritten
-                double *pX = A.pX + pr * d, *pout = A.pout + (size_t)A.prow * ((size_t)K * (d + 1));
+                double *pX = A.pX + pr * d, *pout = A.pout + (size_t)prow() * ((size_t)K * (d + 1));
                 for (int i = tid; i < d; i += HM_NT) { pX[i] = X[i]; pout[K + kd + i] = g[i]; }
                 if (tid == 0) pout[k] = lpt;
             }
-            const double nbad = hm_apply_R<KPAD, RES, HM_NT, NRED>(F, L, g, d, flip, [&](int i) -> double & { return V_(NT_WT, i); });     // (reduction 1)
+            const double nbad = hm_apply_R<KPAD, RES, HM_NT, NRED>(F, L, g, d, flip, [&](int i) -> double & { return V_(NT_WT, i); },     // (reduction 1)
+                                                                      FUSED && staged);
             staged = true;
             const bool badg = nbad > 0.0 || !isfinite(lpt);
             if (S.phase == NT_START) {
@@ -318,7 +363,7 @@ __device__ __forceinline__ void nt_step_body(const Args &A_) {
                     if (S.t < A.t_end) open = true;
                     else {
                         for (int i = tid; i < d; i += HM_NT) X[i] = V_(NT_X, i);      // an idle chain's column stays a valid point
-                        S.phase = NT_IDLE; S.fin_round = A.round;
+                        S.phase = NT_IDLE; S.fin_round = round();
                     }
                 } else if (complete) {
                     // ---- the next doubling: from the tree's end in the new direction
@@ -408,7 +453,9 @@ __device__ __forceinline__ void nt_step_body(const Args &A_) {
                 const double y = hm_row_sub<KPAD>(vrow(i), L.sTv, i < KPAD ? L.sZ[i] : VSC_(i));
                 X[i] = fma(se, sqa[i] * y, bslot < 0 ? X[i] : V_(bslot, i));
             }
+            if constexpr (FUSED) staged = true;
         }
+        if constexpr (FUSED) { C = {S, eps, seed, idle_in ? prow() : round(), p, flip, staged, false}; return; }
         __syncthreads();                                     // every thread has read S before thread 0 writes
         if (tid == 0) A.st[k] = S;
 #undef V_
@@ -416,16 +463,14 @@ __device__ __forceinline__ void nt_step_body(const Args &A_) {
 #undef VSC_
     }
     // ---- progress of the round: the last workgroup publishes the number of chains still running
-    if (tid == 0) {
-        if (S.phase != NT_IDLE) __hip_atomic_fetch_add(A.ctr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __threadfence();
-        const int ticket = __hip_atomic_fetch_add(A.ctr + 1, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        if (ticket == K - 1) {
-            const int active = __hip_atomic_load(A.ctr, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
-            A.ctr[0] = 0; A.ctr[1] = 0;
-            __hip_atomic_store(A.h_status, (int64_t)((A.round << 32) | (int64_t)active), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-    }
+    if constexpr (!FUSED) nt_publish(A, S.phase != NT_IDLE, K);
+}
+
+// one launch of the step kernels: one round on the chain's state in HBM
+template <int KPAD, bool RES, int MODE, class Args>
+__device__ __forceinline__ void nt_step_body(const Args &A_) {
+    NtCarry none;                                        // (not read, not written)
+    nt_round<KPAD, RES, MODE, HM_TG_NONE>(A_, none);
 }
 
 #ifndef PF_CHAIN_METRIC_TU             // (nuts_metric_kernel.hip takes the body and nt_args from this file and defines its own kernels)

@@ -119,6 +119,10 @@ struct HmcState {
     int max_depth = 0, md_alloc = 0;                  // the stop rule of the last call; the depth the chains' checkpoints were made for
     int64_t issued = 0, seen = 0, max_rounds = 0;     // rounds launched / last round whose progress word the host has read / hard cap
     bool finished = true;         // every chain has made its transitions (or the cap is reached and seen)
+    // kind 1 through pfmi_nuts_fused_enqueue (nuts_fused_kernel.hip): the pump's rounds are launches of up to fused_cap evaluations each
+    bool fused = false;           // the NUTS run in flight (or resident) is a fused one
+    bool fused_reopen = false;    // its first launch opens with the trip of a CONTINUE
+    int64_t fused_cap = 0;
     // pfmi_hmc_adapt_enqueue / pfmi_nuts_adapt_enqueue (api_adapt.hip): transitions 0 .. W - 1 were the warm-up, t0 = W
     bool adapting = false;        // the call in flight launches the warm kernels (a later plain CONTINUE does not)
     int64_t W = 0;                // > 0: the adaptation states and the warm-up traces [K][W] are resident (pfmi_adapt_get)
@@ -441,6 +445,10 @@ int pf_nuts_vec_slots(int max_depth);
 int32_t pf_launch_nuts_init(pfmi_ctx *c, hipStream_t s);
 int32_t pf_launch_nuts_step(pfmi_ctx *c, int64_t round, int64_t prow, bool reopen, hipStream_t s);
 int32_t pf_nuts_chain_flags(pfmi_ctx *c, std::vector<int32_t> &dead, int64_t *last_round);
+// nuts_fused_kernel.hip: NUTS on a built-in target, launch number `launch` of the call (published with the progress word): up to `cap`
+// evaluations per chain in ONE launch (reopen: its first trip is the opening one of a CONTINUE, which evaluates nothing); the chains' state
+// and buffers are those of pf_launch_nuts_step
+int32_t pf_launch_nuts_fused(pfmi_ctx *c, int64_t launch, int cap, bool reopen, hipStream_t s);
 // hmc_metric_kernel.hip, nuts_metric_kernel.hip: the step launch of chains that carry a scale (c->hmc.scaled), plain or adaptive
 int32_t pf_launch_hmc_metric_step(pfmi_ctx *c, int64_t round, hipStream_t s);
 // chees_kernel.hip: round: the number the launch publishes with its progress word; prow: its row of the recorded path; reopen: the launch

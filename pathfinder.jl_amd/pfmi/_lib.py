@@ -60,7 +60,7 @@ SYMBOLS = [
     "pfmi_host_metric_update",
     "pfmi_chees_enqueue", "pfmi_chees_pump", "pfmi_chees_wait", "pfmi_chees_get", "pfmi_chees_get_update", "pfmi_chees_stats",
     "pfmi_host_chees_leapfrog", "pfmi_host_chees_update",
-    "pfmi_hmc_fused_enqueue",
+    "pfmi_hmc_fused_enqueue", "pfmi_nuts_fused_enqueue",
 ]
 
 # declared argument types (entry points not listed here take what the caller wraps by hand)
@@ -92,6 +92,8 @@ ARGTYPES = {
     "pfmi_hmc_fused_enqueue": [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), _dp, C.POINTER(C.c_uint64), _dp, C.c_int32, C.c_int64, C.c_int64,
                                C.c_double, C.c_int32],
     "pfmi_nuts_adapt_enqueue": [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), _dp, C.POINTER(C.c_uint64), _dp, C.c_int32, C.c_int64, C.c_int64,
+                                C.c_double, C.c_int32],
+    "pfmi_nuts_fused_enqueue": [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), _dp, C.POINTER(C.c_uint64), _dp, C.c_int32, C.c_int64, C.c_int64,
                                 C.c_double, C.c_int32],
     "pfmi_adapt_get": [C.c_void_p, _dp, _dp, _dp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
     "pfmi_host_dual_averaging": [C.c_int64, C.c_double, C.c_double, _dp, _dp, _dp],

@@ -643,6 +643,34 @@ class Engine:
         flags = (self.NUTS_CONTINUE if cont else 0) | (self.NUTS_RECORD_PATH if record_path else 0)
         self._chain_enqueue("nuts", points, x0, seeds, step_size, max_depth, ntransitions, flags)
 
+    def nuts_fused_enqueue(self, points, x0, seeds, step_size, max_depth, ntransitions, nwarmup=0, target_accept=0.8, cont=False,
+                           record_path=False):
+        """nuts_enqueue (nwarmup = 0) or nuts_adapt_enqueue (nwarmup >= 1: cont and record_path must be False) for an engine whose target
+        is BUILT IN (Gaussian family, funnel): logp and its gradient are evaluated inside the chain kernel, one workgroup per chain
+        builds its trees at its own pace over the trips of a launch (include/pfmi.h: pfmi_nuts_fused_enqueue).  nuts_pump, nuts_wait,
+        nuts_get_stats, nuts_path, hmc_get, adapt_get and chain_diagnostics serve the run; nuts_stats reports the most trips a chain made
+        and 0 closure columns.  Issues the first window of launches and returns."""
+        points = np.ascontiguousarray(points, dtype=np.int64)
+        K = len(points)
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
+        eps = np.ascontiguousarray(np.broadcast_to(np.asarray(step_size, dtype=np.float64), (K,)))
+        assert seeds.shape == (K,)
+        x0p = None
+        if x0 is not None:
+            x0 = np.asfortranarray(x0, dtype=np.float64)
+            assert x0.shape == (self.d, K), (x0.shape, self.d, K)
+            x0p = _d(x0)
+        flags = (self.NUTS_CONTINUE if cont else 0) | (self.NUTS_RECORD_PATH if record_path else 0)
+        check(self.L.pfmi_nuts_fused_enqueue(self.ctx, K, points.ctypes.data_as(_i64p), x0p, seeds.ctypes.data_as(C.POINTER(C.c_uint64)), _d(eps),
+                                             int(max_depth), int(nwarmup), int(ntransitions), float(target_accept), flags))
+        self._hmc = (K, int(ntransitions))
+        self._chees = None
+        if nwarmup:
+            self._adapt, self._metric = (K, int(nwarmup)), None
+        elif not cont:
+            self._adapt = self._metric = None
+        self.hmc_runs += 1
+
     # ---- device-resident warm-up (include/pfmi.h: pfmi_hmc_adapt_enqueue, pfmi_nuts_adapt_enqueue) -----------------------------------
     ADAPT_KEPT_STEP = 1
 

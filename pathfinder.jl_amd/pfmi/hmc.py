@@ -8,7 +8,8 @@ where the fits already are.  `hmc`: a fixed number of leapfrog steps per transit
 seeds and step-size adaptation.  The target must be a device closure with a gradient (DeviceCallbackTarget(..., grad_fn=...),
 TorchDeviceTarget(..., grad=...)); one engine only.  On a BUILT-IN target (t_iso, t_diag, t_lowrank, t_funnel, any GaussTarget /
 FunnelTarget) `hmc` takes the fused route instead (pfmi_hmc_fused_enqueue): the chain kernel evaluates logp and its gradient itself and
-loops over a run's rounds in one launch.  All three modes of `hmc` run there; `nuts`, `chees` and adapt_metric=True do not.
+loops over a run's rounds in one launch.  All three modes of `hmc` run there, and so does `nuts` with fused=True
+(pfmi_nuts_fused_enqueue); `chees` and adapt_metric=True do not.
 
 The example's second way, "initialise a metric adaptation" from the fit, is adapt="device" with adapt_metric=True (include/pfmi.h:
 pfmi_hmc_adapt_metric_enqueue): the warm-up also learns a per-coordinate scale c of every chain in Stan's windows, in the coordinates
@@ -191,15 +192,22 @@ def _builtin(target):
     return getattr(target, "kind", None) in (KIND_GAUSS, KIND_FUNNEL)
 
 
-def _chains(name, result, nchains, rng, check_param=None, adapt_metric=False):
+def _chains(name, result, nchains, rng, check_param=None, adapt_metric=False, fused=False):
     """what every sampler here starts from: (engine, starts x0 (d, nchains), fit points, seeds) of `result`; check_param: the sampler's
     own argument check, made where it has always been made (after the engine's and the target's, before nchains')"""
     eng, starts, pts, token = _starts_and_points(result)
     if eng is None:
         raise ValueError(f"pfmi.{name} needs a result whose fits are still on an engine")
     eng.check_token(token, f"pfmi.{name}")
+    if fused and not _builtin(eng.target):
+        raise ValueError(f"pfmi.{name}: fused=True needs a built-in target (pfmi.t_lowrank, t_diag, t_iso, t_funnel); a device closure target "
+                         "with a gradient runs with fused=False")
     if _builtin(eng.target):
-        if name != "hmc":
+        if name == "nuts" and fused:
+            if adapt_metric:
+                raise ValueError("pfmi.nuts: adapt_metric=True needs a device closure target with a gradient; fused=True on a built-in target "
+                                 "samples with the fitted metric itself (adapt_metric=False)")
+        elif name != "hmc":
             raise ValueError(f"pfmi.{name} needs a device closure target with a gradient; on a built-in target static HMC is available "
                              "(pfmi.hmc: fixed step, adapt=\"windows\" and adapt=\"device\")")
         if adapt_metric:
@@ -217,25 +225,26 @@ def _chains(name, result, nchains, rng, check_param=None, adapt_metric=False):
     return eng, np.asfortranarray(starts[:, :nchains]), pts[:nchains], rng.rand_u64(nchains)
 
 
-def _run(name, result, ndraws, nchains, nwarmup, step_size, param, rng, target_accept, window, adapt, adapt_metric=False):
+def _run(name, result, ndraws, nchains, nwarmup, step_size, param, rng, target_accept, window, adapt, adapt_metric=False, fused=False):
     """the driver behind hmc() and nuts(): `name` is the sampler ("hmc" / "nuts"), `param` its nleapfrog / max_depth"""
     is_nuts = name == "nuts"
     def check_param():
         if is_nuts and not 1 <= int(param) <= 10:
             raise ValueError("max_depth must be in 1 .. 10")
 
-    eng, x0, pts, seeds = _chains(name, result, nchains, rng, check_param, adapt_metric)
+    eng, x0, pts, seeds = _chains(name, result, nchains, rng, check_param, adapt_metric, fused)
     d, nchains = x0.shape
-    fused = _builtin(eng.target)                         # (static HMC only: _chains has refused everything else)
+    fused = _builtin(eng.target)                         # (static HMC, or NUTS with fused=True: _chains has refused everything else)
+    fenq = eng.nuts_fused_enqueue if is_nuts else eng.hmc_fused_enqueue
     auto = isinstance(step_size, str)
     if auto and step_size != "auto":
         raise ValueError('step_size must be a number, an array of nchains numbers or "auto"')
     eps = np.full(nchains, d ** -0.25) if auto else np.broadcast_to(np.asarray(step_size, dtype=np.float64), (nchains,)).copy()
-    enqueue, wait = (eng.nuts_enqueue, eng.nuts_wait) if is_nuts else (eng.hmc_fused_enqueue if fused else eng.hmc_enqueue, eng.hmc_wait)
+    enqueue, wait = (fenq if fused else eng.nuts_enqueue, eng.nuts_wait) if is_nuts else (fenq if fused else eng.hmc_enqueue, eng.hmc_wait)
     warm = scale = None
     if _check_adapt(adapt, auto, int(nwarmup), adapt_metric):
         if fused:
-            eng.hmc_fused_enqueue(pts, x0, seeds, eps, param, int(ndraws), int(nwarmup), target_accept)
+            fenq(pts, x0, seeds, eps, param, int(ndraws), int(nwarmup), target_accept)
         else:
             if adapt_metric:
                 aenq = eng.nuts_adapt_metric_enqueue if is_nuts else eng.hmc_adapt_metric_enqueue
@@ -294,13 +303,19 @@ def hmc(result, ndraws, *, nchains=None, nwarmup=0, step_size="auto", nleapfrog=
 
 
 def nuts(result, ndraws, *, nchains=None, nwarmup=0, step_size="auto", max_depth=10, rng=None, target_accept=0.8, window=10, adapt="windows",
-         adapt_metric=False):
+         adapt_metric=False, fused=False):
     """`ndraws` transitions of `nchains` chains of multinomial NUTS from a PathfinderResult / MultiPathfinderResult: the starts, metrics,
     seeds and step-size rule of `hmc` (dual averaging between windows of `window` warm-up transitions on the windows' mean accept_prob,
     the mean over a tree's leaves of min(1, exp(H0 - H))), with trees of at most 2^max_depth - 1 leapfrog steps instead of a fixed count.
     adapt="device": as for `hmc`, one enqueue whose warm-up adapts on the device after every transition (pfmi_nuts_adapt_enqueue);
-    adapt_metric=True: with the metric windows of `hmc` (pfmi_nuts_adapt_metric_enqueue)."""
-    return _run("nuts", result, ndraws, nchains, nwarmup, step_size, max_depth, rng, target_accept, window, adapt, adapt_metric)
+    adapt_metric=True: with the metric windows of `hmc` (pfmi_nuts_adapt_metric_enqueue).
+
+    fused=True, on a built-in target (pfmi.t_lowrank, t_diag, t_iso, t_funnel): the run takes the fused route (pfmi_nuts_fused_enqueue: the
+    chain kernel evaluates logp and its gradient itself and every chain builds its trees at its own pace) in all three modes -- fixed step,
+    adapt="windows", adapt="device" -- and returns the same NUTSResult.  It raises ValueError with adapt_metric=True and on a closure
+    target.  The default is False because pfmi.nuts on a built-in target has been pinned to raise; it will flip to the fused route on
+    built-in targets once that pin may be touched."""
+    return _run("nuts", result, ndraws, nchains, nwarmup, step_size, max_depth, rng, target_accept, window, adapt, adapt_metric, fused)
 
 
 @dataclass
