@@ -51,6 +51,12 @@
 #ifndef QF_CS_LDS
 #define QF_CS_LDS 1                    // 0: the c/s column is never staged in LDS, every block of the pseudo group loads and divides (A/B builds)
 #endif
+#ifndef QF_EPI_PAIR
+#define QF_EPI_PAIR 1                  // 0: every group of a wave is finished on its own, its A operands read inside its chains (A/B builds)
+#endif
+#ifndef QF_EPI_MFMA4
+#define QF_EPI_MFMA4 1                 // 0: the paired finish keeps the 16x16x4 MFMA at every KC (A/B builds; needs QF_EPI_PAIR)
+#endif
 #ifndef QF_NG2_MAXKC
 #define QF_NG2_MAXKC 20                // two groups per wave up to this KC (round 2: 12; KC = 16, 20 take the register-lean block body)
 #endif
@@ -805,6 +811,156 @@ __global__ __launch_bounds__(QF_THREADS) void pf_elbo_qf_kernel(ElboArgs A, int 
         int d_e = d;                                                // (and for the two constants (double) d feeds: one v_cvt here, not 8 B of scratch each)
         asm volatile("" : "+s"(d_e));
         // ---- finish the 16 draws of each group in registers: lane (q, c) holds entries 4T + q of w, A3, A4 of draw c
+#if QF_EPI_PAIR
+        // One finish for all groups of the wave (round 12).  The A operands of T, M, Nn and G are the same for every group and batch:
+        // they are read once here, in one flight in front of the first cross-q sum, and the groups' chains run in lockstep -- T w of
+        // every group, then M tv and Nn tv (independent of each other) step by step, then G tt -- so that no MFMA has the one issued
+        // just before it as an operand.  Every dot product and sum keeps its operations and their order: the same bits.  A group that
+        // is idle or a pseudo group goes through the same arithmetic on its zeroed / constant-bearing accumulators and stores nothing.
+        {
+            // M4 (QF_EPI_MFMA4, KC <= 12, where a 16-row tile is mostly padding): the products run on v_mfma_f64_4x4x4 -- lane (q, c)
+            // holding entry 4T + q of draw c is its B operand (k = q, block = c >> 2, n = c & 3) and its result, the A operand is
+            // Mat[4 rt + (lane & 3)][4 st + q] for all four blocks: one MFMA per 4 x 4 tile of Mat, the tiles of a row in a chain
+            constexpr bool M4 = QF_EPI_MFMA4 != 0 && KC <= 12;
+            constexpr int TRr = TR > 0 ? TR : 1;
+            constexpr int NRT = M4 ? NT : (NT + 3) / 4, NRR = M4 ? TRr : (TRr + 3) / 4;   // row tiles of a KC-row / RPAD-row matrix
+            constexpr bool LOWR = TGT == 1 && RPAD > 0;
+            using acc_t = std::conditional_t<M4, double, qf_d4>;
+            const int l3e = lane_e & 3;
+            auto load_a = [&](const double *Mat, const int ld, const int nrows, auto lower_tag, auto &a) {
+                constexpr bool LOWER = decltype(lower_tag)::value;
+                constexpr int NR = sizeof(a) / sizeof(a[0]), NX = sizeof(a[0]) / sizeof(double);
+#pragma unroll
+                for (int rt = 0; rt < NR; ++rt) {
+                    const int row = M4 ? 4 * rt + l3e : 16 * rt + ce;
+#pragma unroll
+                    for (int st = 0; st < NX; ++st) {
+                        const int col = 4 * st + qe;
+                        const bool ok = row < nrows && (!LOWER || col <= row);
+                        a[rt][st] = ok ? Mat[row * ld + col] : 0.0;
+                    }
+                }
+            };
+            // step st of y = Mat x for every row tile and group: one MFMA each, all on different accumulators
+            auto mv_step = [&](const int st, const auto &a, const auto &x, auto &acc) {
+                constexpr int NR = sizeof(a) / sizeof(a[0]);
+#pragma unroll
+                for (int rt = 0; rt < NR; ++rt)
+#pragma unroll
+                    for (int g = 0; g < NG; ++g) {
+                        if constexpr (M4) acc[g][rt] = qf_mfma4(a[rt][st], x[g][st], acc[g][rt]);
+                        else acc[g][rt] = qf_mfma16(a[rt][st], x[g][st], acc[g][rt]);
+                    }
+            };
+            auto mv_zero = [&](auto &acc) {
+                constexpr int NR = sizeof(acc[0]) / sizeof(acc_t);
+#pragma unroll
+                for (int g = 0; g < NG; ++g)
+#pragma unroll
+                    for (int rt = 0; rt < NR; ++rt) acc[g][rt] = acc_t{};
+            };
+            auto mv_out = [&](const auto &acc, auto &y) {
+                constexpr int NR = sizeof(acc[0]) / sizeof(acc_t), NY = sizeof(y[0]) / sizeof(double);
+#pragma unroll
+                for (int g = 0; g < NG; ++g)
+#pragma unroll
+                    for (int rt = 0; rt < NR; ++rt) {
+                        if constexpr (M4) { if (rt < NY) y[g][rt] = acc[g][rt]; }
+                        else {
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) if (4 * rt + r < NY) y[g][4 * rt + r] = acc[g][rt][r];
+                        }
+                    }
+            };
+            const double *vv = cn_s + 4, *Mm = cn_s + 4 + KC, *t0 = Mm + KC * KC, *Nn = t0 + RPAD, *vh0 = Nn + RPAD * KC;
+            double aT[NRT][NT], aM[NRT][NT], aN[NRR][NT], aG[NRR][TRr];
+            if (TGT != 0) {
+                load_a(t_s, KC, KC, std::false_type{}, aT);
+                load_a(Mm, KC, KC, std::false_type{}, aM);
+                if (LOWR) {
+                    load_a(Nn, KC, RPAD, std::false_type{}, aN);
+                    load_a(g_s, RPAD, RPAD, std::true_type{}, aG);
+                }
+                __builtin_amdgcn_sched_barrier(0);                  // the reads are in flight before the sums below start
+            }
+            double us[NG], lp[NG];
+#pragma unroll
+            for (int g = 0; g < NG; ++g) { us[g] = pf_sum_q(usq[g]); lp[g] = NAN; }
+            if (TGT != 0) {
+                double qs[NG], tvd[NG][NT], mt[NG][NT], nt[NG][TRr], q1[NG];
+                acc_t cT[NG][NRT], cM[NG][NRT], cN[NG][NRR];
+#pragma unroll
+                for (int g = 0; g < NG; ++g) qs[g] = pf_sum_q(q12[g]);
+                mv_zero(cT);
+#pragma unroll
+                for (int st = 0; st < NT; ++st) mv_step(st, aT, accw, cT);
+                mv_out(cT, tvd);
+                mv_zero(cM);
+                if (LOWR) mv_zero(cN);
+#pragma unroll
+                for (int st = 0; st < NT; ++st) {
+                    mv_step(st, aM, tvd, cM);
+                    if (LOWR) mv_step(st, aN, tvd, cN);
+                }
+                mv_out(cM, mt);
+                if (LOWR) mv_out(cN, nt);
+#pragma unroll
+                for (int g = 0; g < NG; ++g) {
+                    double qa = 0.0;
+#pragma unroll
+                    for (int T = 0; T < NT; ++T)
+                        qa = fma(tvd[g][T], mt[g][T] - 2.0 * (FOLD ? acc3[g][T] - vv[4 * T + qe] : vv[4 * T + qe] + acc3[g][T]), qa);   // A3' - v = A3 + v
+                    qa = pf_sum_q(qa);
+                    q1[g] = cn_s[0] + qs[g] + qa;
+                }
+                if (TGT == 1) {
+                    double corr[NG];
+#pragma unroll
+                    for (int g = 0; g < NG; ++g) corr[g] = 0.0;
+                    if (RPAD > 0) {
+                        double tt[NG][TRr], gg[NG][TRr];
+                        acc_t cG[NG][NRR];
+#pragma unroll
+                        for (int g = 0; g < NG; ++g)
+#pragma unroll
+                            for (int T = 0; T < TR; ++T) tt[g][T] = t0[4 * T + qe] + acc4[g][T] - nt[g][T];
+                        mv_zero(cG);
+#pragma unroll
+                        for (int st = 0; st < TRr; ++st) mv_step(st, aG, tt, cG);
+                        mv_out(cG, gg);
+#pragma unroll
+                        for (int g = 0; g < NG; ++g) {
+#pragma unroll
+                            for (int T = 0; T < TR; ++T) corr[g] = fma(gg[g][T], gg[g][T], corr[g]);
+                            corr[g] = pf_sum_q(corr[g]);
+                        }
+                    }
+#pragma unroll
+                    for (int g = 0; g < NG; ++g) lp[g] = A.t_offset - 0.5 * (q1[g] - corr[g]);
+                } else {                                                   // funnel: tau = x_1, ss = sum_{i>=2} x_i^2
+#pragma unroll
+                    for (int g = 0; g < NG; ++g) {
+                        const double zh = __shfl(z00[g], ce, 64);
+                        double pr = 0.0;
+#pragma unroll
+                        for (int T = 0; T < NT; ++T) pr = fma(vh0[4 * T + qe], tvd[g][T], pr);
+                        pr = pf_sum_q(pr);
+                        const double ta = cn_s[1] + cn_s[2] * (zh - pr), t3 = ta / 3.0;
+                        lp[g] = (t3 * t3 + (double)(d_e - 1) * ta + q1[g] * exp(-ta)) / -2.0;
+                    }
+                }
+            }
+#pragma unroll
+            for (int g = 0; g < NG; ++g) {
+                if (!active[g] || pseudo[g]) continue;
+                const int64_t nl = (int64_t)(g_begin + (lb * QF_WAVES + wv_e) * NG + g - npg) * 16 + ce;
+                if (qe == 0 && nl < A.N) {
+                    out_lq[nl] = ((double)d_e * PF_LOG2PI + logdet + us[g]) / -2.0;     // src/mvnormal.jl:36
+                    out_lp[nl] = lp[g];
+                }
+            }
+        }
+#else
 #pragma unroll
         for (int g = 0; g < NG; ++g) {
             if (!active[g] || pseudo[g]) continue;
@@ -878,6 +1034,7 @@ __global__ __launch_bounds__(QF_THREADS) void pf_elbo_qf_kernel(ElboArgs A, int 
                 out_lp[nl] = lp;
             }
         }
+#endif
 #if QF_PROF
         { const long long t_ = wall_clock64(); qf_te += t_ - qf_last; qf_last = t_; }
 #endif

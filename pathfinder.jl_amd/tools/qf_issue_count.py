@@ -237,6 +237,57 @@ def prologue_load_trips(asm, kc=12, tgt=1, rpad=8, ng=2):
     raise RuntimeError("no s_barrier in the kernel")
 
 
+FINISH_CLASSES = ("mfma16", "mfma4", "lds_reads", "scratch_loads", "nop_cycles", "waitcnt", "cross_lane", "waits_in_chain",
+                  "reads_in_chain")
+
+
+def finish_counts(asm, kc=12, tgt=1, rpad=8, ng=2):
+    """counts of the per-batch draw finish of pf_elbo_qf_kernel<kc, tgt, rpad, ng>, tgt != 0: the kernel's text in layout order from its
+    last `s_barrier` (the end of the publish step) to `s_endpgm`, which is the finish of all `ng` groups of a wave and the batch loop's
+    latch.  `per_group` divides by ng.  waits_in_chain / reads_in_chain: `s_waitcnt`s / LDS reads that sit between the first and the last
+    MFMA of a stretch of the region that ends in a group's stores -- inside the dependency chains, where their latency is on the path"""
+    ins = []
+    for l in kernel_lines(asm, mangled(kc, tgt, rpad, ng))[1:]:
+        s = l.strip().split(";")[0].strip()
+        if not s or s.startswith(".") or s.endswith(":"):
+            continue
+        if s.split()[0] == "s_barrier":
+            ins = []
+            continue
+        ins.append(s)
+        if s.split()[0] == "s_endpgm":
+            break
+    c = dict.fromkeys(FINISH_CLASSES, 0)
+    # a group's stores end its chains: the span from the first to the last MFMA is taken per stretch between global stores
+    seg, segs = 0, []
+    for s in ins:
+        segs.append(seg)
+        seg += s.startswith("global_store")
+    span = {}
+    for i, s in enumerate(ins):
+        if s.startswith("v_mfma"):
+            span[segs[i]] = (span.get(segs[i], (i, i))[0], i)
+    for i, s in enumerate(ins):
+        op = s.split()[0]
+        k = classify(s)
+        lo, hi = span.get(segs[i], (0, -1))
+        if k in ("mfma16", "mfma4", "waitcnt"):
+            c[k] += 1
+        elif k == "nop_cycles":
+            c[k] += int(s.split()[1], 0) + 1
+        if op.startswith("ds_read"):
+            c["lds_reads"] += 1
+            c["reads_in_chain"] += lo < i < hi
+        if op.startswith("scratch_load") or (op.startswith("buffer_load") and "offen" in s):
+            c["scratch_loads"] += 1
+        if op.startswith(("v_permlane", "ds_swizzle", "ds_bpermute", "ds_permute")) or "row_" in s or "quad_perm" in s:
+            c["cross_lane"] += 1
+        if k == "waitcnt" and lo < i < hi:
+            c["waits_in_chain"] += 1
+    c["per_group"] = {k: v / ng for k, v in c.items()}
+    return c
+
+
 def main(argv):
     asm_file = None
     if argv[:1] == ["--asm"]:
@@ -252,6 +303,9 @@ def main(argv):
         print(f"  {'~cycles':12s} MFMA {r['mfma_cycles']:.0f} + other {r['non_mfma_cycles']:.0f}")
         t, n = prologue_load_trips(asm, *inst)
         print(f"  prologue: {n} global loads, {t} dependent round trip(s) behind the first flight")
+        if inst[1] != 0:
+            f = finish_counts(asm, *inst)
+            print("  finish, per group: " + ", ".join(f"{k} {f['per_group'][k]:g}" for k in FINISH_CLASSES))
 
 
 if __name__ == "__main__":
