@@ -141,7 +141,8 @@ int32_t pfmi_debug_set(const char *key, const char *value);
  * The fused static-HMC kernel (pfmi_hmc_fused_enqueue) has the stage name "hmc_fused" and, one count per kernel launch,
  * "hmc_fused:<KPAD>:<res|stream>:<f|g0|g8|g16>": column padding KPAD (4 .. 64), the chain's factor rows staged in LDS or streamed
  * from HBM, and the target -- the funnel, or the Gaussian family with rank padding 0, 8 or 16.  The fused NUTS kernel
- * (pfmi_nuts_fused_enqueue) likewise: stage "nuts_fused", counters "nuts_fused:<KPAD>:<res|stream>:<f|g0|g8|g16>". */
+ * (pfmi_nuts_fused_enqueue) likewise: stage "nuts_fused", counters "nuts_fused:<KPAD>:<res|stream>:<f|g0|g8|g16>"; the fused-metric
+ * kernels (pfmi_*_fused_metric_enqueue): stages "hmc_fused_metric" / "nuts_fused_metric", counters "<stage>:<KPAD>:<res|stream>:<f|g0|g8|g16>". */
 int32_t pfmi_timer_start(pfmi_ctx *ctx);
 int32_t pfmi_timer_stop(pfmi_ctx *ctx, double *milliseconds);
 int32_t pfmi_profile(pfmi_ctx *ctx, int32_t enable);
@@ -503,9 +504,9 @@ int32_t pfmi_nuts_adapt_enqueue(pfmi_ctx *ctx, int32_t K, const int64_t *points,
  * pfmi_hmc_stats reports rounds = (fresh ? 1 : 0) + (nwarmup + ntransitions) nleapfrog evaluations and closure_columns = 0.
  * Errors are those of pfmi_hmc_enqueue / pfmi_hmc_adapt_enqueue, in their order and with the drain-on-error rule, except that
  * PFMI_ERR_UNSUPPORTED is returned for any callback target (a DEVICE_CALLBACK target with a gradient closure runs through pfmi_hmc_enqueue)
- * and for a staged scale (pfmi_chain_scale_set: the metric kernels are not fused).
- * NUTS on a built-in target is pfmi_nuts_fused_enqueue below.  Out of scope: ChEES, the metric windows and scaled chains on built-in
- * targets; pfmi_hmc_enqueue, pfmi_nuts_enqueue, the adaptive enqueues and pfmi_chees_enqueue are unchanged and still refuse a built-in target.
+ * and for a staged scale (pfmi_chain_scale_set: pfmi_hmc_fused_metric_enqueue takes it).
+ * NUTS on a built-in target is pfmi_nuts_fused_enqueue below; the metric windows and scaled chains are pfmi_hmc_fused_metric_enqueue.
+ * Out of scope: ChEES; pfmi_hmc_enqueue, pfmi_nuts_enqueue, the adaptive enqueues and pfmi_chees_enqueue are unchanged and still refuse a built-in target.
  * Stage name "hmc_fused"; plan counters "hmc_fused:<KPAD>:<res|stream>:<f|g0|g8|g16>" (pfmi_kernel_time). */
 int32_t pfmi_hmc_fused_enqueue(pfmi_ctx *ctx, int32_t K, const int64_t *points, const double *x0, const uint64_t *seeds,
                                const double *step_size, int32_t nleapfrog, int64_t nwarmup, int64_t ntransitions, double target_accept,
@@ -532,10 +533,10 @@ int32_t pfmi_hmc_fused_enqueue(pfmi_ctx *ctx, int32_t K, const int64_t *points, 
  * gradient, and a chain's rows beyond its own trips keep event t = -1.
  * Errors are those of pfmi_nuts_enqueue / pfmi_nuts_adapt_enqueue, in their order and with the drain-on-error rule, except that
  * PFMI_ERR_UNSUPPORTED is returned for any callback target (a DEVICE_CALLBACK target with a gradient closure runs through
- * pfmi_nuts_enqueue) and for a staged scale or resident scaled chains (the metric kernels are not fused).  PFMI_NUTS_CONTINUE on the
+ * pfmi_nuts_enqueue) and for a staged scale or resident scaled chains (pfmi_nuts_fused_metric_enqueue takes them).  PFMI_NUTS_CONTINUE on the
  * chains of another sampler -- pfmi_hmc_fused_enqueue's included -- is PFMI_ERR_STATE, with max_depth above the chains' PFMI_ERR_ARG.
  * Fused and closure NUTS calls never meet on the same resident chains: replacing the target forgets the chains.
- * Out of scope: ChEES (its chains talk to each other), the metric windows and scaled chains on built-in targets.
+ * Out of scope: ChEES (its chains talk to each other); the metric windows and scaled chains are pfmi_nuts_fused_metric_enqueue.
  * Stage name "nuts_fused"; plan counters "nuts_fused:<KPAD>:<res|stream>:<f|g0|g8|g16>", one count per launch (pfmi_kernel_time). */
 int32_t pfmi_nuts_fused_enqueue(pfmi_ctx *ctx, int32_t K, const int64_t *points, const double *x0, const uint64_t *seeds,
                                 const double *step_size, int32_t max_depth, int64_t nwarmup, int64_t ntransitions, double target_accept,
@@ -601,6 +602,31 @@ int32_t pfmi_nuts_adapt_metric_enqueue(pfmi_ctx *ctx, int32_t K, const int64_t *
  * [K][ends[nwindows - 1] - init][d] the u of every window transition (PFMI_ERR_STATE if the run did not record them).  Any may be NULL.
  * Waits as pfmi_adapt_get does.  PFMI_ERR_STATE without such a run. */
 int32_t pfmi_adapt_metric_get(pfmi_ctx *ctx, int32_t *nwindows, int64_t *ends, double *scale_trace, double *whitened);
+/* ---- the scale and the metric windows on the built-in targets: whole runs in one persistent kernel ----------------------------- */
+/* pfmi_hmc_fused_enqueue / pfmi_nuts_fused_enqueue for chains that carry a per-coordinate scale, and the metric windows above, for a ctx
+ * whose target is PFMI_TARGET_GAUSS or PFMI_TARGET_FUNNEL: the loops of the fused kernels around the round of the metric kernels
+ * (csrc/hmc_fused_metric_kernel.hip, csrc/nuts_fused_metric_kernel.hip).  The end of a window writes the chain's scale and the next kick
+ * reads it inside ONE launch; whatever the cut into launches (HM_FUSED_ROUNDS and its hooks, as they are), the bits are the same.
+ * nwarmup == 0: a plain run; flags: PFMI_*_CONTINUE, PFMI_*_RECORD_PATH.  A scale staged by pfmi_chain_scale_set becomes the chains'
+ *   resident one, a CONTINUE goes on with the one the chains carry; chains that carry a scale are stepped by the fused-metric kernels,
+ *   chains without one by the fused kernels.  With a staged scale of ones the draws are the bits of pfmi_*_fused_enqueue.
+ * nwarmup >= 1: a fresh adaptive run with the metric windows of pfmi_*_adapt_metric_enqueue (same windows, same rule, same restarts of
+ *   the dual averaging, same status bits, a staged scale is the start scale); flags: 0 or PFMI_ADAPT_RECORD_WHITENED; target_accept in
+ *   (0, 1).  nwarmup < 20 without a staged scale has no window: the run is pfmi_*_fused_enqueue's step-size warm-up, on the fused kernels,
+ *   with PFMI_ADAPT_NO_METRIC_WINDOW set.  nwarmup < 0: PFMI_ERR_ARG.
+ * Checks, their order, the drain-on-error rule, the launches' schedule (NUTS: pumped) and everything that serves the run are those of
+ * pfmi_hmc_fused_enqueue / pfmi_nuts_fused_enqueue, plus pfmi_adapt_metric_get for a run with nwarmup >= 1.  A callback target is
+ * PFMI_ERR_UNSUPPORTED (a DEVICE_CALLBACK target with a gradient closure runs through pfmi_hmc_adapt_metric_enqueue /
+ * pfmi_nuts_adapt_metric_enqueue, or pfmi_chain_scale_set in front of pfmi_hmc_enqueue / pfmi_nuts_enqueue).  pfmi_hmc_fused_enqueue and
+ * pfmi_nuts_fused_enqueue keep refusing a staged scale and a CONTINUE of chains that carry one.  Out of scope: ChEES.
+ * Stage names "hmc_fused_metric", "nuts_fused_metric"; plan counters "hmc_fused_metric:<KPAD>:<res|stream>:<f|g0|g8|g16>" and
+ * "nuts_fused_metric:...", one count per launch (pfmi_kernel_time). */
+int32_t pfmi_hmc_fused_metric_enqueue(pfmi_ctx *ctx, int32_t K, const int64_t *points, const double *x0, const uint64_t *seeds,
+                                      const double *step_size, int32_t nleapfrog, int64_t nwarmup, int64_t ntransitions,
+                                      double target_accept, int32_t flags);
+int32_t pfmi_nuts_fused_metric_enqueue(pfmi_ctx *ctx, int32_t K, const int64_t *points, const double *x0, const uint64_t *seeds,
+                                       const double *step_size, int32_t max_depth, int64_t nwarmup, int64_t ntransitions,
+                                       double target_accept, int32_t flags);
 /* Host builds of the device's sources (csrc/adapt.h), as pfmi_host_dual_averaging is; no GPU, no ctx.
  * pfmi_adapt_windows: the windows of nwarmup transitions -- *init the first window's start, *term the transitions after the last,
  * ends [*nwindows] (nwarmup < 20: no window, *init = nwarmup, *term = 0).  PFMI_ERR_ARG: nwarmup < 1, a NULL pointer, cap too small.

@@ -378,7 +378,7 @@ int32_t pfmi_kernel_time(pfmi_ctx *c, const char *name, double *ms, int64_t *lau
         return PFMI_OK;
     }
     bool sampler_plan = false;                                        // launches of one plan of a step or warm kernel or of the operator surface, host-side count ("hmc", "nuts", ... are the stages)
-    for (const char *pre : {"hmc:", "hmc_fused:", "nuts:", "nuts_fused:", "hmc_adapt:", "nuts_adapt:", "hmc_metric:", "nuts_metric:", "chees:", "woodbury:", "woodbury_diag:"}) sampler_plan = sampler_plan || strncmp(name, pre, strlen(pre)) == 0;
+    for (const char *pre : {"hmc:", "hmc_fused:", "nuts:", "nuts_fused:", "hmc_adapt:", "nuts_adapt:", "hmc_metric:", "nuts_metric:", "hmc_fused_metric:", "nuts_fused_metric:", "chees:", "woodbury:", "woodbury_diag:"}) sampler_plan = sampler_plan || strncmp(name, pre, strlen(pre)) == 0;
     if (sampler_plan) {
         auto pl = c->hmc_plans.find(name);
         if (ms) *ms = 0.0;

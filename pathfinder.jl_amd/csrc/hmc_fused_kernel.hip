@@ -23,34 +23,36 @@ struct HmFusedArgs : HmArgs {
     int ntrips;                        // trips of this launch; `round` is the first one's (-1: the opening trip of a CONTINUE)
 };
 
-template <int KPAD, bool RES, int TG>
-__global__ __launch_bounds__(HM_NT) void pf_hmc_fused_kernel(HmFusedArgs A) {
-    const int k = blockIdx.x;
-    HmCarry C = {A.st[k], A.eps[k], A.round, 0, false};
-#pragma unroll 1
-    for (int trip = 0; trip < A.ntrips; ++trip) hm_round<KPAD, RES, HM_WARM, TG>(A, C);
-    __syncthreads();                                     // every thread has read S before thread 0 writes
+// The loop of a launch, the body of a kernel <KPAD, RES, TG> whose parameter is A: MODE is HM_WARM here and HM_METRIC in
+// hmc_fused_metric_kernel.hip (A: HmFusedArgs, there with HmMetric M behind it).  A macro and not a function: the fused kernel is then the
+// code it has always been -- through a forceinline function every instantiation of it moved about 20 more scalar registers into lanes.
+#define HM_FUSED_LOOP(MODE)                                                                                               \
+    const int k = blockIdx.x;                                                                                             \
+    HmCarry C = {A.st[k], A.eps[k], A.round, 0, false};                                                                   \
+    _Pragma("unroll 1")                                                                                                   \
+    for (int trip = 0; trip < A.ntrips; ++trip) hm_round<KPAD, RES, MODE, TG>(A, C);                                      \
+    __syncthreads();                                     /* every thread has read S before thread 0 writes */             \
     if (threadIdx.x == 0) A.st[k] = C.S;
-}
 
-// trips [round, round + ntrips) of the call in one launch, counted under "hmc_fused:<KPAD>:<res|stream>:<f|g0|g8|g16>"
-int32_t pf_launch_hmc_fused(pfmi_ctx *c, int64_t round, int ntrips, hipStream_t s) {
+// One launch of a fused family (Family::kernel<KPAD, RES, TG>() is its kernel, Family::plan its plan name; Args: HmFusedArgs or a struct
+// that extends it): trips [round, round + ntrips) of the call, counted under "<plan>:<KPAD>:<res|stream>:<f|g0|g8|g16>"
+template <class Family, class Args>
+static int32_t hm_launch_fused(pfmi_ctx *c, Args &A, int64_t round, int ntrips, hipStream_t s) {
     const TargetDev &T = c->target;
-    HmFusedArgs A;
     static_cast<HmArgs &>(A) = hm_args(c, round);
     A.tg = {T.mean.as<double>(), T.a.as<double>(), T.wd.as<double>(), T.g.as<double>(), T.offset};
     A.gout = c->hm_out.as<double>();
     A.ntrips = ntrips;
     const int tgs = T.kind == PFMI_TARGET_FUNNEL ? HM_TG_FUNNEL : T.rpad;
     PF_CHECK((T.kind == PFMI_TARGET_FUNNEL || T.kind == PFMI_TARGET_GAUSS) && (tgs == HM_TG_FUNNEL || tgs == 0 || tgs == 8 || tgs == 16), PFMI_ERR_UNSUPPORTED,
-             "hmc_fused: target kind %d with rank padding %d has no fused kernel", T.kind, T.rpad);
+             "%s: target kind %d with rank padding %d has no fused kernel", Family::plan, T.kind, T.rpad);
     const bool res = pf_hmc_resident(A.d, c->kpad);
     auto go = [&](auto KP, auto RES, auto TG) -> int32_t {
-        auto *kern = &pf_hmc_fused_kernel<KP(), RES(), TG()>;
+        auto *kern = Family::template kernel<KP(), RES(), TG()>();
         if (RES()) PF_TRY(pf_raise_lds_limit(c, reinterpret_cast<const void *>(kern), HM_LDS_RES));
-        char name[40], tn[8];
+        char name[48], tn[8];
         if (TG() == HM_TG_FUNNEL) snprintf(tn, sizeof tn, "f"); else snprintf(tn, sizeof tn, "g%d", (int)TG());
-        snprintf(name, sizeof name, "hmc_fused:%d:%s:%s", (int)KP(), RES() ? "res" : "stream", tn);
+        snprintf(name, sizeof name, "%s:%d:%s:%s", Family::plan, (int)KP(), RES() ? "res" : "stream", tn);
         ++c->hmc_plans[name];
         hipLaunchKernelGGL(kern, dim3(A.K), dim3(HM_NT), RES() ? (size_t)A.d * KP() * sizeof(double) : 0, s, A);
         return PFMI_OK;
@@ -72,3 +74,21 @@ int32_t pf_launch_hmc_fused(pfmi_ctx *c, int64_t round, int ntrips, hipStream_t 
     PF_HIP(hipGetLastError());
     return PFMI_OK;
 }
+
+#ifndef PF_FUSED_METRIC_TU             // (hmc_fused_metric_kernel.hip takes the loop, HmFusedArgs and the launch from this file and defines its own kernel)
+template <int KPAD, bool RES, int TG>
+__global__ __launch_bounds__(HM_NT) void pf_hmc_fused_kernel(HmFusedArgs A) {
+    HM_FUSED_LOOP(HM_WARM)
+}
+
+struct HmFusedFamily {
+    static constexpr const char *plan = "hmc_fused";
+    template <int KPAD, bool RES, int TG>
+    static auto kernel() { return &pf_hmc_fused_kernel<KPAD, RES, TG>; }
+};
+
+int32_t pf_launch_hmc_fused(pfmi_ctx *c, int64_t round, int ntrips, hipStream_t s) {
+    HmFusedArgs A;
+    return hm_launch_fused<HmFusedFamily>(c, A, round, ntrips, s);
+}
+#endif

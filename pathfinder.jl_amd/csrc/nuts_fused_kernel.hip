@@ -30,55 +30,58 @@ struct NtFusedArgs : NtArgs {
     int cap;                           // most evaluations of this launch; `round` is the launch's number, `reopen` its first trip's
 };
 
-template <int KPAD, bool RES, int TG>
-__global__ __launch_bounds__(HM_NT) void pf_nuts_fused_kernel(NtFusedArgs A_) {
+// The loop of a launch, its carry, ticket and nt_publish: the body of a kernel <KPAD, RES, TG> whose first and only parameter is ARGS A_.
+// MODE is NT_WARM here and NT_METRIC in nuts_fused_metric_kernel.hip (ARGS: NtFusedArgs, there with HmMetric M behind it).  A macro and
+// not a function: the fused kernel is then the code it has always been (nuts_kernel.hip is sensitive to how its callers are written).
 #if defined(__HIP_DEVICE_COMPILE__)
-    const NtFusedArgs &A = *(const NtFusedArgs *)__builtin_amdgcn_kernarg_segment_ptr();     // (nt_round says why)
+#define NT_FUSED_ARGS(ARGS) const ARGS &A = *(const ARGS *)__builtin_amdgcn_kernarg_segment_ptr();     /* (nt_round says why) */
 #else
-    const NtFusedArgs &A = A_;
+#define NT_FUSED_ARGS(ARGS) const ARGS &A = A_;
 #endif
-    const int k = blockIdx.x, tid = threadIdx.x;
-    // the chain's scalars go through LDS, as in the step kernels: the values live in vector registers
-    __shared__ NtChain sS0;
-    __shared__ double sEps0;
-    __shared__ uint64_t sSeed0;
-    __shared__ int sPt0;
-    if (tid == 0) { sS0 = A.st[k]; sEps0 = A.eps[k]; sSeed0 = A.seeds[k]; sPt0 = A.pts[k]; }
-    __syncthreads();
-    NtCarry C;
-    C.S = sS0; C.eps = sEps0; C.seed = sSeed0; C.pt = sPt0;
-    C.flip = 0; C.staged = false;
-    C.reopen = A.reopen != 0;
-    C.trip = C.reopen ? 0 : C.S.fin_round;               // a CONTINUE counts its own evaluations
-    const int64_t trip_end = C.trip + A.cap;
-    const bool entered = C.reopen || C.S.phase != NT_IDLE;
-#pragma unroll 1
-    while (C.reopen || (C.S.phase != NT_IDLE && C.trip < trip_end)) nt_round<KPAD, RES, NT_WARM, TG>(A_, C);
-    if (entered) {
-        __syncthreads();                                 // every thread has read sS0 before thread 0 writes
-        if (tid == 0) { C.S.fin_round = C.trip; A.st[k] = C.S; }
-    }
+#define NT_FUSED_LOOP(ARGS, MODE)                                                                                         \
+    NT_FUSED_ARGS(ARGS)                                                                                                   \
+    const int k = blockIdx.x, tid = threadIdx.x;                                                                          \
+    /* the chain's scalars go through LDS, as in the step kernels: the values live in vector registers */                 \
+    __shared__ NtChain sS0;                                                                                               \
+    __shared__ double sEps0;                                                                                              \
+    __shared__ uint64_t sSeed0;                                                                                           \
+    __shared__ int sPt0;                                                                                                  \
+    if (tid == 0) { sS0 = A.st[k]; sEps0 = A.eps[k]; sSeed0 = A.seeds[k]; sPt0 = A.pts[k]; }                              \
+    __syncthreads();                                                                                                      \
+    NtCarry C;                                                                                                            \
+    C.S = sS0; C.eps = sEps0; C.seed = sSeed0; C.pt = sPt0;                                                               \
+    C.flip = 0; C.staged = false;                                                                                         \
+    C.reopen = A.reopen != 0;                                                                                             \
+    C.trip = C.reopen ? 0 : C.S.fin_round;               /* a CONTINUE counts its own evaluations */                      \
+    const int64_t trip_end = C.trip + A.cap;                                                                              \
+    const bool entered = C.reopen || C.S.phase != NT_IDLE;                                                                \
+    _Pragma("unroll 1")                                                                                                   \
+    while (C.reopen || (C.S.phase != NT_IDLE && C.trip < trip_end)) nt_round<KPAD, RES, MODE, TG>(A_, C);                 \
+    if (entered) {                                                                                                        \
+        __syncthreads();                                 /* every thread has read sS0 before thread 0 writes */           \
+        if (tid == 0) { C.S.fin_round = C.trip; A.st[k] = C.S; }                                                          \
+    }                                                                                                                     \
     nt_publish(A, C.S.phase != NT_IDLE, A.K);
-}
 
-// one launch of the call: up to `cap` evaluations per chain, counted under "nuts_fused:<KPAD>:<res|stream>:<f|g0|g8|g16>"
-int32_t pf_launch_nuts_fused(pfmi_ctx *c, int64_t launch, int cap, bool reopen, hipStream_t s) {
+// One launch of a fused family (Family::kernel<KPAD, RES, TG>() is its kernel, Family::plan its plan name; Args: NtFusedArgs or a struct
+// that extends it): up to `cap` evaluations per chain, counted under "<plan>:<KPAD>:<res|stream>:<f|g0|g8|g16>"
+template <class Family, class Args>
+static int32_t nt_launch_fused(pfmi_ctx *c, Args &A, int64_t launch, int cap, bool reopen, hipStream_t s) {
     const TargetDev &T = c->target;
-    NtFusedArgs A;
     static_cast<NtArgs &>(A) = nt_args(c, launch, 0, reopen);
     A.tg = {T.mean.as<double>(), T.a.as<double>(), T.wd.as<double>(), T.g.as<double>(), T.offset};
     A.gout = c->hm_out.as<double>();
     A.cap = cap;
     const int tgs = T.kind == PFMI_TARGET_FUNNEL ? HM_TG_FUNNEL : T.rpad;
     PF_CHECK((T.kind == PFMI_TARGET_FUNNEL || T.kind == PFMI_TARGET_GAUSS) && (tgs == HM_TG_FUNNEL || tgs == 0 || tgs == 8 || tgs == 16), PFMI_ERR_UNSUPPORTED,
-             "nuts_fused: target kind %d with rank padding %d has no fused kernel", T.kind, T.rpad);
+             "%s: target kind %d with rank padding %d has no fused kernel", Family::plan, T.kind, T.rpad);
     const bool res = pf_hmc_resident(A.d, c->kpad);
     auto go = [&](auto KP, auto RES, auto TG) -> int32_t {
-        auto *kern = &pf_nuts_fused_kernel<KP(), RES(), TG()>;
+        auto *kern = Family::template kernel<KP(), RES(), TG()>();
         if (RES()) PF_TRY(pf_raise_lds_limit(c, reinterpret_cast<const void *>(kern), HM_LDS_RES));
-        char name[40], tn[8];
+        char name[48], tn[8];
         if (TG() == HM_TG_FUNNEL) snprintf(tn, sizeof tn, "f"); else snprintf(tn, sizeof tn, "g%d", (int)TG());
-        snprintf(name, sizeof name, "nuts_fused:%d:%s:%s", (int)KP(), RES() ? "res" : "stream", tn);
+        snprintf(name, sizeof name, "%s:%d:%s:%s", Family::plan, (int)KP(), RES() ? "res" : "stream", tn);
         ++c->hmc_plans[name];
         hipLaunchKernelGGL(kern, dim3(A.K), dim3(HM_NT), RES() ? (size_t)A.d * KP() * sizeof(double) : 0, s, A);
         return PFMI_OK;
@@ -100,3 +103,21 @@ int32_t pf_launch_nuts_fused(pfmi_ctx *c, int64_t launch, int cap, bool reopen, 
     PF_HIP(hipGetLastError());
     return PFMI_OK;
 }
+
+#ifndef PF_FUSED_METRIC_TU             // (nuts_fused_metric_kernel.hip takes the loop, NtFusedArgs and the launch from this file and defines its own kernel)
+template <int KPAD, bool RES, int TG>
+__global__ __launch_bounds__(HM_NT) void pf_nuts_fused_kernel(NtFusedArgs A_) {
+    NT_FUSED_LOOP(NtFusedArgs, NT_WARM)
+}
+
+struct NtFusedFamily {
+    static constexpr const char *plan = "nuts_fused";
+    template <int KPAD, bool RES, int TG>
+    static auto kernel() { return &pf_nuts_fused_kernel<KPAD, RES, TG>; }
+};
+
+int32_t pf_launch_nuts_fused(pfmi_ctx *c, int64_t launch, int cap, bool reopen, hipStream_t s) {
+    NtFusedArgs A;
+    return nt_launch_fused<NtFusedFamily>(c, A, launch, cap, reopen, s);
+}
+#endif

@@ -451,6 +451,10 @@ int32_t pf_nuts_chain_flags(pfmi_ctx *c, std::vector<int32_t> &dead, int64_t *la
 int32_t pf_launch_nuts_fused(pfmi_ctx *c, int64_t launch, int cap, bool reopen, hipStream_t s);
 // hmc_metric_kernel.hip, nuts_metric_kernel.hip: the step launch of chains that carry a scale (c->hmc.scaled), plain or adaptive
 int32_t pf_launch_hmc_metric_step(pfmi_ctx *c, int64_t round, hipStream_t s);
+// hmc_fused_metric_kernel.hip, nuts_fused_metric_kernel.hip: pf_launch_hmc_fused / pf_launch_nuts_fused for chains that carry a scale
+// (c->hmc.scaled) on a built-in target, plain or adaptive with metric windows
+int32_t pf_launch_hmc_fused_metric(pfmi_ctx *c, int64_t round, int ntrips, hipStream_t s);
+int32_t pf_launch_nuts_fused_metric(pfmi_ctx *c, int64_t launch, int cap, bool reopen, hipStream_t s);
 // chees_kernel.hip: round: the number the launch publishes with its progress word; prow: its row of the recorded path; reopen: the launch
 // that opens the next trajectory without reading the closure (after an update, or first in a CONTINUE).  _update: the three launches of
 // the cross-chain update, which do nothing unless the step launch before them ended a warm-up transition.

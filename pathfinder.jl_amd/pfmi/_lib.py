@@ -61,6 +61,7 @@ SYMBOLS = [
     "pfmi_chees_enqueue", "pfmi_chees_pump", "pfmi_chees_wait", "pfmi_chees_get", "pfmi_chees_get_update", "pfmi_chees_stats",
     "pfmi_host_chees_leapfrog", "pfmi_host_chees_update",
     "pfmi_hmc_fused_enqueue", "pfmi_nuts_fused_enqueue",
+    "pfmi_hmc_fused_metric_enqueue", "pfmi_nuts_fused_metric_enqueue",
 ]
 
 # declared argument types (entry points not listed here take what the caller wraps by hand)
@@ -101,6 +102,10 @@ ARGTYPES = {
     "pfmi_hmc_adapt_metric_enqueue": [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), _dp, C.POINTER(C.c_uint64), _dp, C.c_int32, C.c_int64,
                                       C.c_int64, C.c_double, C.c_int32],
     "pfmi_nuts_adapt_metric_enqueue": [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), _dp, C.POINTER(C.c_uint64), _dp, C.c_int32, C.c_int64,
+                                       C.c_int64, C.c_double, C.c_int32],
+    "pfmi_hmc_fused_metric_enqueue": [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), _dp, C.POINTER(C.c_uint64), _dp, C.c_int32, C.c_int64,
+                                      C.c_int64, C.c_double, C.c_int32],
+    "pfmi_nuts_fused_metric_enqueue": [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), _dp, C.POINTER(C.c_uint64), _dp, C.c_int32, C.c_int64,
                                        C.c_int64, C.c_double, C.c_int32],
     "pfmi_adapt_metric_get": [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64), _dp, _dp],
     "pfmi_adapt_windows": [C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_int32)],

@@ -554,6 +554,12 @@ class Engine:
         is BUILT IN (Gaussian family, funnel): logp and its gradient are evaluated inside the chain kernel, one workgroup per chain
         loops over the rounds of a launch (include/pfmi.h: pfmi_hmc_fused_enqueue).  hmc_wait, hmc_get, hmc_path, adapt_get and
         chain_diagnostics serve the run; hmc_stats reports its evaluations and 0 closure columns.  Does not wait."""
+        self._fused_enqueue("hmc_fused", points, x0, seeds, step_size, nleapfrog, ntransitions, nwarmup, target_accept, cont, record_path)
+
+    def _fused_enqueue(self, name, points, x0, seeds, step_size, param, ntransitions, nwarmup, target_accept, cont, record_path, metric=False,
+                       record_whitened=False):
+        """the one enqueue of the fused routes: pfmi_<name>_enqueue (name: hmc_fused, nuts_fused, and with metric=True hmc_fused_metric,
+        nuts_fused_metric, whose adaptive run has metric windows and takes record_whitened)"""
         points = np.ascontiguousarray(points, dtype=np.int64)
         K = len(points)
         seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
@@ -564,16 +570,26 @@ class Engine:
             x0 = np.asfortranarray(x0, dtype=np.float64)
             assert x0.shape == (self.d, K), (x0.shape, self.d, K)
             x0p = _d(x0)
-        flags = (self.HMC_CONTINUE if cont else 0) | (self.HMC_RECORD_PATH if record_path else 0)
-        check(self.L.pfmi_hmc_fused_enqueue(self.ctx, K, points.ctypes.data_as(_i64p), x0p, seeds.ctypes.data_as(C.POINTER(C.c_uint64)), _d(eps),
-                                            int(nleapfrog), int(nwarmup), int(ntransitions), float(target_accept), flags))
+        flags = (self.HMC_CONTINUE if cont else 0) | (self.HMC_RECORD_PATH if record_path else 0) | (self.ADAPT_RECORD_WHITENED if record_whitened else 0)
+        check(getattr(self.L, f"pfmi_{name}_enqueue")(self.ctx, K, points.ctypes.data_as(_i64p), x0p, seeds.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                      _d(eps), int(param), int(nwarmup), int(ntransitions), float(target_accept), flags))
         self._hmc = (K, int(ntransitions))
         self._chees = None
         if nwarmup:
-            self._adapt, self._metric = (K, int(nwarmup)), None
+            self._adapt, self._metric = (K, int(nwarmup)), ((K, int(nwarmup), bool(record_whitened)) if metric else None)
         elif not cont:
             self._adapt = self._metric = None
         self.hmc_runs += 1
+
+    def hmc_fused_metric_enqueue(self, points, x0, seeds, step_size, nleapfrog, ntransitions, nwarmup=0, target_accept=0.8, cont=False,
+                                 record_path=False, record_whitened=False):
+        """hmc_fused_enqueue for chains that carry a per-coordinate scale, and hmc_adapt_metric_enqueue on a BUILT-IN target (include/pfmi.h:
+        pfmi_hmc_fused_metric_enqueue).  nwarmup = 0: a plain run; a scale staged by chain_scale_set becomes the chains' resident one, and
+        cont=True goes on with the one they carry (from an adaptive run, say).  nwarmup >= 1: a fresh adaptive run whose warm-up also
+        adapts the scale in Stan's windows (cont and record_path must be False; record_whitened keeps the whitened rows); adapt_metric_get
+        serves it as well.  Below 20 warm-up transitions there is no window: the run is hmc_fused_enqueue's.  Does not wait."""
+        self._fused_enqueue("hmc_fused_metric", points, x0, seeds, step_size, nleapfrog, ntransitions, nwarmup, target_accept, cont, record_path,
+                            metric=True, record_whitened=record_whitened)
 
     # ---- chain diagnostics (include/pfmi.h: pfmi_chain_diagnostics) ---------------------------------------------------------------
     CHAIN_SRC_HMC, CHAIN_SRC_HOST, CHAIN_WITH_LP = 0, 1, 1
@@ -650,26 +666,15 @@ class Engine:
         builds its trees at its own pace over the trips of a launch (include/pfmi.h: pfmi_nuts_fused_enqueue).  nuts_pump, nuts_wait,
         nuts_get_stats, nuts_path, hmc_get, adapt_get and chain_diagnostics serve the run; nuts_stats reports the most trips a chain made
         and 0 closure columns.  Issues the first window of launches and returns."""
-        points = np.ascontiguousarray(points, dtype=np.int64)
-        K = len(points)
-        seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
-        eps = np.ascontiguousarray(np.broadcast_to(np.asarray(step_size, dtype=np.float64), (K,)))
-        assert seeds.shape == (K,)
-        x0p = None
-        if x0 is not None:
-            x0 = np.asfortranarray(x0, dtype=np.float64)
-            assert x0.shape == (self.d, K), (x0.shape, self.d, K)
-            x0p = _d(x0)
-        flags = (self.NUTS_CONTINUE if cont else 0) | (self.NUTS_RECORD_PATH if record_path else 0)
-        check(self.L.pfmi_nuts_fused_enqueue(self.ctx, K, points.ctypes.data_as(_i64p), x0p, seeds.ctypes.data_as(C.POINTER(C.c_uint64)), _d(eps),
-                                             int(max_depth), int(nwarmup), int(ntransitions), float(target_accept), flags))
-        self._hmc = (K, int(ntransitions))
-        self._chees = None
-        if nwarmup:
-            self._adapt, self._metric = (K, int(nwarmup)), None
-        elif not cont:
-            self._adapt = self._metric = None
-        self.hmc_runs += 1
+        self._fused_enqueue("nuts_fused", points, x0, seeds, step_size, max_depth, ntransitions, nwarmup, target_accept, cont, record_path)
+
+    def nuts_fused_metric_enqueue(self, points, x0, seeds, step_size, max_depth, ntransitions, nwarmup=0, target_accept=0.8, cont=False,
+                                  record_path=False, record_whitened=False):
+        """nuts_fused_enqueue for chains that carry a per-coordinate scale, and nuts_adapt_metric_enqueue on a BUILT-IN target
+        (include/pfmi.h: pfmi_nuts_fused_metric_enqueue): the arguments and rules of hmc_fused_metric_enqueue with max_depth in place of
+        the leapfrog count; nuts_pump / nuts_wait issue the launches."""
+        self._fused_enqueue("nuts_fused_metric", points, x0, seeds, step_size, max_depth, ntransitions, nwarmup, target_accept, cont, record_path,
+                            metric=True, record_whitened=record_whitened)
 
     # ---- device-resident warm-up (include/pfmi.h: pfmi_hmc_adapt_enqueue, pfmi_nuts_adapt_enqueue) -----------------------------------
     ADAPT_KEPT_STEP = 1

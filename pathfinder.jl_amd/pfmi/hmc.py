@@ -9,7 +9,8 @@ seeds and step-size adaptation.  The target must be a device closure with a grad
 TorchDeviceTarget(..., grad=...)); one engine only.  On a BUILT-IN target (t_iso, t_diag, t_lowrank, t_funnel, any GaussTarget /
 FunnelTarget) `hmc` takes the fused route instead (pfmi_hmc_fused_enqueue): the chain kernel evaluates logp and its gradient itself and
 loops over a run's rounds in one launch.  All three modes of `hmc` run there, and so does `nuts` with fused=True
-(pfmi_nuts_fused_enqueue); `chees` and adapt_metric=True do not.
+(pfmi_nuts_fused_enqueue); the metric windows run there as adapt_metric="fused" (pfmi_hmc_fused_metric_enqueue,
+pfmi_nuts_fused_metric_enqueue); `chees` does not, and adapt_metric=True stays the closure route's.
 
 The example's second way, "initialise a metric adaptation" from the fit, is adapt="device" with adapt_metric=True (include/pfmi.h:
 pfmi_hmc_adapt_metric_enqueue): the warm-up also learns a per-coordinate scale c of every chain in Stan's windows, in the coordinates
@@ -111,9 +112,9 @@ class HMCResult:
     engine: Any = field(repr=False, default=None)
     run: int = 0                      # engine.hmc_runs after this result's last hmc_enqueue (0: unknown)
     # adapt="device": the warm-up's traces (Engine.adapt_get: eps_trace, accept_trace, divergent, n_leapfrog (nchains, nwarmup), status)
-    # adapt_metric=True: also window_ends (nwin,) and scale_trace (nchains, nwin, d) (Engine.adapt_metric_get)
+    # adapt_metric=True / "fused": also window_ends (nwin,) and scale_trace (nchains, nwin, d) (Engine.adapt_metric_get)
     warmup: Any = field(default=None, kw_only=True)
-    # adapt_metric=True: (nchains, d) the per-coordinate scale the sampling phase used on the fit's factor (None: the fitted metric itself)
+    # adapt_metric=True / "fused": (nchains, d) the per-coordinate scale the sampling phase used on the fit's factor (None: the fitted metric itself)
     metric_scale: Any = field(default=None, kw_only=True)
 
     def summary(self):
@@ -163,8 +164,10 @@ def _starts_and_points(result):
 def _check_adapt(adapt, auto, nwarmup, adapt_metric=False):
     if adapt not in ("windows", "device"):
         raise ValueError('adapt must be "windows" or "device"')
+    if adapt_metric not in (False, True, "fused"):
+        raise ValueError('adapt_metric must be False, True or "fused"')
     if adapt_metric and adapt != "device":
-        raise ValueError('adapt_metric=True adapts the metric in the windows of the device warm-up: it needs adapt="device"')
+        raise ValueError('adapt_metric adapts the metric in the windows of the device warm-up: it needs adapt="device"')
     if adapt == "device" and not (auto and nwarmup >= 1):
         raise ValueError('adapt="device" adapts the step size during the warm-up: it needs step_size="auto" and nwarmup >= 1')
     return adapt == "device"
@@ -199,20 +202,24 @@ def _chains(name, result, nchains, rng, check_param=None, adapt_metric=False, fu
     if eng is None:
         raise ValueError(f"pfmi.{name} needs a result whose fits are still on an engine")
     eng.check_token(token, f"pfmi.{name}")
+    metric_fused = isinstance(adapt_metric, str)          # "fused" (_check_adapt refuses any other string before anything is enqueued)
+    if metric_fused and not _builtin(eng.target):
+        raise ValueError(f"pfmi.{name}: adapt_metric=\"fused\" needs a built-in target (pfmi.t_lowrank, t_diag, t_iso, t_funnel); a device closure "
+                         "target with a gradient adapts its metric with adapt_metric=True")
     if fused and not _builtin(eng.target):
         raise ValueError(f"pfmi.{name}: fused=True needs a built-in target (pfmi.t_lowrank, t_diag, t_iso, t_funnel); a device closure target "
                          "with a gradient runs with fused=False")
     if _builtin(eng.target):
-        if name == "nuts" and fused:
-            if adapt_metric:
+        if name == "nuts" and (fused or metric_fused):
+            if adapt_metric and not metric_fused:
                 raise ValueError("pfmi.nuts: adapt_metric=True needs a device closure target with a gradient; fused=True on a built-in target "
-                                 "samples with the fitted metric itself (adapt_metric=False)")
+                                 "samples with the fitted metric itself (adapt_metric=False) or adapts it with adapt_metric=\"fused\"")
         elif name != "hmc":
             raise ValueError(f"pfmi.{name} needs a device closure target with a gradient; on a built-in target static HMC is available "
                              "(pfmi.hmc: fixed step, adapt=\"windows\" and adapt=\"device\")")
-        if adapt_metric:
+        if adapt_metric and not metric_fused:
             raise ValueError("pfmi.hmc: adapt_metric=True needs a device closure target with a gradient; on a built-in target static HMC is "
-                             "available with the fitted metric itself (adapt_metric=False)")
+                             "available with the fitted metric itself (adapt_metric=False) or with adapt_metric=\"fused\"")
     elif not getattr(eng.target, "has_device_gradient", False):
         raise ValueError(f"pfmi.{name} needs a device closure target with a gradient (host closures and device closures without a gradient "
                          "are not supported; on built-in targets static HMC is available through pfmi.hmc)")
@@ -235,7 +242,10 @@ def _run(name, result, ndraws, nchains, nwarmup, step_size, param, rng, target_a
     eng, x0, pts, seeds = _chains(name, result, nchains, rng, check_param, adapt_metric, fused)
     d, nchains = x0.shape
     fused = _builtin(eng.target)                         # (static HMC, or NUTS with fused=True: _chains has refused everything else)
-    fenq = eng.nuts_fused_enqueue if is_nuts else eng.hmc_fused_enqueue
+    if isinstance(adapt_metric, str):                    # "fused": the metric windows inside the fused kernels
+        fenq = eng.nuts_fused_metric_enqueue if is_nuts else eng.hmc_fused_metric_enqueue
+    else:
+        fenq = eng.nuts_fused_enqueue if is_nuts else eng.hmc_fused_enqueue
     auto = isinstance(step_size, str)
     if auto and step_size != "auto":
         raise ValueError('step_size must be a number, an array of nchains numbers or "auto"')
@@ -298,7 +308,10 @@ def hmc(result, ndraws, *, nchains=None, nwarmup=0, step_size="auto", nleapfrog=
     transitions); `metric_scale` is the scale the sampling used, `warmup` also holds window_ends and scale_trace.
 
     On a built-in target (pfmi.t_lowrank, t_diag, t_iso, t_funnel) the run takes the fused route (pfmi_hmc_fused_enqueue) in all three
-    modes -- fixed step, adapt="windows", adapt="device" -- and returns the same HMCResult; adapt_metric=True raises ValueError there."""
+    modes -- fixed step, adapt="windows", adapt="device" -- and returns the same HMCResult; adapt_metric=True raises ValueError there.
+    adapt_metric="fused" (adapt="device", built-in targets only) is the metric adaptation on that route: the windows run inside the fused
+    kernel (pfmi_hmc_fused_metric_enqueue), and `metric_scale`, `warmup["window_ends"]` and `warmup["scale_trace"]` are filled as for
+    adapt_metric=True on a closure target; it raises ValueError on a closure target."""
     return _run("hmc", result, ndraws, nchains, nwarmup, step_size, nleapfrog, rng, target_accept, window, adapt, adapt_metric)
 
 
@@ -313,9 +326,11 @@ def nuts(result, ndraws, *, nchains=None, nwarmup=0, step_size="auto", max_depth
     fused=True, on a built-in target (pfmi.t_lowrank, t_diag, t_iso, t_funnel): the run takes the fused route (pfmi_nuts_fused_enqueue: the
     chain kernel evaluates logp and its gradient itself and every chain builds its trees at its own pace) in all three modes -- fixed step,
     adapt="windows", adapt="device" -- and returns the same NUTSResult.  It raises ValueError with adapt_metric=True and on a closure
-    target.  The default is False because pfmi.nuts on a built-in target has been pinned to raise; it will flip to the fused route on
+    target.  adapt_metric="fused" (adapt="device", built-in targets only) adapts the metric in windows inside the fused kernel
+    (pfmi_nuts_fused_metric_enqueue) and implies the fused route, with or without fused=True.  The default of `fused` is False because pfmi.nuts on a built-in target has been pinned to raise; it will flip to the fused route on
     built-in targets once that pin may be touched."""
-    return _run("nuts", result, ndraws, nchains, nwarmup, step_size, max_depth, rng, target_accept, window, adapt, adapt_metric, fused)
+    return _run("nuts", result, ndraws, nchains, nwarmup, step_size, max_depth, rng, target_accept, window, adapt, adapt_metric,
+                fused or isinstance(adapt_metric, str))
 
 
 @dataclass
